@@ -30,6 +30,10 @@ Prints ONE JSON line on rank 0.  Extra objects:
                   launch, its bound (mfma / hbm) and fraction, sorted by time per step.
   cpu_baseline -- the NumPy oracle (a port of the Chainer-CPU algorithm) timed on
                   this box's host cores on a bounded sample (N=1, rank 0 only).
+
+--dump-outputs DIR (e.g. bench_out/a) writes what the LAST TIMED step left to its
+caller as DIR/<name>.npy: model, inputs and step count are functions of the
+arguments alone, so two builds run with the same arguments compare file for file.
 """
 import argparse
 import json
@@ -45,7 +49,7 @@ import numpy as np  # noqa: E402
 CFG = dict(d=64, k=512, n_loop=2, n_layer=10, filter_size=2, input_dim=256, quantize=256,
            residual=256, dilated=256, skip=256, local_dim=64, global_dim=128, n_speaker=109,
            length=7680, beta=0.25, lr=2e-4, ema_mu=0.9999, batch_per_gpu=16)
-PEAK_FP32_MFMA_TFLOPS = 157.3       # /opt/skills/guides/MI355X_MICROARCH.md chip table
+PEAK_FP32_MFMA_TFLOPS = 157.3       # MI355X: dense fp32 matrix peak of the whole chip
 
 # The north star's kernel (`roofline`) and what one launch of it computes.  While the
 # residual 1x1 conv is a separate launch the extra term is 0.
@@ -396,6 +400,21 @@ def vq_stress_inputs(N, d, k):
     return rows, W
 
 
+DUMP_MAX_ELEMS = 4 << 20      # per array: 16 MB as float32 (a step leaves three arrays: under 64 MB together)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the last timed step left to its caller, one DIR/<name>.npy (float32) per array.  An array
+    of more than DUMP_MAX_ELEMS elements is stored as a sample at flat indices drawn from a fixed seed (sorted, with
+    repetition), which depend on its size only: two builds run with the same arguments write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).randint(0, a.size, DUMP_MAX_ELEMS))]
+        np.save(os.path.join(path, name + '.npy'), a.astype(np.float32))
+
+
 def run_c4(args, rank, n, local):
     """BASELINE configs[3]: large-codebook VQ stress, k=8192 d=128.  One step = one
     StraightThrough.forward (nearest code + gather, utils.py:176-211) over N latent rows laid out
@@ -440,6 +459,8 @@ def run_c4(args, rank, n, local):
     comm.barrier()
     dt = comm.max_scalar(time.perf_counter() - t0)
     lib.vqvae_prof_enable(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'idx': idx.get(), 'e': e.get()})
     tot, cnt = C.c_double(0), C.c_int(0)
     _lib.call('vqvae_prof_read', tag, C.byref(tot), C.byref(cnt))
     seen = comm.ranks_seen()
@@ -502,6 +523,10 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last of them left to its caller as DIR/<name>.npy (float32; '
+                         'rank 0): the three losses, the parameter arena (trained values, then the EMA shadows) and the '
+                         'gradient arena; c4: idx and e.  Arrays above 4 Mi elements as a fixed, seeded sample')
     ap.add_argument('--batch', type=int, default=CFG['batch_per_gpu'])
     ap.add_argument('--workload', choices=['c2', 'c4', 'c5'], default='c2',
                     help='c2: BASELINE configs[1]/[2] (softmax, 20 blocks, fp32) -- the metric config; '
@@ -659,6 +684,9 @@ def main():
     comm.barrier()
     dt = time.perf_counter() - t0
     lib.vqvae_prof_enable(0)
+    if args.dump_outputs and rank == 0:      # (here: the passes below step the model further)
+        dump_outputs(args.dump_outputs, {'losses': np.array([float(l.data.get()) for l in upd.last_losses]),
+                                         'params': opt.params.get(), 'grads': opt.grads.get()})
     roofline_pass = 'the timed steps'
     if use_graph:
         # per-launch time of the gate kernel: the same job, the same kernels, launched eagerly with the dispatch's own

@@ -51,15 +51,18 @@ def test_two_process_parallel_updater_on_one_gpu(gpu, tmp_path, mode):
             assert os.path.exists(os.path.join(d, 'ar_%d_rank%d.npy' % (step, r)))
 
 
-def test_bench_self_spawn_reaches_rccl(gpu):
+def test_bench_self_spawn_reaches_rccl(gpu, tmp_path):
     """`python bench.py --gpus N` from a bare shell spawns its own ranks and brings RCCL up: with
     one GPU on the test box that is N=1 with --force-comm (ncclCommInitRank, all-reduce of the
-    gradient arena every step, ncclCommCount reported in the JSON line)."""
+    gradient arena every step, ncclCommCount reported in the JSON line).  --dump-outputs leaves the
+    last timed step's losses (these steps are eager: the ones the line reports), parameters and
+    gradients as float32 files."""
     env = dict(os.environ)
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR'):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--force-comm',
-                          '--steps', '2', '--warmup', '1', '--batch', '2', '--no-cpu-baseline'],
+                          '--steps', '2', '--warmup', '1', '--batch', '2', '--no-cpu-baseline',
+                          '--dump-outputs', str(tmp_path / 'dump')],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith('{')]
@@ -67,6 +70,12 @@ def test_bench_self_spawn_reaches_rccl(gpu):
     rec = json.loads(lines[0])
     assert rec['n_gpus'] == 1 and rec['ranks_seen_by_rccl'] == [1, 1]
     assert rec['value'] > 0 and rec['roofline']['achieved'] > 0
+    dump = {f[:-4]: np.load(str(tmp_path / 'dump' / f)) for f in os.listdir(str(tmp_path / 'dump'))}
+    assert sorted(dump) == ['grads', 'losses', 'params']
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in dump.values())
+    np.testing.assert_array_equal(dump['losses'], np.array(rec['losses_last_step'], np.float32))
+    assert dump['grads'].size == min(rec['trainable_params'], 4 << 20) and np.any(dump['grads'] != 0)
+    assert dump['params'].size == 4 << 20 and sum(a.nbytes for a in dump.values()) <= 64e6
 
 
 def test_bench_two_ranks_spawned_from_bare_invocation(gpu):

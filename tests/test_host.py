@@ -352,6 +352,22 @@ def test_bench_traffic_is_null_when_the_profile_is_stale(monkeypatch, tmp_path):
     assert v is None and 'stale' in why
 
 
+def test_bench_dump_outputs_is_float32_and_samples_large_arrays_at_fixed_indices(monkeypatch, tmp_path):
+    """bench.py --dump-outputs: small arrays whole, in their shape; an array above the cap as a sample whose indices
+    depend on its size alone (two builds' dumps are compared element for element); everything as float32."""
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_MAX_ELEMS', 1000)
+    big = np.arange(5000, dtype=np.float64).reshape(50, 100)
+    for d, scale in (('a', 1.0), ('b', 2.0)):
+        bench.dump_outputs(str(tmp_path / d), {'idx': np.arange(12, dtype=np.int32).reshape(3, 4), 'big': big * scale})
+    idx, a, b = (np.load(str(tmp_path / f)) for f in ('a/idx.npy', 'a/big.npy', 'b/big.npy'))
+    assert idx.dtype == a.dtype == np.float32 and idx.shape == (3, 4)
+    np.testing.assert_array_equal(idx.reshape(-1), np.arange(12))
+    assert a.shape == (1000,) and len(np.unique(a)) > 800 and np.all(np.diff(a) >= 0)
+    np.testing.assert_array_equal(b, 2 * a)                    # the same elements of both
+    assert sorted(os.listdir(str(tmp_path / 'a'))) == ['big.npy', 'idx.npy']
+
+
 def test_bench_spawns_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher environment starts two ranks with RANK /
     LOCAL_RANK / WORLD_SIZE / MASTER_* / a shared rendezvous id and propagates failure (here the

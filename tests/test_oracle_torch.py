@@ -8,8 +8,18 @@ import pytest
 
 import vqvae_oracle as O
 
-torch = pytest.importorskip('torch')
-F = torch.nn.functional
+torch = F = None        # bound by _torch when the first test of this module runs
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _torch():
+    """torch is imported when a test of this module runs, not when the module is collected.  `-m gpu` collects
+    this module too, in the process that then runs the package's kernels, and a ROCm build of torch brings a HIP
+    runtime of its own under the soname libvqvae_hip.so links against: imported first, it is the runtime the
+    library gets, whatever release it was compiled for (a recorded step's first hipGraphLaunch segfaulted on it)."""
+    global torch, F
+    torch = pytest.importorskip('torch')
+    F = torch.nn.functional
 
 
 def _t(a, grad=False):
