@@ -13,6 +13,8 @@
 //   * the sampler runs on the device from caller-supplied uniform doubles (the numbers NumPy's
 //     global RNG would hand generate.py:117/136) and writes the next input vector in place.
 // Weights are read in their Chainer layout (no packing); 15.8 MB of fp32 weights stay L2/MALL resident.
+#include <algorithm>
+
 #include "common.h"
 
 namespace vq {
@@ -341,8 +343,8 @@ extern "C" int vqvae_wavenet_gen_step(const vqvae_gen_desc* d, vqvae_stream_t s)
 // through tagged 8-byte granules {float, step tag} written with one agent-scope store and gathered
 // by spinning loads (~1.8 us measured, tools/ubench/edge_latency.hip), and the weights stay L2-hot
 // because the launch never ends.
-//   * MEGA_G workgroups of 2 waves.  Wave 0 of every workgroup walks the dependency chain for the
-//     rows it owns (row r belongs to workgroup r % MEGA_G: one gate pair, two rows of every 256-row
+//   * G workgroups of 2 waves.  Wave 0 of every workgroup walks the dependency chain for the
+//     rows it owns (row r belongs to workgroup r % G: one gate pair, two rows of every 2G-row
 //     matrix -- a single wave issues one VALU instruction per 4 cycles, so the chain's instruction
 //     count IS its latency and is kept to a few hundred per stage); wave 1 computes, a step ahead
 //     and off the critical path, everything of the gate pre-activation that does not depend on
@@ -362,17 +364,37 @@ extern "C" int vqvae_wavenet_gen_step(const vqvae_gen_desc* d, vqvae_stream_t s)
 //     pre-activations; the parity tests hold the 1e-4 fp32 bar against the oracle's plain order).
 // The global sequential dependency (nothing of step t+1 can be produced before the sample of step
 // t, which needs every workgroup's step-t rows) makes single-buffered mailboxes race-free.
+//   * Two width classes, both compile-time (the chain wave's instruction count is its latency):
+//     MegaNarrow = 128 workgroups, vectors of <= 256 channels (4 elements per lane), the 15.8 MB of a
+//     256-channel decoder stay L2-hot; MegaWide = 256 workgroups, vectors of <= 512 channels
+//     (8 per lane), condition <= 640 (10 per lane), gate half <= 256: the reference's default decoder
+//     (params.py: 512 / 512 / 256, condition 640), whose ~150 MB of packed records are streamed once
+//     per step, one block ahead of the chain.  Same protocol, same record order, wider records.
 // =================================================================================================
 namespace vq {
 
-constexpr int MEGA_G = 128;         // workgroups; rows are dealt round-robin
-constexpr int MEGA_RJ = 2;          // rows per workgroup per 256-row matrix
+struct MegaNarrow {                 // <= 256 channels per vector, dilated <= 256
+  static constexpr int G = 128;     // workgroups; rows are dealt round-robin
+  static constexpr int VI = 4;      // vector elements per lane: residual, skip, out_dim
+  static constexpr int CVI = 4;     // condition elements per lane
+  static constexpr int HV = 2;      // gate-half (z) elements per lane in the packed rows
+};
+struct MegaWide {                   // <= 512 channels per vector, dilated <= 512, condition <= 640
+  static constexpr int G = 256;
+  static constexpr int VI = 8;
+  static constexpr int CVI = 10;
+  static constexpr int HV = 4;
+};
+constexpr int MEGA_RJ = 2;          // rows per workgroup per 2G-row matrix
 constexpr int MEGA_PJ = 1;          // gate pairs per workgroup
 constexpr int MEGA_NHELP = 1;       // helper waves per workgroup
 constexpr int MEGA_THREADS = 64 * (1 + MEGA_NHELP);
-constexpr int MEGA_VI = 4;          // vector elements per lane (<= 256 channels)
+constexpr int MEGA_ZV = 4;          // elements per lane gathered from a z mailbox (gate half <= 256)
 constexpr int MEGA_MAXL = 64;
 constexpr int MEGA_SPIN_LIMIT = 1 << 22;
+// float4s per lane in a chain / helper record
+template <class C> constexpr int mega_crec() { return (2 * C::VI + 2 * C::HV + 2 * MEGA_RJ * C::HV) / 4; }
+template <class C> constexpr int mega_hrec() { return (2 * C::VI + 2 * C::CVI) / 4; }
 
 struct MegaBlock {
   const float *conv_W, *conv_b, *cond_W, *cond_b, *res_W, *res_b, *skip_W, *skip_b;
@@ -385,9 +407,9 @@ struct MegaQ { long qoff; int dilation, pad_; };     // what the step loop needs
 struct MegaArgs {
   const MegaBlock* blk;
   const MegaQ* qt;
-  const float4* crec;    // chain-wave weight records  [L][MEGA_G][64 lanes][4 x float4]
-  const float4* hrec;    // helper-wave weight records [L][MEGA_G][64 lanes][4 x float4]
-  const float4* brec;    // biases [L][MEGA_G][2 x float4]: {bR0, bR1, bS0, bS1}, {conv_b+cond_b of the pair, 0, 0}
+  const float4* crec;    // chain-wave weight records  [L][G][64 lanes][mega_crec x float4]
+  const float4* hrec;    // helper-wave weight records [L][G][64 lanes][mega_hrec x float4]
+  const float4* brec;    // biases [L][G][2 x float4]: {bR0, bR1, bS0, bS1}, {conv_b+cond_b of the pair, cb0, cb1}
   const float *embed_W, *embed_b, *proj1_W, *proj1_b, *proj2_W, *proj2_b;
   const float* cond; long cond_bstride, cond_cstride;
   const double* uniforms; const void* forced; void* out; long out_bstride; float* logits_out;
@@ -412,19 +434,20 @@ __device__ __forceinline__ void mega_abort(int* status, int code) {
   __hip_atomic_store(status, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Gathers K (<= 64*MEGA_VI) granules carrying `tag`: element k = lane + 64 i lands in v[i].
-__device__ __forceinline__ bool mega_gather(const gran_t* box, int K, uint32_t tag, float (&v)[MEGA_VI], int* status) {
+// Gathers K (<= 64*VI) granules carrying `tag`: element k = lane + 64 i lands in v[i].
+template <int VI>
+__device__ __forceinline__ bool mega_gather(const gran_t* box, int K, uint32_t tag, float (&v)[VI], int* status) {
   const int lane = threadIdx.x & 63;
   unsigned pending = 0;
 #pragma unroll
-  for (int i = 0; i < MEGA_VI; ++i) { v[i] = 0.f; if (lane + 64 * i < K) pending |= 1u << i; }
+  for (int i = 0; i < VI; ++i) { v[i] = 0.f; if (lane + 64 * i < K) pending |= 1u << i; }
   int spins = 0;
   for (;;) {
-    gran_t g[MEGA_VI];
+    gran_t g[VI];
 #pragma unroll
-    for (int i = 0; i < MEGA_VI; ++i) if (pending & (1u << i)) g[i] = g_get(box + lane + 64 * i);
+    for (int i = 0; i < VI; ++i) if (pending & (1u << i)) g[i] = g_get(box + lane + 64 * i);
 #pragma unroll
-    for (int i = 0; i < MEGA_VI; ++i)
+    for (int i = 0; i < VI; ++i)
       if ((pending & (1u << i)) && (uint32_t)(g[i] >> 32) == tag) { v[i] = __uint_as_float((uint32_t)g[i]); pending &= ~(1u << i); }
     if (__all(pending == 0)) return true;
     if ((++spins & 255) == 0) {
@@ -498,80 +521,113 @@ __device__ __forceinline__ float mega_gate(float h0, float h1) {          // tan
 typedef const __attribute__((address_space(1))) float* gfp_t;    // pointers read from the block table are
 #define GF(p) ((gfp_t)(p))                                          // generic: make the loads global_load again
 
+template <class C>
 struct MegaBlkW {                    // record l: what the chain wave needs once z_l has arrived
-  float wU[2][MEGA_VI];              // conv tap 1 of block l+1, its gate pair rows (shadow term Wc1_{l+1} x_l)
-  float wM[2][2];                    // M_l = Wc1_{l+1} Wr_l, the same two rows, k = lane + 64 i
-  float wR[MEGA_RJ][2], wS[MEGA_RJ][2];
+  float wU[2][C::VI];                // conv tap 1 of block l+1, its gate pair rows (shadow term Wc1_{l+1} x_l)
+  float wM[2][C::HV];                // M_l = Wc1_{l+1} Wr_l, the same two rows, k = lane + 64 i
+  float wR[MEGA_RJ][C::HV], wS[MEGA_RJ][C::HV];
   float bR[MEGA_RJ], bS[MEGA_RJ], cb[2];   // cb = Wc1_{l+1} br_l
 };
-constexpr int MEGA_CREC = 5;         // float4 per lane in a chain record
-static_assert(MEGA_PJ == 1 && MEGA_RJ == 2 && MEGA_VI == 4, "the packed weight records are laid out for 1 pair / 2 rows / 4 elements per lane");
-__device__ __forceinline__ void mega_load_blk(MegaBlkW& w, const MegaArgs& a, int l, int g, int lane) {
-  const float4* rec = a.crec + ((size_t)(l * MEGA_G + g) * 64 + lane) * MEGA_CREC;
-  const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3], r4 = rec[4];
-  const float4 bq = a.brec[(size_t)(l * MEGA_G + g) * 2], bc = a.brec[(size_t)(l * MEGA_G + g) * 2 + 1];
-  w.wU[0][0] = r0.x; w.wU[0][1] = r0.y; w.wU[0][2] = r0.z; w.wU[0][3] = r0.w;
-  w.wU[1][0] = r1.x; w.wU[1][1] = r1.y; w.wU[1][2] = r1.z; w.wU[1][3] = r1.w;
-  w.wM[0][0] = r2.x; w.wM[0][1] = r2.y; w.wM[1][0] = r2.z; w.wM[1][1] = r2.w;
-  w.wR[0][0] = r3.x; w.wR[0][1] = r3.y; w.wR[1][0] = r3.z; w.wR[1][1] = r3.w;
-  w.wS[0][0] = r4.x; w.wS[0][1] = r4.y; w.wS[1][0] = r4.z; w.wS[1][1] = r4.w;
+static_assert(MEGA_PJ == 1 && MEGA_RJ == 2, "the packed weight records are laid out for 1 gate pair / 2 rows per workgroup");
+// A lane's record: wU[2][VI] | wM[2][HV] | wR[2][HV] | wS[2][HV], as whole float4s.
+template <class C>
+__device__ __forceinline__ void mega_load_blk(MegaBlkW<C>& w, const MegaArgs& a, int l, int g, int lane) {
+  constexpr int NQ = mega_crec<C>(), VI = C::VI, HV = C::HV;
+  const float4* rec = a.crec + ((size_t)(l * C::G + g) * 64 + lane) * NQ;
+  float4 r[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) r[q] = rec[q];
+  const float4 bq = a.brec[(size_t)(l * C::G + g) * 2], bc = a.brec[(size_t)(l * C::G + g) * 2 + 1];
+  float f[4 * NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) { f[4 * q] = r[q].x; f[4 * q + 1] = r[q].y; f[4 * q + 2] = r[q].z; f[4 * q + 3] = r[q].w; }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+#pragma unroll
+    for (int i = 0; i < VI; ++i) w.wU[h][i] = f[h * VI + i];
+#pragma unroll
+    for (int i = 0; i < HV; ++i) {
+      w.wM[h][i] = f[2 * VI + h * HV + i];
+      w.wR[h][i] = f[2 * VI + 2 * HV + h * HV + i];
+      w.wS[h][i] = f[2 * VI + 4 * HV + h * HV + i];
+    }
+  }
   w.bR[0] = bq.x; w.bR[1] = bq.y; w.bS[0] = bq.z; w.bS[1] = bq.w;
   w.cb[0] = bc.z; w.cb[1] = bc.w;
 }
+// Row of a 1x1 matrix times z (k = lane + 64 i), before the wave sum: pairs first, as the narrow
+// class has always summed them.
+template <int HV>
+__device__ __forceinline__ float mega_dot_z(const float (&w)[HV], const float (&z)[MEGA_ZV]) {
+  static_assert(HV == 2 || HV == 4, "gate half of 128 or 256 channels");
+  if constexpr (HV == 2) return w[0] * z[0] + w[1] * z[1];
+  else return (w[0] * z[0] + w[1] * z[1]) + (w[2] * z[2] + w[3] * z[3]);
+}
 
-// One-off repack of the Chainer-layout weights into per-(block, workgroup, lane) records (four or
-// five coalesced 16-byte loads per lane fetch a block), including the composite matrices.
+// One-off repack of the Chainer-layout weights into per-(block, workgroup, lane) records (a few
+// coalesced 16-byte loads per lane fetch a block), including the composite matrices.
+template <class C>
 __global__ __launch_bounds__(64) void gen_mega_pack_kernel(const MegaBlock* blk, int L, int R, int half, int S, int Cc,
                                                            float4* crec, float4* hrec, float4* brec) {
-  const int l = blockIdx.x / MEGA_G, g = blockIdx.x % MEGA_G, lane = threadIdx.x;
+  constexpr int G = C::G, VI = C::VI, CVI = C::CVI, HV = C::HV, NQC = mega_crec<C>(), NQH = mega_hrec<C>();
+  const int l = blockIdx.x / G, g = blockIdx.x % G, lane = threadIdx.x;
   const MegaBlock bk = blk[l];
   const bool last = l == L - 1;
   const MegaBlock bn = blk[last ? l : l + 1];
-  float c[20], h[16];
+  float c[4 * NQC], h[4 * NQH];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < VI; ++i) {
     const int k = lane + 64 * i;
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
       const int row = g + hh * half;
       const bool ok = g < half && k < R;
-      c[hh * 4 + i] = (ok && !last) ? bn.conv_W[((size_t)row * R + k) * 2 + 1] : 0.f;   // tap 1 of block l+1
-      h[hh * 4 + i] = ok ? bk.conv_W[((size_t)row * R + k) * 2] : 0.f;                  // tap 0 of block l
-      h[8 + hh * 4 + i] = (g < half && k < Cc) ? bk.cond_W[(size_t)row * Cc + k] : 0.f;
+      c[hh * VI + i] = (ok && !last) ? bn.conv_W[((size_t)row * R + k) * 2 + 1] : 0.f;   // tap 1 of block l+1
+      h[hh * VI + i] = ok ? bk.conv_W[((size_t)row * R + k) * 2] : 0.f;                  // tap 0 of block l
     }
+  }
+#pragma unroll
+  for (int i = 0; i < CVI; ++i) {
+    const int k = lane + 64 * i;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh)
+      h[2 * VI + hh * CVI + i] = (g < half && k < Cc) ? bk.cond_W[(size_t)(g + hh * half) * Cc + k] : 0.f;
   }
   double cbv[2] = {0.0, 0.0};
 #pragma unroll
   for (int hh = 0; hh < 2; ++hh) {
     const int row = g + hh * half;
-    double m0 = 0.0, m1 = 0.0;
+    double m[HV];
+#pragma unroll
+    for (int i = 0; i < HV; ++i) m[i] = 0.0;
     if (!last && g < half) {
       for (int cc = 0; cc < R; ++cc) {
         const double w = (double)bn.conv_W[((size_t)row * R + cc) * 2 + 1];
-        if (lane < half) m0 += w * (double)bk.res_W[(size_t)cc * half + lane];
-        if (lane + 64 < half) m1 += w * (double)bk.res_W[(size_t)cc * half + lane + 64];
+#pragma unroll
+        for (int i = 0; i < HV; ++i)
+          if (lane + 64 * i < half) m[i] += w * (double)bk.res_W[(size_t)cc * half + lane + 64 * i];
         cbv[hh] += w * (double)bk.res_b[cc];
       }
     }
-    c[8 + hh * 2] = (float)m0;
-    c[8 + hh * 2 + 1] = (float)m1;
+#pragma unroll
+    for (int i = 0; i < HV; ++i) c[2 * VI + hh * HV + i] = (float)m[i];
   }
 #pragma unroll
   for (int j = 0; j < 2; ++j)
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int r = g + MEGA_G * j, k = lane + 64 * i;
-      c[12 + j * 2 + i] = (!last && r < R && k < half) ? bk.res_W[(size_t)r * half + k] : 0.f;
-      c[16 + j * 2 + i] = (r < S && k < half) ? bk.skip_W[(size_t)r * half + k] : 0.f;
+    for (int i = 0; i < HV; ++i) {
+      const int r = g + G * j, k = lane + 64 * i;
+      c[2 * VI + 2 * HV + j * HV + i] = (!last && r < R && k < half) ? bk.res_W[(size_t)r * half + k] : 0.f;
+      c[2 * VI + 4 * HV + j * HV + i] = (r < S && k < half) ? bk.skip_W[(size_t)r * half + k] : 0.f;
     }
-  float4* cr = crec + ((size_t)blockIdx.x * 64 + lane) * MEGA_CREC;
-  float4* hr = hrec + ((size_t)blockIdx.x * 64 + lane) * 4;
+  float4* cr = crec + ((size_t)blockIdx.x * 64 + lane) * NQC;
+  float4* hr = hrec + ((size_t)blockIdx.x * 64 + lane) * NQH;
 #pragma unroll
-  for (int q = 0; q < MEGA_CREC; ++q) cr[q] = make_float4(c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]);
+  for (int q = 0; q < NQC; ++q) cr[q] = make_float4(c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]);
 #pragma unroll
-  for (int q = 0; q < 4; ++q) hr[q] = make_float4(h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]);
+  for (int q = 0; q < NQH; ++q) hr[q] = make_float4(h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]);
   if (lane == 0) {
-    const int r0 = g, r1 = g + MEGA_G;
+    const int r0 = g, r1 = g + G;
     brec[(size_t)blockIdx.x * 2] = make_float4((!last && r0 < R) ? bk.res_b[r0] : 0.f, (!last && r1 < R) ? bk.res_b[r1] : 0.f,
                                                r0 < S ? bk.skip_b[r0] : 0.f, r1 < S ? bk.skip_b[r1] : 0.f);
     brec[(size_t)blockIdx.x * 2 + 1] = make_float4(g < half ? bk.conv_b[g] + bk.cond_b[g] : 0.f,
@@ -581,27 +637,28 @@ __global__ __launch_bounds__(64) void gen_mega_pack_kernel(const MegaBlock* blk,
 }
 
 // All sequences' vectors of one mailbox in a single polling loop (element k = lane + 64 i of sequence b).
-template <int NB>
+template <int NB, int VI>
 __device__ __forceinline__ bool mega_gather_n(const gran_t* box, size_t bstride, int n, int K, uint32_t tag,
-                                              float (&v)[NB][MEGA_VI], int* status) {
+                                              float (&v)[NB][VI], int* status) {
+  static_assert(NB * VI <= 32, "one pending bit per element");
   const int lane = threadIdx.x & 63;
   unsigned pending = 0;
 #pragma unroll
   for (int b = 0; b < NB; ++b)
 #pragma unroll
-    for (int i = 0; i < MEGA_VI; ++i) { v[b][i] = 0.f; if (b < n && lane + 64 * i < K) pending |= 1u << (b * MEGA_VI + i); }
+    for (int i = 0; i < VI; ++i) { v[b][i] = 0.f; if (b < n && lane + 64 * i < K) pending |= 1u << (b * VI + i); }
   int spins = 0;
   for (;;) {
-    gran_t gr[NB][MEGA_VI];
+    gran_t gr[NB][VI];
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
-      for (int i = 0; i < MEGA_VI; ++i) if (pending & (1u << (b * MEGA_VI + i))) gr[b][i] = g_get(box + b * bstride + lane + 64 * i);
+      for (int i = 0; i < VI; ++i) if (pending & (1u << (b * VI + i))) gr[b][i] = g_get(box + b * bstride + lane + 64 * i);
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
-      for (int i = 0; i < MEGA_VI; ++i) {
-        const unsigned bit = 1u << (b * MEGA_VI + i);
+      for (int i = 0; i < VI; ++i) {
+        const unsigned bit = 1u << (b * VI + i);
         if ((pending & bit) && (uint32_t)(gr[b][i] >> 32) == tag) { v[b][i] = __uint_as_float((uint32_t)gr[b][i]); pending &= ~bit; }
       }
     if (__all(pending == 0)) return true;
@@ -613,12 +670,14 @@ __device__ __forceinline__ bool mega_gather_n(const gran_t* box, size_t bstride,
 }
 
 // NB = sequences the code is unrolled for; EXACT: n == NB is known at compile time (no per-sequence tests)
-template <int NB, bool EXACT>
+// C = width class (MegaNarrow / MegaWide)
+template <class C, int NB, bool EXACT>
 __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
+  constexpr int G = C::G, VI = C::VI, CVI = C::CVI;
   __shared__ float pre_s[MEGA_MAXL][MEGA_PJ][2][NB];
   __shared__ int ready_s[MEGA_MAXL];
   __shared__ int consumed_s[MEGA_MAXL];
-  __shared__ float lg_s[NB][64 * MEGA_VI];
+  __shared__ float lg_s[NB][64 * VI];
   const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = EXACT ? NB : a.n, R = a.R, half = a.D >> 1, S = a.S, O = a.O;
   for (int i = threadIdx.x; i < MEGA_MAXL; i += MEGA_THREADS) { ready_s[i] = a.t0; consumed_s[i] = a.t0; }
@@ -627,11 +686,11 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
   if (wave != 0) {
     // ---------------- helper waves: step-independent part of the gate pre-activation -------------
     for (int s = a.t0; s < a.t0 + a.steps; ++s) {
-      float cv[NB][MEGA_VI];
+      float cv[NB][CVI];
 #pragma unroll
       for (int b = 0; b < NB; ++b)
 #pragma unroll
-        for (int i = 0; i < MEGA_VI; ++i) {
+        for (int i = 0; i < CVI; ++i) {
           const int k = lane + 64 * i;
           cv[b][i] = (b < n && k < a.Cc) ? a.cond[b * a.cond_bstride + k * a.cond_cstride + s] : 0.f;
         }
@@ -639,22 +698,31 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
         const MegaQ bk = a.qt[l];
         const int d = bk.dilation;
         // weights and biases first: they do not depend on anything
-        float w0[MEGA_PJ][2][MEGA_VI], wc[MEGA_PJ][2][MEGA_VI], bb[MEGA_PJ][2];
+        float w0[MEGA_PJ][2][VI], wc[MEGA_PJ][2][CVI], bb[MEGA_PJ][2];
         {
-          const float4* rec = a.hrec + ((size_t)(l * MEGA_G + g) * 64 + lane) * 4;
-          const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
-          const float4 bq = a.brec[(size_t)(l * MEGA_G + g) * 2 + 1];
-          w0[0][0][0] = r0.x; w0[0][0][1] = r0.y; w0[0][0][2] = r0.z; w0[0][0][3] = r0.w;
-          w0[0][1][0] = r1.x; w0[0][1][1] = r1.y; w0[0][1][2] = r1.z; w0[0][1][3] = r1.w;
-          wc[0][0][0] = r2.x; wc[0][0][1] = r2.y; wc[0][0][2] = r2.z; wc[0][0][3] = r2.w;
-          wc[0][1][0] = r3.x; wc[0][1][1] = r3.y; wc[0][1][2] = r3.z; wc[0][1][3] = r3.w;
+          constexpr int NQ = mega_hrec<C>();     // a lane's record: w0[2][VI] | wc[2][CVI]
+          const float4* rec = a.hrec + ((size_t)(l * G + g) * 64 + lane) * NQ;
+          float4 r[NQ];
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) r[q] = rec[q];
+          const float4 bq = a.brec[(size_t)(l * G + g) * 2 + 1];
+          float f[4 * NQ];
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) { f[4 * q] = r[q].x; f[4 * q + 1] = r[q].y; f[4 * q + 2] = r[q].z; f[4 * q + 3] = r[q].w; }
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+#pragma unroll
+            for (int i = 0; i < VI; ++i) w0[0][h][i] = f[h * VI + i];
+#pragma unroll
+            for (int i = 0; i < CVI; ++i) wc[0][h][i] = f[2 * VI + h * CVI + i];
+          }
           bb[0][0] = bq.x; bb[0][1] = bq.y;
         }
-        float xo[NB][MEGA_VI];
+        float xo[NB][VI];
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
 #pragma unroll
-          for (int i = 0; i < MEGA_VI; ++i) xo[b][i] = 0.f;
+          for (int i = 0; i < VI; ++i) xo[b][i] = 0.f;
           if (b < n && s - d >= 0) {
             const gran_t* q = a.xq + bk.qoff + ((size_t)((s - d) % (d + 1)) * n + b) * R;
             if (!mega_gather(q, R, (uint32_t)(s - d + 1), xo[b], a.status)) return;
@@ -667,10 +735,14 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
           for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
-              if (b >= n || g + MEGA_G * j >= half) continue;
+              if (b >= n || g + G * j >= half) continue;
               float acc = 0.f;
 #pragma unroll
-              for (int i = 0; i < MEGA_VI; ++i) acc += w0[j][h][i] * xo[b][i] + wc[j][h][i] * cv[b][i];
+              for (int i = 0; i < (VI > CVI ? VI : CVI); ++i) {
+                if (i < VI && i < CVI) acc += w0[j][h][i] * xo[b][i] + wc[j][h][i] * cv[b][i];
+                else if (i < VI) acc += w0[j][h][i] * xo[b][i];
+                else acc += wc[j][h][i] * cv[b][i];
+              }
               acc = mega_wave_sum(acc) + bb[j][h];
               if (lane == 0) pre_s[l][j][h][b] = acc;
             }
@@ -705,11 +777,11 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
     }
   }
   // step-invariant registers: embed bias, head weights and biases, block 0's tap-1 rows
-  float bE[MEGA_RJ], b1[MEGA_RJ], b2[MEGA_RJ], w1[MEGA_RJ][MEGA_VI], w2[MEGA_RJ][MEGA_VI], wU0[2][MEGA_VI], bEf[MEGA_VI];
+  float bE[MEGA_RJ], b1[MEGA_RJ], b2[MEGA_RJ], w1[MEGA_RJ][VI], w2[MEGA_RJ][VI], wU0[2][VI], bEf[VI];
   {
     const MegaBlock bk0 = a.blk[0];
 #pragma unroll
-    for (int i = 0; i < MEGA_VI; ++i) {
+    for (int i = 0; i < VI; ++i) {
       const int k = lane + 64 * i;
       bEf[i] = k < R ? a.embed_b[k] : 0.f;
 #pragma unroll
@@ -718,23 +790,23 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
   }
 #pragma unroll
   for (int j = 0; j < MEGA_RJ; ++j) {
-    const int r = g + MEGA_G * j;
+    const int r = g + G * j;
     bE[j] = r < R ? a.embed_b[r] : 0.f;
     b1[j] = r < S ? a.proj1_b[r] : 0.f;
     b2[j] = r < O ? a.proj2_b[r] : 0.f;
 #pragma unroll
-    for (int i = 0; i < MEGA_VI; ++i) {
+    for (int i = 0; i < VI; ++i) {
       const int k = lane + 64 * i;
       w1[j][i] = (r < S && k < S) ? a.proj1_W[(size_t)r * S + k] : 0.f;
       w2[j][i] = (r < O && k < S) ? a.proj2_W[(size_t)r * S + k] : 0.f;
     }
   }
-  MegaBlkW cur, nxt;
-  mega_load_blk(cur, a, 0, g, lane);
+  MegaBlkW<C> cur, nxt;
+  mega_load_blk<C>(cur, a, 0, g, lane);
 
   for (int t = a.t0; t < a.t0 + a.steps; ++t) {
     const uint32_t tag = (uint32_t)t + 1u;
-    float xown[MEGA_RJ][NB], sacc[MEGA_RJ][NB], xf[NB][MEGA_VI];
+    float xown[MEGA_RJ][NB], sacc[MEGA_RJ][NB], xf[NB][VI];
     // ---- embed (modules.py:247-248) on [input(t-1), input(t)]: a function of the two fed-back
     //      values only, so every workgroup rebuilds the whole x_0 itself -- no hand-off ----
     {
@@ -743,7 +815,7 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
 #pragma unroll
-        for (int i = 0; i < MEGA_VI; ++i) {
+        for (int i = 0; i < VI; ++i) {
           const int k = lane + 64 * i;
           float e0 = 0.f, e1 = 0.f;
           if (b < n && k < R) {
@@ -761,10 +833,10 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
         }
 #pragma unroll
         for (int j = 0; j < MEGA_RJ; ++j) {
-          const int r = g + MEGA_G * j;             // x_0[r] sits in lane r % 64, element r / 64
+          const int r = g + G * j;             // x_0[r] sits in lane r % 64, element r / 64
           float v = 0.f;
 #pragma unroll
-          for (int i = 0; i < MEGA_VI; ++i) if (r / 64 == i) v = __shfl(xf[b][i], r & 63, 64);
+          for (int i = 0; i < VI; ++i) if (r / 64 == i) v = __shfl(xf[b][i], r & 63, 64);
           xown[j][b] = v; sacc[j][b] = 0.f;
           if (r < R && b < n && lane == 0) g_put(q + (size_t)b * R + r, v, tag);      // queue entry for the helpers
         }
@@ -777,7 +849,7 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
       if (b >= n || g >= half) continue;
       float h0 = 0.f, h1 = 0.f;
 #pragma unroll
-      for (int i = 0; i < MEGA_VI; ++i) { h0 += wU0[0][i] * xf[b][i]; h1 += wU0[1][i] * xf[b][i]; }
+      for (int i = 0; i < VI; ++i) { h0 += wU0[0][i] * xf[b][i]; h1 += wU0[1][i] * xf[b][i]; }
       h0 = mega_wave_sum(h0) + pre_s[0][0][0][b];
       h1 = mega_wave_sum(h1) + pre_s[0][0][1][b];
       if (lane == 0) g_put(a.zbox + (size_t)b * half + g, mega_gate(h0, h1), tag);
@@ -787,7 +859,7 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
     // ---- residual blocks (modules.py:102-110), one critical hand-off each: z_l ----
     for (int l = 0; l < a.L; ++l) {
       const bool has_next = l + 1 < a.L;
-      mega_load_blk(nxt, a, has_next ? l + 1 : 0, g, lane);       // lands while z_l is awaited
+      mega_load_blk<C>(nxt, a, has_next ? l + 1 : 0, g, lane);       // lands while z_l is awaited
       // shadow of the z_l hand-off: the x_l term of the next gate, u = Wc1_{l+1} x_l
       float u[2][NB];
 #pragma unroll
@@ -796,7 +868,7 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
         if (l > 0) {
           const MegaQ bk = a.qt[l];
           const gran_t* q = a.xq + bk.qoff + (size_t)(t % (bk.dilation + 1)) * n * R;
-          if (!mega_gather_n<NB>(q, R, n, R, tag, xf, a.status)) return;
+          if (!mega_gather_n(q, R, n, R, tag, xf, a.status)) return;
         }
         MP_T(1);
 #pragma unroll
@@ -804,15 +876,15 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
           if (b >= n || g >= half) continue;
           float u0 = 0.f, u1 = 0.f;
 #pragma unroll
-          for (int i = 0; i < MEGA_VI; ++i) { u0 += cur.wU[0][i] * xf[b][i]; u1 += cur.wU[1][i] * xf[b][i]; }
+          for (int i = 0; i < VI; ++i) { u0 += cur.wU[0][i] * xf[b][i]; u1 += cur.wU[1][i] * xf[b][i]; }
           u[0][b] = mega_wave_sum(u0);
           u[1][b] = mega_wave_sum(u1);
         }
       }
       MP_T(2);
       // the critical hand-off
-      float zv[NB][MEGA_VI];
-      if (!mega_gather_n<NB>(a.zbox + (size_t)l * n * half, half, n, half, tag, zv, a.status)) return;
+      float zv[NB][MEGA_ZV];
+      if (!mega_gather_n(a.zbox + (size_t)l * n * half, half, n, half, tag, zv, a.status)) return;
       MP_T(3);
       if (has_next) {
         // own rows of x_{l+1} = Wr z + br + x_l (modules.py:52-54): published first, they are cheap
@@ -821,11 +893,11 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
         gran_t* qn = a.xq + bn.qoff + (size_t)(t % (bn.dilation + 1)) * n * R;
 #pragma unroll
         for (int j = 0; j < MEGA_RJ; ++j) {
-          const int r = g + MEGA_G * j;
+          const int r = g + G * j;
 #pragma unroll
           for (int b = 0; b < NB; ++b) {
             if (b >= n || r >= R) continue;
-            const float dot = mega_wave_sum(cur.wR[j][0] * zv[b][0] + cur.wR[j][1] * zv[b][1]);
+            const float dot = mega_wave_sum(mega_dot_z(cur.wR[j], zv[b]));
             xown[j][b] = (dot + cur.bR[j]) + xown[j][b];
             if (lane == 0) g_put(qn + (size_t)b * R + r, xown[j][b], tag);
           }
@@ -836,8 +908,8 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
           if (b >= n || g >= half) continue;
-          float h0 = mega_wave_sum(cur.wM[0][0] * zv[b][0] + cur.wM[0][1] * zv[b][1]);
-          float h1 = mega_wave_sum(cur.wM[1][0] * zv[b][0] + cur.wM[1][1] * zv[b][1]);
+          float h0 = mega_wave_sum(mega_dot_z(cur.wM[0], zv[b]));
+          float h1 = mega_wave_sum(mega_dot_z(cur.wM[1], zv[b]));
           h0 = ((h0 + u[0][b]) + cur.cb[0]) + pre_s[l + 1][0][0][b];
           h1 = ((h1 + u[1][b]) + cur.cb[1]) + pre_s[l + 1][0][1][b];
           if (lane == 0) g_put(zb + (size_t)b * half + g, mega_gate(h0, h1), tag);
@@ -848,11 +920,11 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
       // skip rows (modules.py:55, 105-109): nobody waits for them before the head
 #pragma unroll
       for (int j = 0; j < MEGA_RJ; ++j) {
-        const int r = g + MEGA_G * j;
+        const int r = g + G * j;
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
           if (b >= n || r >= S) continue;
-          const float sk = mega_wave_sum(cur.wS[j][0] * zv[b][0] + cur.wS[j][1] * zv[b][1]) + cur.bS[j];
+          const float sk = mega_wave_sum(mega_dot_z(cur.wS[j], zv[b])) + cur.bS[j];
           sacc[j][b] = l == 0 ? sk : sacc[j][b] + sk;
         }
       }
@@ -862,38 +934,38 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
     // ---- head: relu, proj1, relu, proj2 (modules.py:249-255) ----
 #pragma unroll
     for (int j = 0; j < MEGA_RJ; ++j) {
-      const int r = g + MEGA_G * j;
+      const int r = g + G * j;
 #pragma unroll
       for (int b = 0; b < NB; ++b)
         if (r < S && b < n && lane == 0) g_put(a.sbox + (size_t)b * S + r, fmaxf(sacc[j][b], 0.f), tag);
     }
-    float sv[NB][MEGA_VI];
-    if (!mega_gather_n<NB>(a.sbox, S, n, S, tag, sv, a.status)) return;
+    float sv[NB][VI];
+    if (!mega_gather_n(a.sbox, S, n, S, tag, sv, a.status)) return;
     MP_T(6);
 #pragma unroll
     for (int j = 0; j < MEGA_RJ; ++j) {
-      const int r = g + MEGA_G * j;
+      const int r = g + G * j;
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
         if (b >= n || r >= S) continue;
         float acc = 0.f;
 #pragma unroll
-        for (int i = 0; i < MEGA_VI; ++i) acc += w1[j][i] * sv[b][i];
+        for (int i = 0; i < VI; ++i) acc += w1[j][i] * sv[b][i];
         acc = mega_wave_sum(acc) + b1[j];
         if (lane == 0) g_put(a.s1box + (size_t)b * S + r, fmaxf(acc, 0.f), tag);
       }
     }
-    if (!mega_gather_n<NB>(a.s1box, S, n, S, tag, sv, a.status)) return;
+    if (!mega_gather_n(a.s1box, S, n, S, tag, sv, a.status)) return;
     MP_T(7);
 #pragma unroll
     for (int j = 0; j < MEGA_RJ; ++j) {
-      const int r = g + MEGA_G * j;
+      const int r = g + G * j;
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
         if (b >= n || r >= O) continue;
         float acc = 0.f;
 #pragma unroll
-        for (int i = 0; i < MEGA_VI; ++i) acc += w2[j][i] * sv[b][i];
+        for (int i = 0; i < VI; ++i) acc += w2[j][i] * sv[b][i];
         acc = mega_wave_sum(acc) + b2[j];
         if (lane == 0) g_put(a.lgbox + (size_t)b * O + r, acc, tag);
       }
@@ -902,28 +974,28 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
     // ---- sampler on workgroup 0 (generate.py:109-141) ----
     if (g == 0) {
       for (int b = 0; b < n; ++b) {
-        float lv[MEGA_VI];
+        float lv[VI];
         if (!mega_gather(a.lgbox + (size_t)b * O, O, tag, lv, a.status)) return;
         if (a.logits_out)
 #pragma unroll
-          for (int i = 0; i < MEGA_VI; ++i)
+          for (int i = 0; i < VI; ++i)
             if (lane + 64 * i < O) a.logits_out[((size_t)t * n + b) * O + lane + 64 * i] = lv[i];
         float fb = 0.f;
         if (a.mode == VQVAE_GEN_SOFTMAX) {
           float m = -INFINITY;
 #pragma unroll
-          for (int i = 0; i < MEGA_VI; ++i) if (lane + 64 * i < O) m = fmaxf(m, lv[i]);
+          for (int i = 0; i < VI; ++i) if (lane + 64 * i < O) m = fmaxf(m, lv[i]);
 #pragma unroll
           for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-          float e[MEGA_VI], s = 0.f;
+          float e[VI], s = 0.f;
 #pragma unroll
-          for (int i = 0; i < MEGA_VI; ++i) { e[i] = lane + 64 * i < O ? expf(lv[i] - m) : 0.f; s += e[i]; }
+          for (int i = 0; i < VI; ++i) { e[i] = lane + 64 * i < O ? expf(lv[i] - m) : 0.f; s += e[i]; }
           s = gen_wave_sum(s);
           // float64 cdf in index order k = lane + 64 i: full rows below + an in-row scan
           const double u = a.uniforms[((size_t)t * n + b) * a.n_uniform];
-          double base = 0.0, cdf[MEGA_VI];
+          double base = 0.0, cdf[VI];
 #pragma unroll
-          for (int i = 0; i < MEGA_VI; ++i) {
+          for (int i = 0; i < VI; ++i) {
             const double pk = (double)(e[i] / s);
             const double sc = wave_incl_scan(pk);
             cdf[i] = base + sc;
@@ -932,7 +1004,7 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
           const double total = base;
           int cnt = 0;
 #pragma unroll
-          for (int i = 0; i < MEGA_VI; ++i) if (lane + 64 * i < O && cdf[i] / total <= u) ++cnt;
+          for (int i = 0; i < VI; ++i) if (lane + 64 * i < O && cdf[i] / total <= u) ++cnt;
 #pragma unroll
           for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
           const int idx = cnt < O ? cnt : O - 1;
@@ -941,7 +1013,7 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
           fb = __int_as_float(nxt_in);
         } else {
 #pragma unroll
-          for (int i = 0; i < MEGA_VI; ++i) lg_s[b][lane + 64 * i] = lv[i];
+          for (int i = 0; i < VI; ++i) lg_s[b][lane + 64 * i] = lv[i];
           __builtin_amdgcn_wave_barrier();
           float v = 0.f;
           if (lane == 0) {
@@ -972,7 +1044,7 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
     MP_T(9);
     // ---- feedback: every workgroup learns the next input (generate.py:127, 139-141) ----
     {
-      float fv[MEGA_VI];
+      float fv[VI];
       if (!mega_gather(a.idxbox, n, tag, fv, a.status)) return;
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
@@ -995,9 +1067,18 @@ __global__ __launch_bounds__(MEGA_THREADS) void gen_mega_kernel(MegaArgs a) {
 
 }  // namespace vq
 
-static size_t mega_layout(const vqvae_gen_desc* d, size_t* off_tab, size_t* off_xq, size_t* off_z, size_t* off_s,
+// ---- host side: class selection, workspace layout, launch ---------------------------------------
+enum { MEGA_CLASS_NONE = 0, MEGA_CLASS_NARROW = 1, MEGA_CLASS_WIDE = 2 };
+struct MegaClassInfo { int G, crec, hrec; };
+static MegaClassInfo mega_class_info(int cls) {
+  if (cls == MEGA_CLASS_WIDE) return MegaClassInfo{MegaWide::G, mega_crec<MegaWide>(), mega_hrec<MegaWide>()};
+  return MegaClassInfo{MegaNarrow::G, mega_crec<MegaNarrow>(), mega_hrec<MegaNarrow>()};
+}
+
+static size_t mega_layout(const vqvae_gen_desc* d, int cls, size_t* off_tab, size_t* off_xq, size_t* off_z, size_t* off_s,
                           size_t* off_s1, size_t* off_lg, size_t* off_idx, size_t* off_qt, size_t* off_crec,
                           size_t* off_hrec, size_t* off_brec, long* qoffs) {
+  const MegaClassInfo ci = mega_class_info(cls);
   size_t o = 256;                                             // status word
   *off_tab = o; o += vq::align_up(sizeof(vq::MegaBlock) * d->n_blocks, 256);
   size_t q = 0;
@@ -1012,21 +1093,59 @@ static size_t mega_layout(const vqvae_gen_desc* d, size_t* off_tab, size_t* off_
   *off_lg = o; o += vq::align_up((size_t)d->n * d->out_dim * 8, 256);
   *off_idx = o; o += 256;
   *off_qt = o; o += vq::align_up(sizeof(vq::MegaQ) * d->n_blocks, 256);
-  const size_t recs = (size_t)d->n_blocks * vq::MEGA_G;
-  *off_crec = o; o += recs * 64 * 16 * vq::MEGA_CREC;
-  *off_hrec = o; o += recs * 64 * 64;
+  const size_t recs = (size_t)d->n_blocks * ci.G;
+  *off_crec = o; o += recs * 64 * 16 * ci.crec;
+  *off_hrec = o; o += recs * 64 * 16 * ci.hrec;
   *off_brec = o; o += vq::align_up(recs * 32, 256);
   return o;
 }
 
-static int mega_check(const vqvae_gen_desc* d) {
+// The smallest class whose per-lane register vectors hold the descriptor's channel counts.
+static int mega_class_of(const vqvae_gen_desc* d) {
+  const int vec = std::max(std::max(d->residual, d->skip), d->out_dim), half = d->dilated / 2;
+  if (vec <= 64 * MegaNarrow::VI && d->cond_dim <= 64 * MegaNarrow::CVI && half <= MegaNarrow::G) return MEGA_CLASS_NARROW;
+  if (vec <= 64 * MegaWide::VI && d->cond_dim <= 64 * MegaWide::CVI && half <= MegaWide::G) return MEGA_CLASS_WIDE;
+  return MEGA_CLASS_NONE;
+}
+
+template <class C, int NB, bool EXACT>
+static int mega_resident_launches_of() {
+  int dev = 0, cus = 0, per_cu = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gen_mega_kernel<C, NB, EXACT>, MEGA_THREADS, 0) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return (int)((long)cus * per_cu / C::G);
+}
+// How many launches of (class, n) fit on the current device at the same time, every workgroup resident:
+// the waves of a launch wait for each other, so a launch that is only partly resident cannot finish.
+static int mega_resident_launches(int cls, int n) {
+  static int cache[3][GEN_NB + 1];                // 0 = not asked yet, -1 = none
+  int& c = cache[cls][n];
+  if (c == 0) {
+    int r;
+    if (cls == MEGA_CLASS_WIDE)
+      r = n == 1 ? mega_resident_launches_of<MegaWide, 1, true>() : n == 2 ? mega_resident_launches_of<MegaWide, 2, true>()
+        : n == 4 ? mega_resident_launches_of<MegaWide, 4, true>() : mega_resident_launches_of<MegaWide, 4, false>();
+    else
+      r = n == 1 ? mega_resident_launches_of<MegaNarrow, 1, true>() : n == 2 ? mega_resident_launches_of<MegaNarrow, 2, true>()
+        : n == 4 ? mega_resident_launches_of<MegaNarrow, 4, true>() : mega_resident_launches_of<MegaNarrow, 4, false>();
+    c = r > 0 ? r : -1;
+  }
+  return c > 0 ? c : 0;
+}
+
+static int mega_check(const vqvae_gen_desc* d, int* cls_out) {
   VQ_REQUIRE(d, "gen_run: null descriptor");
-  VQ_REQUIRE(d->n >= 1 && d->n <= GEN_NB, "gen_run: n must be 1..%d sequences (got %d)", GEN_NB, d->n);
   VQ_REQUIRE(d->n_blocks >= 1 && d->n_blocks <= MEGA_MAXL && d->blocks, "gen_run: 1..%d residual blocks", MEGA_MAXL);
-  const int lim = 64 * MEGA_VI;
-  VQ_REQUIRE(d->residual >= 1 && d->residual <= lim && d->skip >= 1 && d->skip <= lim && d->out_dim >= 1 && d->out_dim <= lim &&
-             d->cond_dim >= 1 && d->cond_dim <= lim && d->dilated >= 2 && d->dilated % 2 == 0 && d->dilated / 2 <= 128 && d->input_dim >= 1,
-             "gen_run: the persistent kernel holds at most %d channels per vector (dilated <= 256)", lim);
+  VQ_REQUIRE(d->residual >= 1 && d->skip >= 1 && d->out_dim >= 1 && d->cond_dim >= 1 && d->dilated >= 2 && d->dilated % 2 == 0 &&
+             d->input_dim >= 1, "gen_run: bad dimensions");
+  const int cls = mega_class_of(d);
+  VQ_REQUIRE(cls != MEGA_CLASS_NONE, "gen_run: the persistent kernel holds at most %d channels per vector (dilated <= %d, condition <= %d)",
+             64 * MegaWide::VI, 2 * MegaWide::G, 64 * MegaWide::CVI);
+  const MegaClassInfo ci = mega_class_info(cls);
+  VQ_REQUIRE(d->n >= 1 && d->n <= GEN_NB, "gen_run: n must be 1..%d sequences (got %d)", GEN_NB, d->n);
   VQ_REQUIRE(d->sample_mode == VQVAE_GEN_SOFTMAX || d->sample_mode == VQVAE_GEN_MOL, "gen_run: sample_mode must be SOFTMAX or MOL");
   VQ_REQUIRE(d->uniforms && d->n_uniform >= 1 && d->cond && d->cond_follows_step, "gen_run: uniforms / per-step condition missing");
   if (d->sample_mode == VQVAE_GEN_MOL) VQ_REQUIRE(d->out_dim % 3 == 0 && d->n_uniform >= d->out_dim / 3, "gen_run: mixture sampling needs out_dim = 3*nr_mix and nr_mix uniforms");
@@ -1036,22 +1155,40 @@ static int mega_check(const vqvae_gen_desc* d) {
     VQ_REQUIRE(bk.conv_W && bk.conv_b && bk.cond_W && bk.cond_b && bk.res_W && bk.res_b && bk.skip_W && bk.skip_b && bk.dilation >= 1,
                "gen_run: block %d incomplete", l);
   }
+  VQ_REQUIRE(mega_resident_launches(cls, d->n) >= 1, "gen_run: the %d workgroups of a launch cannot all be resident on this device", ci.G);
+  *cls_out = cls;
   return 0;
 }
 
 extern "C" size_t vqvae_wavenet_gen_run_workspace_bytes(const vqvae_gen_desc* d) {
-  if (mega_check(d) != 0) return 0;
+  int cls;
+  if (mega_check(d, &cls) != 0) return 0;
   size_t o[11];
-  return mega_layout(d, o, o + 1, o + 2, o + 3, o + 4, o + 5, o + 6, o + 7, o + 8, o + 9, o + 10, nullptr);
+  return mega_layout(d, cls, o, o + 1, o + 2, o + 3, o + 4, o + 5, o + 6, o + 7, o + 8, o + 9, o + 10, nullptr);
+}
+
+extern "C" int vqvae_wavenet_gen_run_concurrency(const vqvae_gen_desc* d) {
+  int cls;
+  if (mega_check(d, &cls) != 0) return 0;
+  return mega_resident_launches(cls, d->n);
+}
+
+template <class C>
+static void mega_launch(const vqvae_gen_desc* d, const MegaArgs& a, hipStream_t st) {
+  if (d->n == 1) hipLaunchKernelGGL((gen_mega_kernel<C, 1, true>), dim3(C::G), dim3(MEGA_THREADS), 0, st, a);
+  else if (d->n == 2) hipLaunchKernelGGL((gen_mega_kernel<C, 2, true>), dim3(C::G), dim3(MEGA_THREADS), 0, st, a);
+  else if (d->n == 4) hipLaunchKernelGGL((gen_mega_kernel<C, 4, true>), dim3(C::G), dim3(MEGA_THREADS), 0, st, a);
+  else hipLaunchKernelGGL((gen_mega_kernel<C, 4, false>), dim3(C::G), dim3(MEGA_THREADS), 0, st, a);
 }
 
 extern "C" int vqvae_wavenet_gen_run(const vqvae_gen_desc* d, int t0, int steps, void* ws, size_t ws_bytes, vqvae_stream_t s) {
-  int rc = mega_check(d);
+  int cls;
+  int rc = mega_check(d, &cls);
   if (rc) return rc;
   VQ_REQUIRE(t0 >= 0 && steps >= 0 && ws, "gen_run: bad step range / workspace");
   size_t off_tab, off_xq, off_z, off_s, off_s1, off_lg, off_idx, off_qt, off_crec, off_hrec, off_brec;
   long qoffs[MEGA_MAXL];
-  const size_t need = mega_layout(d, &off_tab, &off_xq, &off_z, &off_s, &off_s1, &off_lg, &off_idx, &off_qt, &off_crec,
+  const size_t need = mega_layout(d, cls, &off_tab, &off_xq, &off_z, &off_s, &off_s1, &off_lg, &off_idx, &off_qt, &off_crec,
                                   &off_hrec, &off_brec, qoffs);
   if (ws_bytes < need) { set_error("gen_run: workspace %zu < %zu bytes", ws_bytes, need); return VQVAE_E_WORKSPACE; }
   hipStream_t st = (hipStream_t)s;
@@ -1068,7 +1205,9 @@ extern "C" int vqvae_wavenet_gen_run(const vqvae_gen_desc* d, int t0, int steps,
     VQ_CHECK_HIP(hipMemcpyAsync(base + off_tab, tab, sizeof(MegaBlock) * d->n_blocks, hipMemcpyHostToDevice, st));
     VQ_CHECK_HIP(hipMemcpyAsync(base + off_qt, qt, sizeof(MegaQ) * d->n_blocks, hipMemcpyHostToDevice, st));
     VQ_CHECK_HIP(hipStreamSynchronize(st));      // `tab`, `qt` are stack buffers
-    hipLaunchKernelGGL(gen_mega_pack_kernel, dim3(d->n_blocks * MEGA_G), dim3(64), 0, st, (const MegaBlock*)(base + off_tab),
+    const MegaClassInfo ci = mega_class_info(cls);
+    auto pack = cls == MEGA_CLASS_WIDE ? gen_mega_pack_kernel<MegaWide> : gen_mega_pack_kernel<MegaNarrow>;
+    hipLaunchKernelGGL(pack, dim3(d->n_blocks * ci.G), dim3(64), 0, st, (const MegaBlock*)(base + off_tab),
                        d->n_blocks, d->residual, d->dilated / 2, d->skip, d->cond_dim, (float4*)(base + off_crec),
                        (float4*)(base + off_hrec), (float4*)(base + off_brec));
     VQ_LAUNCH_CHECK();
@@ -1086,10 +1225,8 @@ extern "C" int vqvae_wavenet_gen_run(const vqvae_gen_desc* d, int t0, int steps,
   a.status = (int*)base;
   a.L = d->n_blocks; a.n = d->n; a.input_dim = d->input_dim; a.R = d->residual; a.D = d->dilated; a.S = d->skip; a.Cc = d->cond_dim;
   a.O = d->out_dim; a.mode = d->sample_mode; a.n_uniform = d->n_uniform; a.t0 = t0; a.steps = steps; a.log_scale_min = d->log_scale_min;
-  if (d->n == 1) hipLaunchKernelGGL((gen_mega_kernel<1, true>), dim3(MEGA_G), dim3(MEGA_THREADS), 0, st, a);
-  else if (d->n == 2) hipLaunchKernelGGL((gen_mega_kernel<2, true>), dim3(MEGA_G), dim3(MEGA_THREADS), 0, st, a);
-  else if (d->n == 4) hipLaunchKernelGGL((gen_mega_kernel<4, true>), dim3(MEGA_G), dim3(MEGA_THREADS), 0, st, a);
-  else hipLaunchKernelGGL((gen_mega_kernel<4, false>), dim3(MEGA_G), dim3(MEGA_THREADS), 0, st, a);
+  if (cls == MEGA_CLASS_WIDE) mega_launch<MegaWide>(d, a, st);
+  else mega_launch<MegaNarrow>(d, a, st);
   VQ_LAUNCH_CHECK();
   return 0;
 }

@@ -210,6 +210,7 @@ PROTOTYPES = {
     'vqvae_wavenet_gen_step': (c_int, [C.POINTER(GenDesc), P]),
     'vqvae_wavenet_gen_run_workspace_bytes': (c_size_t, [C.POINTER(GenDesc)]),
     'vqvae_wavenet_gen_run': (c_int, [C.POINTER(GenDesc), c_int, c_int, P, c_size_t, P]),
+    'vqvae_wavenet_gen_run_concurrency': (c_int, [C.POINTER(GenDesc)]),
     'vqvae_graph_capture_begin': (c_int, [P]),
     'vqvae_graph_capture_begin_relaxed': (c_int, [P]),
     'vqvae_graph_capture_end': (c_int, [P, C.POINTER(c_void_p)]),

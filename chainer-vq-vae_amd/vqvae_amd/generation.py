@@ -136,8 +136,9 @@ class GenerationState(object):
         d.max_steps = steps
         nbytes = 0
         if steps and persistent:
-            # shapes outside the persistent kernel's limits (> 256 channels per vector) run on the
-            # per-step kernels below -- same results, more launches
+            # the library picks the width class (<= 256 or <= 512 channels per vector); shapes outside
+            # both (or a device too small to hold a launch) get 0 bytes and run on the per-step
+            # kernels below -- same results, more launches
             nbytes = _lib.load().vqvae_wavenet_gen_run_workspace_bytes(C.byref(d))
         if steps and persistent and nbytes:
             # one persistent launch per `chunk` steps; queues + mailboxes live in its workspace
@@ -179,7 +180,7 @@ def run_many(wavenet, condition, uniforms, mode, n_steps=None, group=_lib.GEN_MA
              chunk=4096):
     """Batched serving form of the loop: N sequences = ceil(N / group) independent persistent
     launches of <= ``group`` lockstep sequences each, spread over ``max_streams`` HIP streams so
-    they run concurrently (a launch occupies 128 two-wave workgroups: a fraction of the GPU).
+    they run concurrently (a launch occupies 128 or 256 two-wave workgroups: a fraction of the GPU).
     condition (N, condition_dim, T) on the device, uniforms (T, N[, nr_mix]) on the host.
     Returns the host array (N, T) of sampled bins / values."""
     if condition.ndim == 4:
@@ -213,10 +214,10 @@ def run_many(wavenet, condition, uniforms, mode, n_steps=None, group=_lib.GEN_MA
         ws = DeviceArray((nbytes // 4 + 1,), np.int32)
         jobs.append((st, d, out, ws, u_dev, cview))
     backend.synchronize()                  # buffers above were prepared on the main stream
-    # every workgroup of a launch must be resident at once (its waves wait for each other): a launch
-    # holds 128 two-wave workgroups and a CU takes ~12 such waves (VGPR-limited) -- stay well inside
-    resident = backend.device_info()['n_cu'] * 12 // (128 * 2)
-    max_streams = max(1, min(max_streams, resident * 2 // 3))
+    # every workgroup of a launch must be resident at once (its waves wait for each other): the
+    # library knows the width class's workgroup count and the kernel's occupancy on this device
+    resident = min(lib.vqvae_wavenet_gen_run_concurrency(C.byref(j[1])) for j in jobs)
+    max_streams = max(1, min(max_streams, resident))
     for t0 in range(0, steps, chunk):
         for i, (st, d, out, ws, _, _) in enumerate(jobs):
             _lib.call('vqvae_wavenet_gen_run', C.byref(d), t0, min(chunk, steps - t0), ws.ptr, ws.nbytes,

@@ -867,7 +867,7 @@ class WaveNet(Chain):
         float32 samples, last column 0 as in generate.py:103-105 (plus the per-step logits
         (steps, n, out_dim) when ``return_logits``).  ``forced`` (T, n) feeds these values back
         instead of the samples (teacher forcing).  ``persistent`` runs the loop as one persistent
-        kernel (csrc/generate.hip, channel counts <= 256); otherwise as a replayed hipGraph of
+        kernel (csrc/generate.hip, channel counts <= 512, condition <= 640); otherwise as a replayed hipGraph of
         per-step kernels (``graph_steps`` steps per graph, 0 = eager launches)."""
         from .core import Variable
         cd = condition.data if isinstance(condition, Variable) else condition

@@ -714,12 +714,21 @@ int vqvae_wavenet_gen_step(const vqvae_gen_desc* d, vqvae_stream_t s);
  * queues at t0 == 0 (the call zero-fills `ws`: that is WaveNet.initialize) or continuing a
  * previous call on the same `ws`, `out` and `forced_next`.  Uses the weights, cond, uniforms,
  * forced_next, out, logits_out, sample_mode (SOFTMAX or MOL) fields of `d`; the device state
- * fields are not used (queues and hand-off mailboxes live in `ws`).  Channel counts <= 256.
+ * fields are not used (queues and hand-off mailboxes live in `ws`).  Two width classes, chosen
+ * from the descriptor: residual, skip, out_dim, cond_dim <= 256 and dilated <= 256 (128 workgroups),
+ * or residual, skip, out_dim <= 512, dilated <= 512 and cond_dim <= 640 (256 workgroups: the
+ * reference's default decoder, params.py).  vqvae_wavenet_gen_run_workspace_bytes returns 0 for any
+ * other shape, and when the workgroups of one launch cannot all be resident on the current device:
+ * the caller then drives vqvae_wavenet_gen_step.
  * After the stream has drained, the first int32 of `ws` is 0 on success, non-zero when a bounded
  * device-side wait timed out (the launch then ended early).                                    */
 size_t vqvae_wavenet_gen_run_workspace_bytes(const vqvae_gen_desc* d);
 int vqvae_wavenet_gen_run(const vqvae_gen_desc* d, int t0, int steps, void* ws, size_t ws_bytes,
                           vqvae_stream_t s);
+/* How many vqvae_wavenet_gen_run launches of this descriptor fit on the current device at the same
+ * time with every workgroup resident (0 where workspace_bytes returns 0).  The waves of a launch
+ * wait for each other, so concurrent launches on separate streams must stay inside this number. */
+int vqvae_wavenet_gen_run_concurrency(const vqvae_gen_desc* d);
 
 /* ---- hipGraph capture/replay of a launch sequence on one stream (launch-bound inner loops:
  *      the per-sample chain of generate.py:105-145)                                          */

@@ -1,5 +1,5 @@
 """Throughput of the device-resident generation loop (generate.py:105-145) at BASELINE decoder sizes.
-usage: python tools/gen_bench.py [--workload c2|c5] [--n 1] [--steps 16000] [--graph-steps 8]"""
+usage: python tools/gen_bench.py [--workload c2|c5|ref] [--n 1] [--steps 16000] [--graph-steps 8]"""
 import argparse
 import os
 import sys
@@ -13,7 +13,9 @@ sys.path.insert(0, os.path.join(ROOT, 'chainer-vq-vae_amd'))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--workload', default='c2')
+    ap.add_argument('--workload', default='c2', help='c2 / c5: BASELINE decoders (256 channels); ref: the reference\'s default '
+                    'decoder (params.py: 3 x 10 blocks, 512 / 512 / 256, condition 640, softmax 256)')
+    ap.add_argument('--dump', default='', help='write the sampled outputs to this .npy file (same seed = same file)')
     ap.add_argument('--n', type=int, default=1)
     ap.add_argument('--steps', type=int, default=16000)
     ap.add_argument('--graph-steps', type=int, default=8)
@@ -26,29 +28,36 @@ def main():
     from vqvae_amd.wavenet import WaveNet
     backend.init(0)
     mol = a.workload == 'c5'
-    n_loop = 4 if mol else 2
-    dec = WaveNet(n_loop, 10, 2, 1 if mol else 256, 256, 256, 256, 256, mol, 30, -40, 192, 0)
+    ref = a.workload == 'ref'
+    n_loop = 4 if mol else 3 if ref else 2
+    Cc = 640 if ref else 192
+    if ref:
+        dec = WaveNet(n_loop, 10, 2, 256, 512, 512, 256, 256, False, 30, -40, Cc, 0)
+    else:
+        dec = WaveNet(n_loop, 10, 2, 1 if mol else 256, 256, 256, 256, 256, mol, 30, -40, Cc, 0)
     from vqvae_amd import functions as F
     from vqvae_amd.core import Variable
     # materialise the lazily initialised parameters with one tiny forward
     x = backend.zeros((1, 1 if mol else 256, 2048, 1))
-    c = backend.zeros((1, 192, 2048, 1))
+    c = backend.zeros((1, Cc, 2048, 1))
     dec.to_gpu()
     dec(Variable(x), Variable(c))
     T = a.steps + 1
     if a.batch:
         rs = np.random.RandomState(0)
-        cond = backend.to_device(rs.standard_normal((a.batch, 192, T)).astype(np.float32))
+        cond = backend.to_device(rs.standard_normal((a.batch, Cc, T)).astype(np.float32))
         u = rs.uniform(0.01, 0.99, (T, a.batch, 10 if mol else 1))
         dec.generate_batch(cond, u, n_steps=64, group=a.group, max_streams=a.streams)
         t0 = time.time()
         o = dec.generate_batch(cond, u, group=a.group, max_streams=a.streams)
         dt = time.time() - t0
+        if a.dump:
+            np.save(a.dump, o)
         print('group %d streams %d: ' % (a.group, a.streams) + 'batch of %d sequences x %d steps in %.3f s = %.0f samples/s aggregate (%.1f sequences in real time at 16 kHz)'
               % (a.batch, a.steps, dt, a.batch * a.steps / dt, a.batch * a.steps / dt / 16000))
         return
     rs = np.random.RandomState(0)
-    cond = backend.to_device(rs.standard_normal((a.n, 192, T)).astype(np.float32))
+    cond = backend.to_device(rs.standard_normal((a.n, Cc, T)).astype(np.float32))
     u = rs.uniform(0.01, 0.99, (T, a.n, 10 if mol else 1))
     pers = not a.per_step_kernels
     dec.generate_sequence(cond, u, n_steps=64, graph_steps=a.graph_steps, persistent=pers)      # warm-up
@@ -56,6 +65,8 @@ def main():
     out = dec.generate_sequence(cond, u, graph_steps=a.graph_steps, persistent=pers)
     dt = time.time() - t0
     o = out.get()
+    if a.dump:
+        np.save(a.dump, o)
     print('%s workload %s n=%d: %d steps in %.3f s = %.1f us/step, %.0f samples/s per sequence (%.2fx real time at 16 kHz), '
           'distinct outputs %d' % ('persistent' if pers else 'per-step kernels', a.workload, a.n, a.steps, dt, 1e6 * dt / a.steps, a.steps / dt,
                                    a.steps / dt / 16000, len(np.unique(o))))

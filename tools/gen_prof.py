@@ -1,4 +1,5 @@
-"""Stage timing of the persistent generation kernel (library built with `make EXTRA=-DMEGA_PROF`)."""
+"""Stage timing of the persistent generation kernel (library built with `make EXTRA=-DMEGA_PROF`).
+usage: python tools/gen_prof.py [n] [c2|ref]"""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -8,12 +9,15 @@ from vqvae_amd.wavenet import WaveNet
 from vqvae_amd.core import Variable
 backend.init(0)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1
-dec = WaveNet(2, 10, 2, 256, 256, 256, 256, 256, False, 30, -40, 192, 0)
+ref = len(sys.argv) > 2 and sys.argv[2] == 'ref'        # the reference's default decoder: the wide class
+Cc = 640 if ref else 192
+dec = WaveNet(3, 10, 2, 256, 512, 512, 256, 256, False, 30, -40, Cc, 0) if ref else \
+    WaveNet(2, 10, 2, 256, 256, 256, 256, 256, False, 30, -40, 192, 0)
 dec.to_gpu()
-dec(Variable(backend.zeros((1, 256, 2048, 1))), Variable(backend.zeros((1, 192, 2048, 1))))
+dec(Variable(backend.zeros((1, 256, 2048, 1))), Variable(backend.zeros((1, Cc, 2048, 1))))
 steps = 4000
 rs = np.random.RandomState(0)
-cond = backend.to_device(rs.standard_normal((n, 192, steps + 1)).astype(np.float32))
+cond = backend.to_device(rs.standard_normal((n, Cc, steps + 1)).astype(np.float32))
 u = rs.uniform(0.01, 0.99, (steps + 1, n))
 dec.generate_sequence(cond, u, persistent=True)
 ws = dec._gen._last_ws
