@@ -242,8 +242,9 @@ CONTRACT_LOG2_LIMIT = 8
 
 
 def contract_report():
-    """The three device words (violations, float bits of the worst bound / max, tensors checked); allocated OUTSIDE any
-    recording's arena, once, so that eager and replayed steps count into the same words."""
+    """The three device words (violations, float bits of the worst bound / max, tensors checked) of
+    vqvae_f32x2_contract_check, in a 16-byte buffer whose fourth word is padding the library never touches; allocated
+    OUTSIDE any recording's arena, once, so that eager and replayed steps count into the same words."""
     r = _state.get('contract')
     if r is None:
         arena, _state['arena'] = _state.get('arena'), None

@@ -367,8 +367,8 @@ int vqvae_pullback_reduce_into(const float* part, const int32_t* v0, int nblocks
  * to its ACTUAL maximum.  A bound 2^m above the maximum costs m bits of the mode's absolute floor; the check counts, on
  * the device and without a host round trip, every tensor with bound / max > 2^log2_limit (or a bound below the maximum):
  *   report[0] += violations, report[1] = max(report[1], float bits of the largest bound / max seen), report[2] += tensors
- * checked (report: 3 device words the caller zeroes when it starts counting).  NULL pairs, groups nobody wrote and
- * all-zero tensors are skipped.  There is no counterpart in the reference (Chainer computes in fp32, modules.py:40-55). */
+ * checked (report: exactly THREE device words, zeroed by the caller when it starts counting; no other word is read or
+ * written).  Pairs are checked 64 per launch.  NULL pairs, groups nobody wrote and all-zero tensors are skipped.  There is no counterpart in the reference (Chainer computes in fp32, modules.py:40-55). */
 int vqvae_f32x2_contract_check(int n, const uint32_t* const* scale, const uint32_t* const* amax, int log2_limit,
                                uint32_t* report, vqvae_stream_t s);
 
@@ -496,6 +496,11 @@ int vqvae_upsample_linear_fwd(const float* x, int B, int C, int Tin, int Tout,
                               const int32_t* v0, const int32_t* v1, const float* w0,
                               const float* w1,
                               float* y, long y_bstride, vqvae_stream_t s);
+/* vqvae_upsample_linear_bwd accepts any Tin >= 1, Tout and 4-byte aligned pointers: it picks its kernel from the ratio,
+ * Tout % 4, gy_bstride % 4 and the 16-byte alignment of gy / w0 / w1 (same result to a few ulp on every road).  The
+ * _bf16 / _f16x2 / _blocks forms serve the decoder's pull-back only and return VQVAE_E_INVALID otherwise: Tin >= 3,
+ * Tout >= 8 Tin, Tout % 4 == 0, Tout <= 8192, strides % 4 == 0, w0 / w1 / gy 16-byte aligned (bf16 gy: 8).  gx rows are
+ * C * Tin floats inside gx_bstride; nothing between the rows is written.                                           */
 int vqvae_upsample_linear_bwd(const float* gy, long gy_bstride, int B, int C, int Tin,
                               int Tout, const float* w0, const float* w1,
                               const int32_t* lo0, const int32_t* hi0,
@@ -595,7 +600,8 @@ int vqvae_embed_gather_fwd(const int32_t* idx, long idx_bstride, int B, int T, c
                            const float* b, int Cout, int q, int K, float* y, vqvae_stream_t s);
 /*      embed_gather_bound: amax_out (VQVAE_AMAX_SLOTS words) = an upper bound of max |y| of embed_gather_fwd from the
  *                  weights alone, max_co (|b[co]| + sum_tap max_q |W[co, q, tap]|): the scale of the first gate GEMM's
- *                  operand in matmul mode 3 without a scan of y.                                               */
+ *                  operand in matmul mode 3 without a scan of y.  The call SETS the words (zeroes, then raises them):
+ *                  the caller need not zero them.  The bound is at most 1.001 x that expression.                  */
 int vqvae_embed_gather_bound(const float* W, const float* b, int Cout, int q, int K, uint32_t* amax_out,
                              vqvae_stream_t s);
 /*      embed_onehot_fwd / _wgrad: the SAME conv applied to the reference's one-hot float input
