@@ -261,13 +261,15 @@ __global__ __launch_bounds__(256) void gen_finish_kernel(GenFinishArgs a) {
   if (tid == 0) *a.step = t + 1;
 }
 
+int gen_step_lockstep(const vqvae_gen_desc* d, hipStream_t st);   // generate_lockstep.hip: the batch in MFMA columns
+
 }  // namespace vq
 
 using namespace vq;
 
 extern "C" int vqvae_wavenet_gen_step(const vqvae_gen_desc* d, vqvae_stream_t s) {
   VQ_REQUIRE(d, "gen_step: null descriptor");
-  VQ_REQUIRE(d->n >= 1 && d->n <= GEN_NB, "gen_step: n must be 1..%d sequences (got %d)", GEN_NB, d->n);
+  VQ_REQUIRE(d->n >= 1 && d->n <= VQVAE_GEN_MAX_LOCKSTEP, "gen_step: n must be 1..%d sequences (got %d)", VQVAE_GEN_MAX_LOCKSTEP, d->n);
   VQ_REQUIRE(d->n_blocks >= 1 && d->blocks, "gen_step: no residual blocks");
   VQ_REQUIRE(d->input_dim >= 1 && d->residual >= 1 && d->dilated >= 2 && d->dilated % 2 == 0 && d->skip >= 1 &&
              d->out_dim >= 1 && d->cond_dim >= 0, "gen_step: bad dimensions");
@@ -281,6 +283,7 @@ extern "C" int vqvae_wavenet_gen_step(const vqvae_gen_desc* d, vqvae_stream_t s)
     else VQ_REQUIRE(d->out_dim % 3 == 0 && d->n_uniform >= d->out_dim / 3, "gen_step: mixture sampling needs out_dim = 3*nr_mix and nr_mix uniforms");
   }
   hipStream_t st = (hipStream_t)s;
+  if (d->n > GEN_NB) return gen_step_lockstep(d, st);   // n <= 4: the kernels above, as before
   const int n = d->n, R = d->residual, half = d->dilated / 2;
 
   GenConvArgs e{};   // embed: pad-free 2-tap conv on [previous input, current input] (modules.py:234, 247-248)

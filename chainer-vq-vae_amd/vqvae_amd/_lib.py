@@ -232,7 +232,8 @@ PROF_RESBLOCK_GATE, PROF_RESBLOCK_OUT, PROF_RESBLOCK_BWD_GZ, PROF_RESBLOCK_BWD_G
     PROF_RESBLOCK_BWD_GC, PROF_RESBLOCK_WGRAD, PROF_CONV_FWD, PROF_CONV_BWD_DATA, \
     PROF_CONV_WGRAD, PROF_VQ_NEAREST, PROF_RESSTACK_SKIP, PROF_WGRAD_DIL, PROF_WGRAD_RES_SKIP = range(1, 14)
 GEN_NONE, GEN_SOFTMAX, GEN_MOL = range(3)
-GEN_MAX_N = 4
+GEN_MAX_N = 4               # VQVAE_GEN_MAX_N: the persistent kernel and WaveNet.initialize
+GEN_MAX_LOCKSTEP = 128      # VQVAE_GEN_MAX_LOCKSTEP: vqvae_wavenet_gen_step
 
 
 class HipError(RuntimeError):

@@ -22,11 +22,12 @@ _INT_MAX = 2 ** 31 - 1
 class GenerationState(object):
     """Device state behind WaveNet.initialize(n): zero queues (modules.py:58-67, 232-244) as
     per-block rings of ``dilation`` slots, the 2-sample embed queue, the step counter."""
+    max_n = _lib.GEN_MAX_N
 
     def __init__(self, wavenet, n):
-        if not 1 <= n <= _lib.GEN_MAX_N:
+        if not 1 <= n <= self.max_n:
             raise ValueError('generation runs 1..%d sequences in lockstep (generate.py:42 runs 1), got %d'
-                             % (_lib.GEN_MAX_N, n))
+                             % (self.max_n, n))
         blocks = list(wavenet.resnet.children())
         for p in wavenet.params():
             if p.data is None:
@@ -230,3 +231,113 @@ def run_many(wavenet, condition, uniforms, mode, n_steps=None, group=_lib.GEN_MA
             raise RuntimeError('persistent generation kernel gave up waiting (status %d)' % status)
         res.append(out.get())
     return np.concatenate(res, axis=0)
+
+
+class LockstepState(GenerationState):
+    """The same descriptor and buffers for 1..128 sequences: vqvae_wavenet_gen_step runs n > 4 on the lockstep
+    kernels (csrc/generate_lockstep.hip, the batch in MFMA columns).  The persistent kernel stays at n <= 4, so
+    ``run`` is used with ``persistent=False``."""
+    max_n = _lib.GEN_MAX_LOCKSTEP
+
+
+def plan_lockstep(N, T, lengths=None, n_steps=None, group=_lib.GEN_MAX_LOCKSTEP):
+    """Who runs with whom, and for how long.  Returns (steps, groups): steps[i] = steps sequence i runs
+    (lengths[i] - 1 as generate.py:105 would for a condition of that length, capped by ``n_steps``), groups = list of
+    (indices, group_steps) in running order.  With ``lengths`` the sequences are sorted by length (longest first,
+    ties in the caller's order) before they are cut into groups of <= ``group``, so that a group stops at its
+    longest member; without, groups are consecutive slices.  A group of fewer than 5 is filled up to 5 with
+    repeats of its last member."""
+    if not _lib.GEN_MAX_N < group <= _lib.GEN_MAX_LOCKSTEP:
+        raise ValueError('generate_lockstep: group must be %d..%d, got %d' % (_lib.GEN_MAX_N + 1, _lib.GEN_MAX_LOCKSTEP, group))
+    if lengths is None:
+        full = T - 1 if n_steps is None else int(n_steps)
+        if not 0 <= full <= T:
+            raise ValueError('generate_lockstep: n_steps must be in [0, %d]' % T)
+        steps = np.full((N,), full, np.int64)
+        order = np.arange(N)
+    else:
+        lengths = np.asarray(lengths).astype(np.int64).reshape(-1)
+        if lengths.shape != (N,) or (lengths < 1).any() or (lengths > T).any():
+            raise ValueError('generate_lockstep: lengths must be (N,) = (%d,) integers in [1, %d]' % (N, T))
+        steps = lengths - 1
+        if n_steps is not None:
+            if int(n_steps) < 0:
+                raise ValueError('generate_lockstep: n_steps must not be negative')
+            steps = np.minimum(steps, int(n_steps))
+        order = np.argsort(-steps, kind='stable')
+    groups = []
+    for g0 in range(0, N, group):
+        idx = order[g0:g0 + group]
+        if len(idx) <= _lib.GEN_MAX_N:
+            # n <= 4 would run the matrix-vector kernels, which sum in another order: repeat the last member so
+            # that every sequence of every call goes through the same arithmetic
+            idx = np.concatenate([idx, np.repeat(idx[-1:], _lib.GEN_MAX_N + 1 - len(idx))])
+        groups.append((idx, int(steps[idx].max())))
+    return steps, groups
+
+
+def _device_group_runner(wavenet, condition, mode, graph_steps, return_logits):
+    """One group of run_lockstep on the device: fresh LockstepState, the group's condition rows gathered into one
+    array, a replayed hipGraph of per-step launches on the main stream."""
+    N, Cc, T = condition.shape
+
+    def run_group(idx, u, forced, steps):
+        n = len(idx)
+        if (np.diff(idx) == 1).all():
+            cview = condition.flat_view(int(idx[0]) * Cc * T, n * Cc * T, (n, Cc, T))
+        else:
+            cview = DeviceArray((n, Cc, T), np.float32)
+            backend.copy_many([(cview.flat_view(j * Cc * T, Cc * T), condition.flat_view(int(i) * Cc * T, Cc * T))
+                               for j, i in enumerate(idx)])
+        st = LockstepState(wavenet, n)
+        res = st.run(cview, u, mode, steps, forced, return_logits, graph_steps, persistent=False)
+        if return_logits:
+            return res[0].get(), res[1].get()[:steps]
+        return res.get(), None
+    return run_group
+
+
+def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None, forced=None, return_logits=False,
+                 graph_steps=8, group=_lib.GEN_MAX_LOCKSTEP, _run_group=None):
+    """Many sequences at once (converting a validation set or a corpus): N sequences of any count as groups of
+    <= ``group`` (<= 128) lockstep sequences, each group a replayed hipGraph of ``graph_steps`` per-step launches
+    (0 = eager launches), the groups one after another on the main stream.  The weights are streamed once per
+    step for the whole group.
+
+    condition (N, condition_dim, T) on the device, uniforms (T, N[, nr_mix]) host doubles, forced (T, N) or None.
+    ``lengths`` (N,) integers: sequence i runs lengths[i] - 1 steps, as generate.py:105 would for a condition of
+    that length, and its output columns from lengths[i] - 1 on are 0.
+    Returns the host array (N, T) in the caller's order (and, with ``return_logits``, the host array
+    (max steps, N, out_dim), rows past a sequence's own steps 0).  Every sequence gets the values it gets in any
+    other batch of 5..128 and in any other position of it, bit for bit."""
+    if condition.ndim == 4:
+        condition = condition.reshape(condition.shape[:3])
+    N, Cc, T = condition.shape
+    steps, groups = plan_lockstep(N, T, lengths, n_steps, group)
+    softmax = mode == _lib.GEN_SOFTMAX
+    out_dim = wavenet.proj2.W.shape[0]
+    n_uniform = 1 if softmax else out_dim // 3
+    u = np.asarray(uniforms, np.float64)
+    max_steps = int(steps.max()) if N else 0
+    if u.ndim < 2 or u.shape[1] != N:
+        raise ValueError('generate_lockstep: uniforms must be (T, N[, %d]) = (%d, %d, ...), got %s'
+                         % (n_uniform, T, N, u.shape))
+    u = u.reshape(u.shape[0], N, -1)
+    if u.shape[0] < max_steps or u.shape[2] < n_uniform:
+        raise ValueError('generate_lockstep: need (%d, %d, %d) uniform doubles, got %s' % (max_steps, N, n_uniform, u.shape))
+    if forced is not None:
+        forced = np.asarray(forced).reshape(-1, N)
+        if forced.shape[0] < max_steps:
+            raise ValueError('generate_lockstep: forced must be (steps, N) = (%d, %d), got %s' % (max_steps, N, forced.shape))
+    run_group = _run_group or _device_group_runner(wavenet, condition, mode, graph_steps, return_logits)
+    out = np.zeros((N, T), np.int32 if softmax else np.float32)                  # generate.py:103
+    logits = np.zeros((max_steps, N, out_dim), np.float32) if return_logits else None
+    for idx, gsteps in groups:
+        ug = np.ascontiguousarray(u[:max(gsteps, 1), idx, :n_uniform])
+        fg = None if forced is None else np.ascontiguousarray(forced[:gsteps, idx])
+        o, lg = run_group(idx, ug, fg, gsteps)
+        for j, i in enumerate(idx):
+            out[i, :steps[i]] = o[j, :steps[i]]           # a shorter sequence kept running: its tail is discarded
+            if return_logits:
+                logits[:steps[i], i] = lg[:steps[i], j]
+    return (out, logits) if return_logits else out

@@ -14,7 +14,7 @@ from .utils import MuLaw
 
 
 def synthesize(encoder, vq, decoder, condition_embed, x_enc, global_condition, rng=None,
-               quantize=256, use_logistic=False, n_steps=None, persistent=True):
+               quantize=256, use_logistic=False, n_steps=None, persistent=True, lockstep=False):
     """generate.py:100-148.
 
     encoder / vq / decoder / condition_embed: device-resident links (decoder = the WaveNet, EMA or
@@ -24,6 +24,8 @@ def synthesize(encoder, vq, decoder, condition_embed, x_enc, global_condition, r
     rng: numpy.random.RandomState (default: a fresh RandomState(), the stand-in for NumPy's global
         RNG that generate.py:117 / 136 draws from).  The uniforms are drawn up front, one per step
         (softmax output) or nr_mix per step (mixture of logistics), in the reference's order.
+    lockstep: any number of waveforms; the decoder advances them together through WaveNet.generate_lockstep
+        (groups of <= 128) instead of generate_sequence (n <= 4).
     Returns (wave, output): wave float64/float32 host array (n, T) as written by generate.py:146-149
         (mu-law expanded for the softmax output), output = the raw sampled bins / values."""
     rng = np.random.RandomState() if rng is None else rng
@@ -43,7 +45,10 @@ def synthesize(encoder, vq, decoder, condition_embed, x_enc, global_condition, r
         u = rng.uniform(0, 1, (max(steps, 1), n, nr_mix))            # generate.py:117
     else:
         u = rng.random_sample((max(steps, 1), n))                    # inside numpy.random.choice, generate.py:136
-    out = decoder.generate_sequence(cond, u, n_steps=steps, persistent=persistent).get()
+    if lockstep:
+        out = decoder.generate_lockstep(cond, u, n_steps=steps)
+    else:
+        out = decoder.generate_sequence(cond, u, n_steps=steps, persistent=persistent).get()
     if use_logistic:
         return out, out                                             # generate.py:147
     return MuLaw(quantize).itransform(out), out                     # generate.py:149

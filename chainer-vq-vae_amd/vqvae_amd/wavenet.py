@@ -888,3 +888,18 @@ class WaveNet(Chain):
         backend.require_device(cd)
         mode = _lib.GEN_MOL if self.use_logistic else _lib.GEN_SOFTMAX
         return run_many(self, cd, uniforms, mode, n_steps, group, max_streams)
+
+    def generate_lockstep(self, condition, uniforms, n_steps=None, lengths=None, forced=None, return_logits=False,
+                          graph_steps=8, group=128):
+        """Many sequences (a validation set, a corpus): N sequences of any count as groups of <= ``group`` (<= 128)
+        sequences that advance in lockstep on the matrix pipe, one weight stream per step for the whole group
+        (csrc/generate_lockstep.hip).  condition (N, condition_dim, T[, 1]) on the device, uniforms (T, N[, nr_mix])
+        host doubles; ``lengths`` (N,): sequence i runs lengths[i] - 1 steps and the rest of its row is 0.  Returns the
+        host array (N, T) in the caller's order (plus the logits (steps, N, out_dim) when ``return_logits``).  One
+        sequence alone is faster on generate_sequence (persistent kernel); see INTEGRATION.md "Generation"."""
+        from .core import Variable
+        from .generation import run_lockstep
+        cd = condition.data if isinstance(condition, Variable) else condition
+        backend.require_device(cd)
+        mode = _lib.GEN_MOL if self.use_logistic else _lib.GEN_SOFTMAX
+        return run_lockstep(self, cd, uniforms, mode, n_steps, lengths, forced, return_logits, graph_steps, group)

@@ -668,11 +668,18 @@ int vqvae_comm_destroy(void* comm);
  *      device-side step counter.  Because the step index lives in device memory the identical
  *      launch sequence serves every step: capture it once with vqvae_graph_* and replay.
  *      "initialize" (modules.py:58-67, 232-244) = the caller zero-fills step, x_cur, x_prev and
- *      every ring.  All weights in their Chainer layout.                                     */
+ *      every ring.  All weights in their Chainer layout.
+ *      n = 1..VQVAE_GEN_MAX_LOCKSTEP.  n <= VQVAE_GEN_MAX_N runs the matrix-vector kernels (the batch in
+ *      registers); n > VQVAE_GEN_MAX_N runs the lockstep kernels (the batch in MFMA columns, fp32 in / fp32
+ *      accumulate): same step semantics, same state layouts (n, C) / (ring_len, n, C) sized by the caller for
+ *      its n, nothing written for sequences >= n.  A sequence's values are the same from run to run and do
+ *      not depend on n or on the other sequences of the batch (within the lockstep kernels; the two kernel
+ *      families sum in different orders and agree to fp32 rounding).                             */
 #define VQVAE_GEN_NONE    0   /* no sampling: logits only, the caller writes x_cur (modules.py:246) */
 #define VQVAE_GEN_SOFTMAX 1   /* numpy.random.choice over softmax(y) (generate.py:135-141)          */
 #define VQVAE_GEN_MOL     2   /* softmax-weighted logistic samples (generate.py:113-133)            */
-#define VQVAE_GEN_MAX_N   4
+#define VQVAE_GEN_MAX_N   4          /* the persistent kernel (vqvae_wavenet_gen_run*) and WaveNet.initialize */
+#define VQVAE_GEN_MAX_LOCKSTEP 128   /* vqvae_wavenet_gen_step                                                */
 typedef struct {
   const float* conv_W; const float* conv_b;   /* (dilated, residual, 2), (dilated)    modules.py:13-16 */
   const float* cond_W; const float* cond_b;   /* (dilated, cond_dim), (dilated)       modules.py:17-18 */
@@ -682,7 +689,8 @@ typedef struct {
   int dilation;
 } vqvae_gen_block;
 typedef struct {
-  int n;                     /* sequences in lockstep, 1..VQVAE_GEN_MAX_N (generate.py:42: 1)        */
+  int n;                     /* sequences in lockstep (generate.py:42: 1): 1..VQVAE_GEN_MAX_LOCKSTEP for
+                                vqvae_wavenet_gen_step, 1..VQVAE_GEN_MAX_N for vqvae_wavenet_gen_run     */
   int n_blocks;
   int input_dim, residual, dilated, skip, cond_dim, out_dim;
   int sample_mode;           /* VQVAE_GEN_*                                                          */
@@ -724,7 +732,7 @@ int vqvae_wavenet_gen_step(const vqvae_gen_desc* d, vqvae_stream_t s);
  * from the descriptor: residual, skip, out_dim, cond_dim <= 256 and dilated <= 256 (128 workgroups),
  * or residual, skip, out_dim <= 512, dilated <= 512 and cond_dim <= 640 (256 workgroups: the
  * reference's default decoder, params.py).  vqvae_wavenet_gen_run_workspace_bytes returns 0 for any
- * other shape, and when the workgroups of one launch cannot all be resident on the current device:
+ * other shape, for n > VQVAE_GEN_MAX_N, and when the workgroups of one launch cannot all be resident on the current device:
  * the caller then drives vqvae_wavenet_gen_step.
  * After the stream has drained, the first int32 of `ws` is 0 on success, non-zero when a bounded
  * device-side wait timed out (the launch then ended early).                                    */

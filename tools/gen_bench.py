@@ -1,5 +1,6 @@
 """Throughput of the device-resident generation loop (generate.py:105-145) at BASELINE decoder sizes.
-usage: python tools/gen_bench.py [--workload c2|c5|ref] [--n 1] [--steps 16000] [--graph-steps 8]"""
+usage: python tools/gen_bench.py [--workload c2|c5|ref] [--n 1] [--steps 16000] [--graph-steps 8]
+       python tools/gen_bench.py --workload ref --lockstep 128 [--group 128] [--steps 4000]"""
 import argparse
 import os
 import sys
@@ -22,6 +23,8 @@ def main():
     ap.add_argument('--group', type=int, default=4)
     ap.add_argument('--streams', type=int, default=8)
     ap.add_argument('--batch', type=int, default=0, help='N sequences through generate_batch (concurrent groups of 4)')
+    ap.add_argument('--lockstep', type=int, default=0, help='N sequences through generate_lockstep (groups of <= --group, default 128, '
+                    'advancing together on the MFMA kernels); --graph-steps 0 = eager launches')
     ap.add_argument('--per-step-kernels', action='store_true', help='hipGraph of per-step kernels instead of the persistent kernel')
     a = ap.parse_args()
     from vqvae_amd import backend
@@ -43,6 +46,23 @@ def main():
     dec.to_gpu()
     dec(Variable(x), Variable(c))
     T = a.steps + 1
+    if a.lockstep:
+        group = a.group if a.group > 4 else 128
+        rs = np.random.RandomState(0)
+        cond = backend.to_device(rs.standard_normal((a.lockstep, Cc, T)).astype(np.float32))
+        u = rs.uniform(0.01, 0.99, (T, a.lockstep, 10 if mol else 1))
+        dec.generate_lockstep(cond, u, n_steps=64, group=group, graph_steps=a.graph_steps)      # warm-up
+        t0 = time.time()
+        o = dec.generate_lockstep(cond, u, group=group, graph_steps=a.graph_steps)
+        dt = time.time() - t0
+        if a.dump:
+            np.save(a.dump, o)
+        ngroups = (a.lockstep + group - 1) // group
+        print('lockstep workload %s N=%d group %d graph-steps %d: %d steps in %.3f s = %.1f us/step/group, %.0f steps/s, '
+              '%.0f samples/s aggregate (%.1f sequences in real time at 16 kHz), distinct outputs %d'
+              % (a.workload, a.lockstep, group, a.graph_steps, a.steps, dt, 1e6 * dt / a.steps / ngroups, a.steps * ngroups / dt,
+                 a.lockstep * a.steps / dt, a.lockstep * a.steps / dt / 16000, len(np.unique(o))))
+        return
     if a.batch:
         rs = np.random.RandomState(0)
         cond = backend.to_device(rs.standard_normal((a.batch, Cc, T)).astype(np.float32))
