@@ -304,9 +304,10 @@ def device_info():
 # drops -- not when the GPU work that uses it has finished.  That is safe on ONE stream (a later
 # user of the block is enqueued behind the earlier one).  Work on the side / pool streams must
 # therefore keep every operand referenced until a join event on the main stream has been
-# enqueued AFTER it: ResidualStackFunction.backward holds gh / saved activations / scratch in
-# locals until its final wait_event; generation.run_many synchronises around its launches.  A
-# new side-stream use that frees a temporary earlier would corrupt memory silently.
+# enqueued AFTER it: ResidualStackFunction.backward holds gh / saved activations / scratch on
+# its wavenet._Sweep (and on the node) until its final wait_event, or hands them to
+# defer_to_side; generation.run_many synchronises around its launches.  A new side-stream use
+# that frees a temporary earlier would corrupt memory silently.
 # --------------------------------------------------------------------------- #
 def _round(nbytes):
     return max(256, (nbytes + 255) // 256 * 256)

@@ -9,7 +9,8 @@ WaveNet level -- initialize(n) / generate(x, condition) / generate_sequence(...)
 per-block push/pop fused into one device-side step (generation.py, csrc/generate.hip).
 """
 import ctypes as C
-import os
+from collections import namedtuple
+from functools import partialmethod
 
 import numpy as np
 
@@ -94,6 +95,21 @@ def _groups(nb, size=_lib.MAX_STACK_GROUP):
     return [(lo, min(nb, lo + size)) for lo in range(0, nb, size)]
 
 
+# one block's parameters: ResidualBlock.param_list is built from it, so this is THE order of every flat list of 8 per block
+BlockParams = namedtuple('BlockParams', 'Wd bd Wc bc Wr br Ws bs')
+
+
+def _per_block(flat):
+    """A flat list of eight entries per block (arrays, Variables, gradients) as one BlockParams per block."""
+    n = len(BlockParams._fields)
+    assert len(flat) % n == 0
+    return [BlockParams(*flat[i:i + n]) for i in range(0, len(flat), n)]
+
+
+def _prm(b):
+    return _lib.ResblockParams(*[a.ptr for a in b])
+
+
 def _value_key(params):
     """The parameters' buffers AND the values in them: pointers, the memory's value versions (backend._Block.wver: in-place
     writes through DeviceArray methods -- Link.copyparams, p.data.set(...) -- and recycled addresses), the load / layout /
@@ -117,31 +133,38 @@ def _owner_steps(pvars):
     return tuple(set(out)) if len(set(out)) <= 1 else tuple(out)
 
 
-def _build_cproj(params, nb, stream):
-    """The latent-rate condition projection of all blocks as ONE conv: its weight (nb * Cd, Cc, 1, 1) and its bias, which
-    also carries the dilated convs' biases (the lerp weights of a column sum to one, so they can ride in the projection:
-    vqvae_resblock_cproj::P_has_bd).  ``params``: 8 arrays per block (ResidualBlock.param_list order)."""
-    Cd, Cc = params[2].shape[0], params[2].shape[1]
-    Wc_all = DeviceArray((nb * Cd, Cc, 1, 1), np.float32)
-    bc_all = DeviceArray((nb * Cd,), np.float32)
-    bd_all = DeviceArray((nb * Cd,), np.float32)
+# The latent-rate condition projection of all blocks as ONE conv: its weight (nb * Cd, Cc, 1, 1) and its bias, which also
+# carries the dilated convs' biases (the lerp weights of a column sum to one, so they can ride in the projection:
+# vqvae_resblock_cproj::P_has_bd; bd_all: kept alive until the add has run); slab_f / slab_b: the weight packed for the
+# forward / backward-data conv over a latent of ``shape`` = (B, Cc, Tl), or None.
+CprojPack = namedtuple('CprojPack', 'Wc_all bc_all bd_all slab_f slab_b shape')
+
+# What ResidualNet.prepack_async leaves for the next forward: the keys the projection / the slabs are valid for, every
+# block's weight slabs and the bytes per block, the side-stream event behind all of it, a CprojPack or None, the skip
+# sum's prepared workspace or None, _owner_steps of the parameters at pack time.
+Prepack = namedtuple('Prepack', 'value_key pack_key slabs stride ready cproj skipws owner_steps')
+
+
+def _build_cproj(blocks, stream):
+    """A CprojPack without slabs from the blocks' parameters: three allocations, then the launches on ``stream``."""
+    nb, (Cd, Cc) = len(blocks), blocks[0].Wc.shape[:2]
+    cp = CprojPack(DeviceArray((nb * Cd, Cc, 1, 1), np.float32), DeviceArray((nb * Cd,), np.float32),
+                   DeviceArray((nb * Cd,), np.float32), None, None, None)
     for lo, hi in _groups(nb):
-        _lib.call('vqvae_concat', Wc_all.ptr + lo * Cd * Cc * 4, _lib.ptr_array([params[8 * i + 2] for i in range(lo, hi)]),
-                  hi - lo, Cd * Cc, stream)
-        _lib.call('vqvae_concat', bc_all.ptr + lo * Cd * 4, _lib.ptr_array([params[8 * i + 3] for i in range(lo, hi)]),
-                  hi - lo, Cd, stream)
-        _lib.call('vqvae_concat', bd_all.ptr + lo * Cd * 4, _lib.ptr_array([params[8 * i + 1] for i in range(lo, hi)]),
-                  hi - lo, Cd, stream)
-    _lib.call('vqvae_elementwise', 0, nb * Cd, bc_all.ptr, bd_all.ptr, bc_all.ptr, 1.0, 1.0, stream)
-    return Wc_all, bc_all, bd_all        # (bd_all: kept alive until the add has run)
+        for dst, name, n in ((cp.Wc_all, 'Wc', Cd * Cc), (cp.bc_all, 'bc', Cd), (cp.bd_all, 'bd', Cd)):
+            _lib.call('vqvae_concat', dst.ptr + lo * n * 4, _lib.ptr_array([getattr(b, name) for b in blocks[lo:hi]]),
+                      hi - lo, n, stream)
+    _lib.call('vqvae_elementwise', 0, nb * Cd, cp.bc_all.ptr, cp.bd_all.ptr, cp.bc_all.ptr, 1.0, 1.0, stream)
+    return cp
 
 
-def _pack_stack(params, d0, nb, stream):
-    """Every block's weight slabs (forward and backward forms) re-laid for this step (vqvae_resstack_pack)."""
+def _pack_stack(blocks, d0, stream):
+    """Every block's weight slabs (forward and backward forms) re-laid for this step (vqvae_resstack_pack): the
+    allocation, then the launch on ``stream``.  Returns (slabs, bytes per block)."""
+    nb = len(blocks)
     per = _lib.load().vqvae_resstack_packed_bytes(C.byref(d0))
     packed = DeviceArray((nb * per // 4,), np.float32)
-    prms = (_lib.ResblockParams * nb)(*[
-        _lib.ResblockParams(*[params[8 * i + j].ptr for j in range(8)]) for i in range(nb)])
+    prms = (_lib.ResblockParams * nb)(*[_prm(b) for b in blocks])
     has_res = (C.c_int * nb)(*([1] * (nb - 1) + [0]))
     _lib.call('vqvae_resstack_pack', C.byref(d0), nb, prms, has_res, packed.ptr, packed.nbytes, stream)
     return packed, per
@@ -167,8 +190,81 @@ def _grad_out(var, shape):
     return DeviceArray(shape, np.float32)
 
 
+def _plan_storage(descs, packed, f16):
+    """vqvae_resblock_desc.storage of every block for the forward and the backward sweep, ([fwd], [bwd]), from one round of
+    queries (they depend on a descriptor's geometry only).  Forward, packed chain only: the residual stream between the
+    blocks kept as bf16 (BASELINE configs[4], mode 'bfloat16'; the buffers stay fp32-sized, half used) or, with ``f16``
+    ('float32x2'), PRE-SPLIT (fp16 hi | lo dwords under an a-priori bound: its three readers stage it with two v_perm_b32
+    per element pair instead of splitting it again) -- every block but the last stores its residual output that way, every
+    block but the first reads it; and of tanh, sigmoid, z only the last two are saved (the backward takes tanh = z /
+    sigmoid).  Backward: those, plus gh_l as bf16 / pre-split and the gradient stream g_res_l = gx_{l+1} as bf16."""
+    nb = len(descs)
+    fwd = [0] * nb
+    if not packed:
+        return fwd, fwd
+    lib = _lib.load()
+    sup16 = [lib.vqvae_resblock_bf16_storage(C.byref(d)) if BF16_STORAGE else 0 for d in descs]
+    supx2 = [lib.vqvae_resblock_f16x2_storage(C.byref(d)) if f16 else 0 for d in descs]
+    for l in range(nb):
+        if sup16[l] & _lib.STORE_RES_BF16 and sup16[l] & _lib.STORE_X_BF16:
+            fwd[l] = (_lib.STORE_RES_BF16 if l < nb - 1 else 0) | (_lib.STORE_X_BF16 if l > 0 else 0)
+        if supx2[l] & _lib.STORE_RES_F16X2 and supx2[l] & _lib.STORE_X_F16X2:
+            fwd[l] = (_lib.STORE_RES_F16X2 if l < nb - 1 else 0) | (_lib.STORE_X_F16X2 if l > 0 else 0)
+        fwd[l] |= supx2[l] & _lib.STORE_GATES_SIG
+    gh = supx2[0] & _lib.STORE_GH_F16X2 if f16 else sup16[0] & _lib.STORE_GH_BF16
+    gs = sup16[0] & _lib.STORE_GX_BF16 and sup16[0] & _lib.STORE_GRES_BF16
+    bwd = [fwd[l] | gh | (_lib.STORE_GX_BF16 if gs and l >= 1 else 0) | (_lib.STORE_GRES_BF16 if gs and l <= nb - 2 else 0)
+           for l in range(nb)]
+    return fwd, bwd
+
+
 KEEP_CONTRACT_WORDS = False        # tests: keep a host copy of the last sweep's maxima / scale words in LAST_CONTRACT_WORDS
 LAST_CONTRACT_WORDS = None
+
+
+class ChainWords(object):
+    """Matmul mode 'float32x2': the absolute maximum of every tensor of the chain travels with it as a group of
+    _lib.AMAX_SLOTS device uint32 (float bits) -- groups x_l | gh_l | g_res_l | g_skip; the kernels' epilogues raise the
+    words of what they store (atomicMax), only the tensors that arrive from outside are scanned.  Behind them the SCALE
+    words of the tensors kept pre-split (vqvae_resblock_desc.storage & VQVAE_STORE_*_F16X2): x_l | gh_l again -- the bound
+    each was split under, written by its producer.  One zeroed buffer per step; x(l) ... gh_scale(l) are device addresses."""
+    FIRST = {'x': (0, 0), 'gh': (1, 0), 'g_res': (2, 0), 'g_skip': (3, 0), 'x_scale': (3, 1), 'gh_scale': (4, 1)}
+
+    def __init__(self, nb):
+        self.nb = nb
+        self.buf = backend.zeros(((5 * nb + 1) * _lib.AMAX_SLOTS,), np.uint32)
+
+    @classmethod
+    def index(cls, nb, what, l=0):
+        """Group number of ``what`` for block l in a chain of nb blocks -- also the row of host()'s table."""
+        a, b = cls.FIRST[what]
+        return a * nb + b + l
+
+    def _at(self, what, l=0):
+        return self.buf.ptr + 4 * _lib.AMAX_SLOTS * self.index(self.nb, what, l)
+
+    x, gh, g_res = partialmethod(_at, 'x'), partialmethod(_at, 'gh'), partialmethod(_at, 'g_res')
+    g_skip, x_scale, gh_scale = partialmethod(_at, 'g_skip'), partialmethod(_at, 'x_scale'), partialmethod(_at, 'gh_scale')
+
+    def host(self):
+        """(nb, the words as a host table of one row per group): what KEEP_CONTRACT_WORDS keeps."""
+        return self.nb, self.buf.get().reshape(-1, _lib.AMAX_SLOTS).copy()
+
+
+class _Sweep(object):
+    """What the phases of one ResidualStackFunction.backward share.  Everything the side stream reads or writes is referenced
+    from here or from the node until the join is enqueued or backend.defer_to_side has it (the invariant in backend.py)."""
+    __slots__ = ('indexes', 'cond', 'blocks', 'pvars',       # what was asked for; the inputs as arrays / Variables per block
+                 'g_skip', 'gh_store', 'hpre',               # the incoming gradient; gh_l's storage bit; gh_l is pre-split
+                 'overlap', 'side', 'defer',                 # two-stream sweep and its stream; deferred weight gradients
+                 'tb', 'Tl', 'gP', 'pb_part', 'gh_all',      # latent-rate condition: tables, pulled-back gh, its two batched forms
+                 'dil_group', 'ws_side', 'ws_defer',         # dilated wgrad blocks per launch; scratch of the two side uses
+                 'ghs', 'g_ress', 'g', 'dil_pending')        # per block: gh_l, g_res_l, gradients by name; blocks awaiting dil wgrad
+
+    def grad_out(self, l, name):
+        """Destination of block l's gradient ``name`` (see _grad_out), remembered in self.g."""
+        a = self.g[l][name] = _grad_out(getattr(self.pvars[l], name), getattr(self.blocks[l], name).shape)
+        return a
 
 
 class ResidualStackFunction(FunctionNode):
@@ -185,154 +281,144 @@ class ResidualStackFunction(FunctionNode):
 
     def __init__(self, dilations, relu_out=False, prepacked=None):
         self.dilations = [int(d) for d in dilations]
-        self.prepacked = prepacked       # ResidualNet.prepack_async's (key, packed, stride, event), or None
+        self.prepacked = prepacked       # ResidualNet.prepack_async's Prepack for this step's parameters, or None
         # relu_out: the F.relu WaveNet applies to the skip sum (modules.py:158) in the skip GEMM's epilogue; its backward
         # arrives done when the conv that reads the result masked its gradient (functions.FUSE_RELU_BWD)
         self.relu_out = bool(relu_out)
+        # the latent-rate projection (set by _project_condition): its latent shape, conv descriptor, weight, backward slab
+        self.cproj_shape = self.pdesc = self.Wc_all = self._cslab_b = None
 
     def forward(self, inputs):
         backend.require_device(*inputs)
         x, cond = inputs[0], inputs[1]
-        nb = len(self.dilations)
-        assert len(inputs) == 2 + 8 * nb
-        self.descs, self.saved = [], []
+        blocks = _per_block(inputs[2:])
+        assert len(blocks) == len(self.dilations)
         if self.prepacked is not None:      # whatever becomes of the slabs, the main stream is behind the side stream's writes of them
-            backend.wait_event(_S(), self.prepacked[3])
+            backend.wait_event(_S(), self.prepacked.ready)
+        # The three facts forward and backward branch on, each implying the one before: the condition arrives at the
+        # latent rate (self.lat; else materialised), the weight slabs are laid out once for the step (self.packed; else
+        # per call), the chain runs matmul mode 3, 'float32x2', and its maxima travel with it (self.words)
+        self.lat = cond.latent if isinstance(cond, F.LazyUpsampled) else None                # (B, Cc, Tl)
+        pack = self.lat is not None and PACK_ONCE
+        f16 = pack and _lib.load().vqvae_get_matmul_dtype() == 3
+        self.descs = [_rb_desc(x, cond, b.Wd, b.Ws, dil) for b, dil in zip(blocks, self.dilations)]
+        proj = self._project_condition(inputs[2:], blocks, x.shape[2]) if self.lat is not None else None
+        self.words = ChainWords(len(blocks)) if f16 else None
+        if f16 and getattr(x, 'amax', None) is not None:     # x_0's maximum: it travelled with the tensor, or a scan
+            _lib.call('vqvae_memcpy_d2d', self.words.x(0), x.amax.ptr, 4 * _lib.AMAX_SLOTS, _S())
+        elif f16:
+            _lib.call('vqvae_absmax', x.ptr, x.size, self.words.x(0), _S())
+        self.packed, self.packed_stride, self._skipws = self._stack_slabs(inputs[2:], blocks) if pack else (None, 0, None)
+        self.storage = _plan_storage(self.descs, pack, f16)
+        self.saved = []
         h = x
-        # condition projection at the latent rate (see vqvae_resblock_cproj in the header)
-        self.lat = None
-        if isinstance(cond, F.LazyUpsampled):
-            self.lat = lat = cond.latent                       # (B, Cc, Tl)
-            B, Cc, Tl = lat.shape
-            Cd = inputs[2].shape[0]
-            self.cproj_shape = (B, Cc, Tl)
-            # the projection's weight / bias (the dilated convs' biases ride in the latter: the gate kernels then add no
-            # bias, and their condition term is one more step of the contraction -- vqvae_resblock_cproj::P_has_bd /
-            # P_amax) and its packed slabs: built on the side stream by ResidualNet.prepack_async when the step started, if
-            # the parameters are the ones it saw; else here
-            pre = self.prepacked
-            cp = pre[4] if (pre is not None and pre[0][:5] == _value_key(inputs[2:])) else None
-            self._cslab_b = None
-            if cp is not None:
-                self.Wc_all, bc_all = cp[0], cp[1]
-                slab_f, self._cslab_b = (cp[3], cp[4]) if cp[5] == (B, Cc, Tl) else (None, None)
-            else:
-                self.Wc_all, bc_all, _bd = _build_cproj(inputs[2:], nb, _S())
-                slab_f = None
-            self.pdesc = _lib.Conv1dDesc(B, Cc, Tl, nb * Cd, Tl, 1, 1, 0, 1, 0)
-            P_all = DeviceArray((B, nb * Cd, Tl), np.float32)
-            P_amax = backend.new_amax()
-            ws = backend.workspace(_lib.load().vqvae_conv1d_workspace_bytes(C.byref(self.pdesc)))
-            _lib.call('vqvae_conv1d_fwd_amax', C.byref(self.pdesc), lat.ptr, self.Wc_all.ptr, bc_all.ptr,
-                      P_all.ptr, ws.ptr, ws.nbytes, C.byref(_lib.Conv1dAmax(None, None, P_amax.ptr, _p(slab_f))), _S())
-            tb = F.resize_tables(Tl, x.shape[2])
-        self.packed = None
-        self.amax = None
-        if self.lat is not None and PACK_ONCE and _lib.load().vqvae_get_matmul_dtype() == 3:
-            # matmul mode 3 (float32x2): the absolute maximum of every tensor of the chain travels with it as a
-            # group of _lib.AMAX_SLOTS device uint32 (float bits) -- groups x_l | gh_l | g_res_l | g_skip; the kernels'
-            # epilogues raise the words of what they store (atomicMax), only the tensors that arrive from outside
-            # are scanned.  Behind them the SCALE words of the tensors kept pre-split (vqvae_resblock_desc.storage &
-            # VQVAE_STORE_*_F16X2): x_l | gh_l again -- the bound each was split under, written by its producer
-            self.amax = backend.zeros(((5 * nb + 1) * _lib.AMAX_SLOTS,), np.uint32)
-            if getattr(x, 'amax', None) is not None:     # it travelled with the tensor
-                _lib.call('vqvae_memcpy_d2d', self.amax.ptr, x.amax.ptr, 4 * _lib.AMAX_SLOTS, _S())
-            else:
-                _lib.call('vqvae_absmax', x.ptr, x.size, self.amax.ptr, _S())
-        if self.lat is not None and PACK_ONCE:
-            # every block's weight slabs (forward and backward forms), re-laid once for this step
-            d0 = _rb_desc(x, cond, inputs[2], inputs[8], self.dilations[0])
-            pre = self.prepacked
-            self._skipws = None
-            if pre is not None and pre[0] == _pack_key(inputs[2:], d0):
-                # packed on the side stream while the encoder / quantiser / condition embed ran (ResidualNet.prepack_async)
-                self.packed, self.packed_stride = pre[1], pre[2]
-                self._skipws = pre[5]            # ... and the skip sum's slabs / bias sums (vqvae_resstack_skip_prepare)
-            else:
-                self.packed, self.packed_stride = _pack_stack(inputs[2:], d0, nb, _S())
-        for i, dil in enumerate(self.dilations):
-            Wd, bd, Wc, bc, Wr, br, Ws, bs = inputs[2 + 8 * i: 10 + 8 * i]
-            d = _rb_desc(h, cond, Wd, Ws, dil)
-            prm = _lib.ResblockParams(Wd.ptr, bd.ptr, Wc.ptr, bc.ptr, Wr.ptr, br.ptr, Ws.ptr, bs.ptr)
-            last = (i == nb - 1)
-            if self.packed is not None:
-                # BASELINE configs[4] (matmul mode 'bfloat16'): the residual stream between the blocks kept as bf16 where
-                # the library offers it (vqvae_resblock_desc.storage; the buffers stay fp32-sized, half used): every
-                # block but the last stores its residual output that way, every block but the first reads it
-                sup = _lib.load().vqvae_resblock_bf16_storage(C.byref(d)) if BF16_STORAGE else 0
-                if sup & _lib.STORE_RES_BF16 and sup & _lib.STORE_X_BF16:
-                    d.storage = (0 if last else _lib.STORE_RES_BF16) | (_lib.STORE_X_BF16 if i > 0 else 0)
-                # matmul mode 'float32x2': the same stream kept PRE-SPLIT (fp16 hi | lo dwords under an a-priori bound:
-                # its three readers stage it with two v_perm_b32 per element pair instead of splitting it again)
-                if self.amax is not None:
-                    sup = _lib.load().vqvae_resblock_f16x2_storage(C.byref(d))
-                    if sup & _lib.STORE_RES_F16X2 and sup & _lib.STORE_X_F16X2:
-                        d.storage = (0 if last else _lib.STORE_RES_F16X2) | (_lib.STORE_X_F16X2 if i > 0 else 0)
-                    # ... and of tanh, sigmoid, z = tanh * sigmoid only the last two are saved (a third of the gate
-                    # kernel's stores): the backward takes tanh = z / sigmoid
-                    d.storage |= sup & _lib.STORE_GATES_SIG
-            res = None if last else DeviceArray((d.B, d.Cr, d.T, 1), np.float32)
-            gates = DeviceArray((d.B, d.Cd, d.T), np.float32)
-            z = DeviceArray((d.B, d.Cd // 2, d.T), np.float32)
-            ws = _rb_workspace(d)
-            if self.lat is not None:
-                cp = _lib.ResblockCproj(P_all.ptr + i * d.Cd * Tl * 4, nb * d.Cd * Tl, Tl,
-                                        tb['v0'].ptr, tb['w0'].ptr, tb['w1'].ptr, 1, P_amax.ptr)
-                if self.packed is not None:
-                    am = None
-                    if self.amax is not None:
-                        xpre = bool(d.storage & _lib.STORE_X_F16X2)
-                        am = C.byref(_lib.ResblockAmax(
-                            self._slot(3 * nb + 1 + i) if xpre else self._slot(i), None if last else self._slot(i + 1),
-                            None, None, None, None,
-                            self._slot(i), None if last else self._slot(3 * nb + 1 + i + 1), None))
-                    _lib.call('vqvae_resblock_fwd_packed', C.byref(d), C.byref(prm), h.ptr, C.byref(cp),
-                              _p(res), gates.ptr, z.ptr, ws.ptr, ws.nbytes,
-                              self.packed.ptr + i * self.packed_stride, am, _S())
-                else:
-                    _lib.call('vqvae_resblock_fwd', C.byref(d), C.byref(prm), h.ptr, None, C.byref(cp),
-                              _p(res), None, 0, gates.ptr, z.ptr, ws.ptr, ws.nbytes, _S())
-            else:
-                _lib.call('vqvae_resblock_fwd', C.byref(d), C.byref(prm), h.ptr, cond.ptr, None,
-                          _p(res), None, 0, gates.ptr, z.ptr, ws.ptr, ws.nbytes, _S())
-            self.descs.append(d)
+        for i, b in enumerate(blocks):
+            self.descs[i].storage = self.storage[0][i]
+            res, gates, z = self._block_forward(i, h, cond, b, proj)
             self.saved.append((h, gates, z))
             h = res
-        d = self.descs[0]
-        skip = DeviceArray((d.B, d.Cs, d.T, 1), np.float32)
-        if self.amax is not None:
-            skip.amax = backend.new_amax()       # published by the skip sum's epilogue: the next conv's operand scale
-        skipws = getattr(self, '_skipws', None)
-        for lo, hi in _groups(nb):
-            n = hi - lo
-            zs = _lib.ptr_array([self.saved[i][2] for i in range(lo, hi)])
-            if skipws is not None and n == nb:       # slabs and bias sums were prepared ahead (prepack_async): the GEMM only
-                _lib.call('vqvae_resstack_skip_fwd_prepared', C.byref(d), n, zs, skip.ptr, 0, 1 if self.relu_out else 0,
-                          skipws.ptr, skipws.nbytes, _p(skip.amax), _S())
-                continue
-            ws = backend.workspace(_lib.load().vqvae_resstack_workspace_bytes(C.byref(d), n))
-            Ws = _lib.ptr_array([inputs[2 + 8 * i + 6] for i in range(lo, hi)])
-            bs = _lib.ptr_array([inputs[2 + 8 * i + 7] for i in range(lo, hi)])
-            _lib.call('vqvae_resstack_skip_fwd', C.byref(d), n, Ws, bs, zs, skip.ptr,
-                      0 if lo == 0 else 1, 1 if (self.relu_out and hi == nb) else 0, ws.ptr, ws.nbytes, _p(skip.amax), _S())
-        skip.relu_out = self.relu_out
-        self._skip = skip if self.relu_out else None
+        skip = self._skip_sum(blocks)
         self.retain_inputs(tuple(range(len(inputs))))
         return skip,
 
-    def _check_contract(self, nb, hpre):
+    def _project_condition(self, params, blocks, T):
+        """The condition projection of every block at the latent rate, one conv (see vqvae_resblock_cproj in the header).
+        Its weight / bias (the dilated convs' biases ride in the latter: the gate kernels then add no bias, and their
+        condition term is one more step of the contraction -- vqvae_resblock_cproj::P_has_bd / P_amax) and its packed
+        slabs were built on the side stream by ResidualNet.prepack_async when the step started, if the parameters are the
+        ones it saw; else they are built here, without slabs.  Returns (P_all, P_amax, lerp tables, the CprojPack)."""
+        B, Cc, Tl = self.cproj_shape = tuple(self.lat.shape)
+        nb, Cd = len(blocks), blocks[0].Wd.shape[0]
+        pre = self.prepacked
+        cp = pre.cproj if (pre is not None and pre.value_key == _value_key(params)) else None
+        slab_f = None
+        if cp is None:
+            cp = _build_cproj(blocks, _S())
+        elif cp.shape == (B, Cc, Tl):
+            slab_f, self._cslab_b = cp.slab_f, cp.slab_b
+        self.Wc_all = cp.Wc_all
+        self.pdesc = _lib.Conv1dDesc(B, Cc, Tl, nb * Cd, Tl, 1, 1, 0, 1, 0)
+        P_all = DeviceArray((B, nb * Cd, Tl), np.float32)
+        P_amax = backend.new_amax()
+        ws = backend.workspace(_lib.load().vqvae_conv1d_workspace_bytes(C.byref(self.pdesc)))
+        _lib.call('vqvae_conv1d_fwd_amax', C.byref(self.pdesc), self.lat.ptr, self.Wc_all.ptr, cp.bc_all.ptr,
+                  P_all.ptr, ws.ptr, ws.nbytes, C.byref(_lib.Conv1dAmax(None, None, P_amax.ptr, _p(slab_f))), _S())
+        return P_all, P_amax, F.resize_tables(Tl, T), cp
+
+    def _stack_slabs(self, params, blocks):
+        """(slabs, bytes per block, prepared skip-sum workspace or None): every block's weight slabs, as packed on the side
+        stream while the encoder / quantiser / condition embed ran (ResidualNet.prepack_async; with them the skip sum's
+        slabs / bias sums, vqvae_resstack_skip_prepare) if they are valid for this call, else re-laid here."""
+        d0, pre = self.descs[0], self.prepacked
+        if pre is not None and pre.pack_key == _pack_key(params, d0):
+            return pre.slabs, pre.stride, pre.skipws
+        return _pack_stack(blocks, d0, _S()) + (None,)
+
+    def _block_forward(self, i, h, cond, b, proj):
+        """Block i on input h -> (residual output or None for the last block, gates, z)."""
+        d, nb = self.descs[i], len(self.descs)
+        last = i == nb - 1
+        prm = _prm(b)
+        res = None if last else DeviceArray((d.B, d.Cr, d.T, 1), np.float32)
+        gates = DeviceArray((d.B, d.Cd, d.T), np.float32)
+        z = DeviceArray((d.B, d.Cd // 2, d.T), np.float32)
+        ws = _rb_workspace(d)
+        if proj is None:
+            _lib.call('vqvae_resblock_fwd', C.byref(d), C.byref(prm), h.ptr, cond.ptr, None,
+                      _p(res), None, 0, gates.ptr, z.ptr, ws.ptr, ws.nbytes, _S())
+            return res, gates, z
+        P_all, P_amax, tb = proj[:3]
+        Tl = self.lat.shape[2]
+        cp = _lib.ResblockCproj(P_all.ptr + i * d.Cd * Tl * 4, nb * d.Cd * Tl, Tl,
+                                tb['v0'].ptr, tb['w0'].ptr, tb['w1'].ptr, 1, P_amax.ptr)
+        if self.packed is None:
+            _lib.call('vqvae_resblock_fwd', C.byref(d), C.byref(prm), h.ptr, None, C.byref(cp),
+                      _p(res), None, 0, gates.ptr, z.ptr, ws.ptr, ws.nbytes, _S())
+            return res, gates, z
+        am, w = None, self.words
+        if w is not None:       # (a pre-split x_l is read under its scale words; its maximum goes on as x_max)
+            xpre = bool(d.storage & _lib.STORE_X_F16X2)
+            am = C.byref(_lib.ResblockAmax(
+                w.x_scale(i) if xpre else w.x(i), None if last else w.x(i + 1), None, None, None, None,
+                w.x(i), None if last else w.x_scale(i + 1), None))
+        _lib.call('vqvae_resblock_fwd_packed', C.byref(d), C.byref(prm), h.ptr, C.byref(cp),
+                  _p(res), gates.ptr, z.ptr, ws.ptr, ws.nbytes,
+                  self.packed.ptr + i * self.packed_stride, am, _S())
+        return res, gates, z
+
+    def _skip_sum(self, blocks):
+        d, nb = self.descs[0], len(self.descs)
+        skip = DeviceArray((d.B, d.Cs, d.T, 1), np.float32)
+        if self.words is not None:
+            skip.amax = backend.new_amax()       # published by the skip sum's epilogue: the next conv's operand scale
+        for lo, hi in _groups(nb):
+            n = hi - lo
+            zs = _lib.ptr_array([s[2] for s in self.saved[lo:hi]])
+            if self._skipws is not None and n == nb:       # slabs and bias sums were prepared ahead (prepack_async): the GEMM only
+                _lib.call('vqvae_resstack_skip_fwd_prepared', C.byref(d), n, zs, skip.ptr, 0, 1 if self.relu_out else 0,
+                          self._skipws.ptr, self._skipws.nbytes, _p(skip.amax), _S())
+                continue
+            ws = backend.workspace(_lib.load().vqvae_resstack_workspace_bytes(C.byref(d), n))
+            _lib.call('vqvae_resstack_skip_fwd', C.byref(d), n, _lib.ptr_array([b.Ws for b in blocks[lo:hi]]),
+                      _lib.ptr_array([b.bs for b in blocks[lo:hi]]), zs, skip.ptr,
+                      0 if lo == 0 else 1, 1 if (self.relu_out and hi == nb) else 0, ws.ptr, ws.nbytes, _p(skip.amax), _S())
+        skip.relu_out = self.relu_out
+        self._skip = skip if self.relu_out else None
+        return skip
+
+    def _check_contract(self, hpre):
         """'float32x2': every pre-split tensor of this sweep -- x_l (l >= 1) and, with `hpre`, gh_l -- against the bound it was
         split under (backend.f32x2_contract_violations; one launch, no host round trip unless backend.contract_debug())."""
-        pairs = [(self._slot(3 * nb + 1 + l), self._slot(l)) for l in range(1, nb)
-                 if self.descs[l].storage & _lib.STORE_X_F16X2]
+        w, nb = self.words, len(self.descs)
+        pairs = [(w.x_scale(l), w.x(l)) for l in range(1, nb) if self.descs[l].storage & _lib.STORE_X_F16X2]
         if hpre:
-            pairs += [(self._slot(4 * nb + 1 + l), self._slot(nb + l)) for l in range(nb)]
+            pairs += [(w.gh_scale(l), w.gh(l)) for l in range(nb)]
         if not pairs:
             return
         global LAST_CONTRACT_WORDS
         if KEEP_CONTRACT_WORDS and backend._state.get('arena') is None:           # (tests: the words themselves, per block)
             backend.synchronize()
-            LAST_CONTRACT_WORDS = (nb, self.amax.get().reshape(-1, _lib.AMAX_SLOTS).copy())
+            LAST_CONTRACT_WORDS = w.host()
         sc = (C.c_void_p * len(pairs))(*[p[0] for p in pairs])
         am = (C.c_void_p * len(pairs))(*[p[1] for p in pairs])
         rep = backend.contract_report()
@@ -346,321 +432,278 @@ class ResidualStackFunction(FunctionNode):
                     "(limit 2^%d, %d violation(s) so far): outside the mode's dynamic-range contract (DESIGN.md 3a) -- use "
                     "set_matmul_dtype('float32x3') or backend.set_presplit(4)" % (r['worst_log2'], r['log2_limit'], r['violations']))
 
-    def _slot(self, i):
-        """Device address of group i of self.amax (x_l: l, gh_l: nb + l, g_res_l: 2 nb + l, g_skip: 3 nb; scale words of
-        a pre-split x_l: 3 nb + 1 + l, of a pre-split gh_l: 4 nb + 1 + l)."""
-        return self.amax.ptr + 4 * _lib.AMAX_SLOTS * i
-
     def backward(self, indexes, gys):
+        """The sweep as a schedule.  Two streams: the backward-data chain (gz -> gh -> gx, block by block) is serial and
+        each of its kernels leaves a residency tail (1920 workgroups on 1024 slots); the weight gradients of block l only
+        need gh_l, so they -- and the pull-back of gh_l to the latent rate -- run on the side stream and fill those tails."""
+        s = self._begin_sweep(indexes, gys)
+        self._size_workspaces(s)
+        self._skip_wgrad(s)
+        nb, g_res = len(self.descs), None
+        for i in range(nb - 1, -1, -1):
+            g_res = self._block_backward(s, i, g_res)          # gx of block i is g_res of block i - 1
+            if self.lat is not None:
+                self._block_side_work(s, i)
+        if s.defer:
+            # The weight gradients still due when the chain has reached the first block -- the last group of dilated-conv
+            # gradients and every res conv's -- need nothing that comes later, and what comes later is the latent-rate tail
+            # of the backward pass (~70 launches of 5-30 us on a handful of workgroups each, 0.7 ms of an all but idle chip).
+            # They run BESIDE that tail on the side stream; Variable.backward() joins the streams (backend.join_side)
+            sd = backend.side_stream()
+            backend.wait_event(sd, backend.Event().record(_S()))       # every gh, g_res of the chain is complete
+            self._dil_wgrad(s, sd, s.ws_defer)
+            self._res_wgrad(s, sd, s.ws_defer)
+            backend.defer_to_side([self.saved, s.ghs, s.g_ress, s.g, s.ws_defer, self.packed, self.words, s.g_skip],
+                                  writes=[g[n] for g in s.g for n in ('Wd', 'bd', 'Wr', 'br')])
+        else:
+            self._res_wgrad(s, _S(), None)
+        if s.overlap:
+            # join: what the main stream (and the caller, after backward returns) issues from here is behind the side stream
+            backend.wait_event(_S(), backend.Event().record(s.side))
+        gcond = None
+        if self.lat is not None:
+            gcond = self._cproj_backward(s)
+        elif 1 in indexes:
+            gcond = self._gcond_backward(s)
+        if self.words is not None:
+            self._check_contract(s.hpre)
+        self.saved = None                      # release activations
+        self.packed = None
+        self.words = None
+        return tuple([g_res if 0 in indexes else None, gcond] + [a for g in s.g for a in BlockParams(**g)])
+
+    def _begin_sweep(self, indexes, gys):
+        """The fused ReLU's backward, g_skip's maximum, the backward's storage bits, streams, and the latent-rate
+        destinations (gP and the buffers of the two batched pull-back forms)."""
+        s = _Sweep()
         in_vars = self.get_retained_inputs()
-        ins = [v.data for v in in_vars]
-        cond = ins[1]
-        lat = self.lat
+        s.indexes, s.cond = indexes, in_vars[1].data
+        s.pvars, s.blocks = _per_block(in_vars[2:]), _per_block([v.data for v in in_vars[2:]])
+        nb, w = len(self.descs), self.words
         g_skip = gys[0].data
         if self.relu_out and not getattr(g_skip, 'relu_masked', False):     # the fused ReLU's backward, unless the reader did it
             g0 = g_skip
             g_skip = F._ew(_lib.EW_RELU_BWD, g0, self._skip)
             g_skip.amax = getattr(g0, 'amax', None)
-        nb = len(self.dilations)
-        f16 = self.amax is not None
-        if f16:
+        s.g_skip = g_skip
+        if w is not None:
             if getattr(g_skip, 'amax', None) is not None:
-                _lib.call('vqvae_memcpy_d2d', self._slot(3 * nb), g_skip.amax.ptr, 4 * _lib.AMAX_SLOTS, _S())
+                _lib.call('vqvae_memcpy_d2d', w.g_skip(), g_skip.amax.ptr, 4 * _lib.AMAX_SLOTS, _S())
             else:
-                _lib.call('vqvae_absmax', g_skip.ptr, g_skip.size, self._slot(3 * nb), _S())
-        # BASELINE configs[4] (matmul mode 'bfloat16'): the tensors of the backward chain the library can keep in HBM as
-        # bf16 (vqvae_resblock_desc.storage); the buffers below stay fp32-sized, half used
-        store = 0
-        if self.packed is not None and lat is not None and BF16_STORAGE:
-            store = _lib.load().vqvae_resblock_bf16_storage(C.byref(self.descs[0])) & _lib.STORE_GH_BF16
-        if f16 and self.packed is not None and lat is not None:    # matmul mode 'float32x2': gh kept pre-split
-            store = _lib.load().vqvae_resblock_f16x2_storage(C.byref(self.descs[0])) & _lib.STORE_GH_F16X2
-        hpre = bool(store & _lib.STORE_GH_F16X2)
-        stream16 = (_lib.STORE_X_BF16 | _lib.STORE_RES_BF16 | _lib.STORE_X_F16X2 | _lib.STORE_RES_F16X2       # the forward's choice for the residual stream stays
-                    | _lib.STORE_GATES_SIG)                                                                   # ... and for the saved gate values
-        gstream = 0                                              # ... and its counterpart, the gradient stream g_res_l = gx_{l+1}
-        if self.packed is not None and lat is not None and BF16_STORAGE:
-            sup = _lib.load().vqvae_resblock_bf16_storage(C.byref(self.descs[0]))
-            if sup & _lib.STORE_GX_BF16 and sup & _lib.STORE_GRES_BF16:
-                gstream = _lib.STORE_GX_BF16 | _lib.STORE_GRES_BF16
-        for l, dd in enumerate(self.descs):
-            gs = (gstream & _lib.STORE_GX_BF16 if l >= 1 else 0) | (gstream & _lib.STORE_GRES_BF16 if l <= nb - 2 else 0)
-            dd.storage = (dd.storage & stream16) | store | gs
-        grads = [None] * len(ins)
-        g_res = None
-        ghs = [None] * nb
-        g_ress = [None] * nb
-        # Two streams.  The backward-data chain (gz -> gh -> gx, block by block) is serial and
-        # each of its kernels leaves a residency tail (1920 workgroups on 1024 slots); the
-        # weight gradients of block l only need gh_l, so they -- and the pull-back of gh_l to
-        # the latent rate -- run on the side stream and fill those tails.
-        overlap = backend.overlap_enabled()
-        side = backend.side_stream() if overlap else _S()
-        slot = 'side' if overlap else 'main'
+                _lib.call('vqvae_absmax', g_skip.ptr, g_skip.size, w.g_skip(), _S())
+        for d, bits in zip(self.descs, self.storage[1]):
+            d.storage = bits
+        s.gh_store = self.storage[1][0] & (_lib.STORE_GH_BF16 | _lib.STORE_GH_F16X2)
+        s.hpre = bool(s.gh_store & _lib.STORE_GH_F16X2)
+        s.overlap = backend.overlap_enabled()
+        s.side = backend.side_stream() if s.overlap else _S()
+        s.ghs, s.g_ress, s.dil_pending = [None] * nb, [None] * nb, []
+        s.g = [dict.fromkeys(BlockParams._fields) for _ in range(nb)]
         d0 = self.descs[0]
-        gP = tb = None
-        if lat is not None:
-            Bl, Cc, Tl = lat.shape
-            tb = F.resize_tables(Tl, d0.T)
-            gP = DeviceArray((Bl, nb * d0.Cd, Tl), np.float32)
+        s.tb = s.Tl = s.gP = s.pb_part = s.gh_all = None
+        if self.lat is None:
+            return s
+        Bl, Cc, s.Tl = self.lat.shape
+        s.tb = F.resize_tables(s.Tl, d0.T)
+        s.gP = DeviceArray((Bl, nb * d0.Cd, s.Tl), np.float32)
         # 'float32x2': the pull-back of every gh_l to the latent rate runs inside the launch that produces gh_l
-        # (vqvae_resblock_amax.pb_part) and one reduce launch finishes all blocks; FUSE_PULLBACK = False: a launch per block
-        pb_part = None
-        # (measured in the bf16 mode too: the gate-derivative kernel of that mode loses more than the launch costs -- configs[4]
-        # 18.8 -> 20.4 ms -- so it keeps its pull-back launches)
-        if (f16 and lat is not None and self.packed is not None and FUSE_PULLBACK and d0.Cd == 256
-                and d0.T % 128 == 0 and d0.T >= 64 * Tl):
-            pb_part = DeviceArray((nb, d0.B, d0.T // 128, d0.Cd, 4), np.float32)
+        # (vqvae_resblock_amax.pb_part) and a reduce launch finishes PB_REDUCE_GROUP blocks; FUSE_PULLBACK = False: a launch
+        # per block.  (Measured in the bf16 mode too: the gate-derivative kernel of that mode loses more than the launch
+        # costs -- configs[4] 18.8 -> 20.4 ms -- so it keeps its pull-back launches)
+        if w is not None and FUSE_PULLBACK and d0.Cd == 256 and d0.T % 128 == 0 and d0.T >= 64 * s.Tl:
+            s.pb_part = DeviceArray((nb, d0.B, d0.T // 128, d0.Cd, 4), np.float32)
         # where the pull-back stays a kernel of its own (bf16 mode, float32x3, fp32 MFMA): ONE launch over all blocks' gh when
         # the chain is done (vqvae_upsample_linear_bwd_blocks) instead of a launch per block -- the gh_l then are the
         # slices of one array.  BATCH_PULLBACK = False: a launch per block, as before (same sums in the same order)
-        gh_all = None
-        if (BATCH_PULLBACK and pb_part is None and lat is not None and self.packed is not None and not overlap
-                and not (store & _lib.STORE_GH_F16X2) and Tl >= 3 and d0.T >= 8 * Tl and d0.T % 4 == 0 and d0.T // 4 <= 2048
+        if (BATCH_PULLBACK and s.pb_part is None and self.packed is not None and not s.overlap and not s.hpre
+                and s.Tl >= 3 and d0.T >= 8 * s.Tl and d0.T % 4 == 0 and d0.T // 4 <= 2048
                 and all((dd.B, dd.Cd, dd.T) == (d0.B, d0.Cd, d0.T) for dd in self.descs)):
-            gh_all = DeviceArray((nb, d0.B, d0.Cd, d0.T), np.float32)
-        # side-stream scratch, sized once for everything it will run (never regrown mid-flight)
-        # res-conv weight gradients: one batched launch on the MAIN stream after the chain (it
-        # then overlaps with whatever the side stream still has queued); balances the two queues
-        grp = nb + 1
-        # dilated-conv weight gradients: DIL_GROUP blocks per launch (each block is filter_size
-        # segments of one contraction), so the K splits and their partial slabs are shared by
-        # DIL_GROUP * 8 output tiles instead of 8 -- 5x less slab traffic for the reduce
-        dil_group = max(1, min(DIL_WGRAD_GROUP, _lib.MAX_STACK_GROUP // d0.K))
-        need = max(_lib.load().vqvae_resblock_workspace_bytes(C.byref(d0)),
-                   _lib.load().vqvae_resstack_workspace_bytes(C.byref(d0), min(nb, _lib.MAX_STACK_GROUP)),
-                   _lib.load().vqvae_resstack_dil_wgrad_workspace_bytes(C.byref(d0), min(nb, dil_group)))
-        ws_side = backend.workspace(need, slot)
-        # The weight gradients that are still due when the chain has reached the first block -- the last group of dilated-conv
-        # gradients and every res conv's -- need nothing that comes later, and what comes later is the latent-rate tail of the
-        # backward pass (pull-back reduce, condition embed, encoder, VQ: ~70 launches of 5-30 us on a handful of workgroups
-        # each, 0.7 ms during which the chip is all but idle).  They go to the side stream and run BESIDE that tail;
-        # Variable.backward() joins the streams when the sweep is done (backend.join_side).  DEFER_WGRAD = False: in line.
-        defer = DEFER_WGRAD and not overlap and lat is not None and self.packed is not None
-        if defer:          # (sized for everything this sweep sends to the side stream before the first of it is enqueued)
-            need = max(need, _lib.load().vqvae_conv1d_workspace_bytes(C.byref(self.pdesc)))
-        ws_defer = backend.workspace(need, 'side') if defer else None
-        dil_pending = []          # blocks whose gh exists but whose dilated-conv wgrad is not issued yet
-        gdil = {}                 # block -> (gWd, gbd) destinations
+            s.gh_all = DeviceArray((nb, d0.B, d0.Cd, d0.T), np.float32)
+        return s
 
-        def flush_dil(stream=None, ws=None):
-            stream = side if stream is None else stream
-            ws = ws_side if ws is None else ws
-            if not dil_pending:
-                return
-            if len(dil_pending) > dil_group:          # (the deferred blocks: a launch per group, as in line)
-                rest = dil_pending[dil_group:]
-                del dil_pending[dil_group:]
-                flush_dil(stream, ws)
-                dil_pending.extend(rest)
-                return flush_dil(stream, ws)
-            blocks = list(dil_pending)
-            del dil_pending[:]
-            if overlap:
-                backend.wait_event(side, backend.Event().record(_S()))    # their gh are complete
-            # one launch per kind of x: the blocks whose input is the bf16 residual stream, and the rest (block 0)
+    def _size_workspaces(self, s):
+        """Side-stream scratch, sized once for everything it will run (never regrown mid-flight), and whether the last
+        weight gradients are deferred (DEFER_WGRAD = False: in line)."""
+        d0, nb, lib = self.descs[0], len(self.descs), _lib.load()
+        # dilated-conv weight gradients: dil_group blocks per launch (each block is filter_size segments of one contraction),
+        # so the K splits and their partial slabs are shared by dil_group * 8 output tiles instead of 8
+        s.dil_group = max(1, min(DIL_WGRAD_GROUP, _lib.MAX_STACK_GROUP // d0.K))
+        need = max(lib.vqvae_resblock_workspace_bytes(C.byref(d0)),
+                   lib.vqvae_resstack_workspace_bytes(C.byref(d0), min(nb, _lib.MAX_STACK_GROUP)),
+                   lib.vqvae_resstack_dil_wgrad_workspace_bytes(C.byref(d0), min(nb, s.dil_group)))
+        s.ws_side = backend.workspace(need, 'side' if s.overlap else 'main')
+        s.defer = DEFER_WGRAD and not s.overlap and self.packed is not None
+        if s.defer:          # (sized for everything this sweep sends to the side stream before the first of it is enqueued)
+            need = max(need, lib.vqvae_conv1d_workspace_bytes(C.byref(self.pdesc)))
+        s.ws_defer = backend.workspace(need, 'side') if s.defer else None
+
+    def _skip_wgrad(self, s):
+        """Skip-conv weight gradients need only g_skip and the saved z_l: started right away, one launch per group."""
+        d0, nb = self.descs[0], len(self.descs)
+        gWs = [s.grad_out(l, 'Ws') for l in range(nb)]
+        gbs = [s.grad_out(l, 'bs') for l in range(nb)]
+        if s.overlap:
+            backend.wait_event(s.side, backend.Event().record(_S()))       # g_skip is ready
+        for lo, hi in _groups(nb):
+            zs = _lib.ptr_array([sv[2] for sv in self.saved[lo:hi]])
+            _lib.call('vqvae_resstack_skip_wgrad', C.byref(d0), hi - lo, s.g_skip.ptr, zs,
+                      _lib.ptr_array(gWs[lo:hi]), _lib.ptr_array(gbs[lo:hi]), 0, s.ws_side.ptr,
+                      s.ws_side.nbytes, self.words.g_skip() if self.words is not None else None, s.side)
+
+    def _block_backward(self, s, i, g_res):
+        """Block i's backward-data launch on the main stream (gz, gate derivative -> gh_i, then gx); returns gx.  With a
+        materialised condition the same launch also gives the dilated conv's and the condition projection's gradients."""
+        d, b, w = self.descs[i], s.blocks[i], self.words
+        h, gates, z = self.saved[i]
+        prm = _prm(b)
+        gx = DeviceArray(h.shape, np.float32) if (i > 0 or 0 in s.indexes) else None
+        gWd, gbd = s.grad_out(i, 'Wd'), s.grad_out(i, 'bd')
+        s.g_ress[i] = g_res                # None for the last block: residual unused
+        if self.lat is None:
+            grd = _lib.ResblockGrads(gWd.ptr, gbd.ptr, s.grad_out(i, 'Wc').ptr, s.grad_out(i, 'bc').ptr, *([None] * 4))
+        gh = s.ghs[i] = (DeviceArray((d.B, d.Cd, d.T), np.float32) if s.gh_all is None else
+                         s.gh_all.flat_view(i * d.B * d.Cd * d.T, d.B * d.Cd * d.T, (d.B, d.Cd, d.T)))
+        ws = _rb_workspace(d)
+        if self.lat is None:
+            _lib.call('vqvae_resblock_bwd', C.byref(d), C.byref(prm), h.ptr, s.cond.ptr, gates.ptr,
+                      z.ptr, _p(g_res), s.g_skip.ptr, _p(gx), None, 0, gh.ptr, C.byref(grd), 0,
+                      ws.ptr, ws.nbytes, _S())
+        elif self.packed is None:
+            none = _lib.ResblockGrads(*([None] * 8))
+            _lib.call('vqvae_resblock_bwd', C.byref(d), C.byref(prm), h.ptr, None, gates.ptr,
+                      z.ptr, _p(g_res), s.g_skip.ptr, _p(gx), None, 0, gh.ptr, C.byref(none), 0,
+                      ws.ptr, ws.nbytes, _S())
+        else:
+            am = None
+            if w is not None:      # in: g_res_i, g_skip; out: gh_i and gx = g_res_{i-1}
+                am = C.byref(_lib.ResblockAmax(
+                    None, None, None if g_res is None else w.g_res(i), w.g_skip(),
+                    w.gh(i), w.g_res(i - 1) if (gx is not None and i > 0) else None,
+                    None, None, w.gh_scale(i) if s.hpre else None,
+                    (s.pb_part.ptr + i * (s.pb_part.nbytes // len(self.descs))) if s.pb_part is not None else None,
+                    s.tb['v0'].ptr, s.tb['w0'].ptr, s.tb['w1'].ptr, s.Tl))
+            _lib.call('vqvae_resblock_bwd_packed', C.byref(d), C.byref(prm), h.ptr, gates.ptr,
+                      z.ptr, _p(g_res), s.g_skip.ptr, _p(gx), gh.ptr, ws.ptr, ws.nbytes,
+                      self.packed.ptr + i * self.packed_stride, am, _S())
+        return gx
+
+    def _block_side_work(self, s, i):
+        """Latent-rate condition, behind block i's launch: its dilated-conv weight gradient joins a group (issued when the
+        group is full, unless kept for the deferred batch), gh_i is pulled back to the latent rate."""
+        d, d0, nb, tb = self.descs[i], self.descs[0], len(self.descs), s.tb
+        s.dil_pending.append(i)
+        if (len(s.dil_pending) >= s.dil_group or i == 0) and not (s.defer and i < DEFER_DIL_BLOCKS):
+            self._dil_wgrad(s, s.side, s.ws_side)               # waits (on the side stream) for the chain up to here
+        elif s.overlap:
+            backend.wait_event(s.side, backend.Event().record(_S()))
+        dst, tabs = s.gP.ptr + i * d.Cd * s.Tl * 4, [tb[k].ptr for k in ('w0', 'w1', 'lo0', 'hi0', 'lo1', 'hi1')]
+        if s.pb_part is not None or s.gh_all is not None:
+            pass                       # done in the gate-derivative launch's epilogue and reduced below / one launch after the chain
+        elif s.hpre:
+            _lib.call('vqvae_upsample_linear_bwd_f16x2', s.ghs[i].ptr, d.Cd * d.T, d.B, d.Cd, s.Tl, d.T,
+                      *(tabs + [dst, nb * d.Cd * s.Tl, self.words.gh_scale(i), s.side]))
+        else:
+            _lib.call('vqvae_upsample_linear_bwd_bf16' if s.gh_store & _lib.STORE_GH_BF16 else 'vqvae_upsample_linear_bwd',
+                      s.ghs[i].ptr, d.Cd * d.T, d.B, d.Cd, s.Tl, d.T, *(tabs + [dst, nb * d.Cd * s.Tl, s.side]))
+        # the fused pull-back's partial sums of the blocks the chain has passed, PB_REDUCE_GROUP at a time (round 5: ~15 us
+        # between two chip-filling launches instead of one launch over all blocks in the tail -- 52 us alone, 160 us beside
+        # the deferred weight gradients; round 6, with those 90 us shorter each: one launch behind the chain measures best)
+        if s.pb_part is not None and (i % PB_REDUCE_GROUP == 0):
+            hi_b = min(nb, i + PB_REDUCE_GROUP)
+            _lib.call('vqvae_pullback_reduce_into', s.pb_part.ptr + i * (s.pb_part.nbytes // nb), tb['v0'].ptr, hi_b - i,
+                      d0.B, d0.T, d0.Cd, s.Tl, s.gP.ptr + i * d0.Cd * s.Tl * 4, nb * d0.Cd * s.Tl, _S())
+
+    def _dil_wgrad(self, s, stream, ws):
+        """Dilated-conv weight gradients of the pending blocks (their gh exist), dil_group blocks at a time."""
+        pending, s.dil_pending = s.dil_pending, []
+        w, d0 = self.words, self.descs[0]
+        for at in range(0, len(pending), s.dil_group):
+            blocks = pending[at:at + s.dil_group]
+            if s.overlap:
+                backend.wait_event(s.side, backend.Event().record(_S()))    # their gh are complete
+            # one launch per kind of x: the blocks whose input is the bf16 / pre-split residual stream, and the rest (block 0)
             for x16 in (_lib.STORE_X_BF16, _lib.STORE_X_F16X2, 0):
                 sel = [i for i in blocks if (self.descs[i].storage & (_lib.STORE_X_BF16 | _lib.STORE_X_F16X2)) == x16]
                 if not sel:
                     continue
                 dg = _lib.ResblockDesc.from_buffer_copy(d0)
-                dg.storage = store | x16
+                dg.storage = s.gh_store | x16
                 dils = (C.c_int * len(sel))(*[self.dilations[i] for i in sel])
-                # (a pre-split operand is read under the bound it was split under: its scale words)
-                xam = (C.c_void_p * len(sel))(*[self._slot(3 * nb + 1 + i if x16 == _lib.STORE_X_F16X2 else i)
-                                                for i in sel]) if f16 else None
-                gam = (C.c_void_p * len(sel))(*[self._slot(4 * nb + 1 + i if hpre else nb + i) for i in sel]) if f16 else None
+                xam = gam = None
+                if w is not None:      # (a pre-split operand is read under the bound it was split under: its scale words)
+                    xam = (C.c_void_p * len(sel))(*[w.x_scale(i) if x16 == _lib.STORE_X_F16X2 else w.x(i) for i in sel])
+                    gam = (C.c_void_p * len(sel))(*[w.gh_scale(i) if s.hpre else w.gh(i) for i in sel])
                 _lib.call('vqvae_resstack_dil_wgrad', C.byref(dg), len(sel), dils,
-                          _lib.ptr_array([self.saved[i][0] for i in sel]),
-                          _lib.ptr_array([ghs[i] for i in sel]),
-                          _lib.ptr_array([gdil[i][0] for i in sel]),
-                          _lib.ptr_array([gdil[i][1] for i in sel]), 0, ws.ptr, ws.nbytes,
-                          xam, gam, stream)
+                          _lib.ptr_array([self.saved[i][0] for i in sel]), _lib.ptr_array([s.ghs[i] for i in sel]),
+                          _lib.ptr_array([s.g[i]['Wd'] for i in sel]), _lib.ptr_array([s.g[i]['bd'] for i in sel]),
+                          0, ws.ptr, ws.nbytes, xam, gam, stream)
 
-        # skip-conv weight gradients need only g_skip and the saved z_l: start them right away
-        gWs = [_grad_out(in_vars[2 + 8 * i + 6], ins[2 + 8 * i + 6].shape) for i in range(nb)]
-        gbs = [_grad_out(in_vars[2 + 8 * i + 7], ins[2 + 8 * i + 7].shape) for i in range(nb)]
-        gWr = [None] * nb
-        gbr = [None] * nb
-        if overlap:
-            backend.wait_event(side, backend.Event().record(_S()))       # g_skip is ready
+    def _res_wgrad(self, s, stream, ws):
+        """gWr_l, gbr_l of every block that has a residual output (g_res_l exists once the chain has passed block l + 1): one
+        batched launch per group behind the chain; ``ws`` None: the main stream's workspace."""
+        d0, nb, w = self.descs[0], len(self.descs), self.words
+        for l in range(nb):
+            if s.g_ress[l] is not None:
+                s.grad_out(l, 'Wr')
+                s.grad_out(l, 'br')
+        for a, b in _groups(nb):
+            wsm = ws if ws is not None else backend.workspace(_lib.load().vqvae_resstack_workspace_bytes(C.byref(d0), b - a))
+            zs = _lib.ptr_array([sv[2] for sv in self.saved[a:b]])
+            ram = None
+            if w is not None:      # g_res_l was published by block l + 1's backward-data launch
+                ram = (C.c_void_p * (b - a))(*[None if s.g_ress[l] is None else w.g_res(l) for l in range(a, b)])
+            _lib.call('vqvae_resstack_res_wgrad', C.byref(d0), b - a, _lib.ptr_array(s.g_ress[a:b]), zs,
+                      _lib.ptr_array([g['Wr'] for g in s.g[a:b]]), _lib.ptr_array([g['br'] for g in s.g[a:b]]),
+                      0, wsm.ptr, wsm.nbytes, ram, stream)
+
+    def _cproj_backward(self, s):
+        """Every block's gh has been pulled back to the latent rate (adjoint of the epilogue lerp) into gP; the
+        (nb*Cd, Cc) 1x1 conv's own backward then gives gWc_l, gbc_l and (returned) the condition gradient."""
+        d, nb, lat, tb = self.descs[0], len(self.descs), self.lat, s.tb
+        Cc = lat.shape[1]
+        if s.gh_all is not None:       # neither the fused nor the per-block pull-back ran: ONE launch over all blocks' gh
+            bf = 1 if s.gh_store & _lib.STORE_GH_BF16 else 0
+            _lib.call('vqvae_upsample_linear_bwd_blocks', s.gh_all.ptr, bf, d.B * d.Cd * d.T * (2 if bf else 1), d.Cd * d.T,
+                      nb, d.B, d.Cd, s.Tl, d.T, tb['w0'].ptr, tb['w1'].ptr, tb['lo0'].ptr, tb['hi0'].ptr, tb['lo1'].ptr,
+                      tb['hi1'].ptr, s.gP.ptr, d.Cd * s.Tl, nb * d.Cd * s.Tl, _S())
+        wsc = backend.workspace(_lib.load().vqvae_conv1d_workspace_bytes(C.byref(self.pdesc)))
+        # the condition gradient first: it is what the rest of the sweep (condition embed, quantiser, encoder) waits
+        # for; the projection's own weight gradient is a leaf -- on the side stream behind the other deferred ones
+        gcond = None
+        if 1 in s.indexes:
+            glat = DeviceArray(lat.shape, np.float32)
+            _lib.call('vqvae_conv1d_bwd_data_amax', C.byref(self.pdesc), self.Wc_all.ptr, s.gP.ptr,
+                      glat.ptr, 0, wsc.ptr, wsc.nbytes,
+                      C.byref(_lib.Conv1dAmax(None, None, None, _p(self._cslab_b))), _S())
+            gcond = F.LatentGrad(s.cond.shape, glat)
+        sw, wsw = _S(), wsc
+        if s.defer:
+            sw, wsw = backend.side_stream(), s.ws_defer
+            backend.wait_event(sw, backend.Event().record(_S()))        # gP is complete
+        gWc_all = DeviceArray(self.Wc_all.shape, np.float32)
+        gbc_all = DeviceArray((nb * d.Cd,), np.float32)
+        _lib.call('vqvae_conv1d_bwd_weight', C.byref(self.pdesc), lat.ptr, s.gP.ptr, gWc_all.ptr,
+                  gbc_all.ptr, 0, wsw.ptr, wsw.nbytes, sw)
+        gWc = [s.grad_out(l, 'Wc') for l in range(nb)]
+        gbc = [s.grad_out(l, 'bc') for l in range(nb)]
         for lo, hi in _groups(nb):
-            zs = _lib.ptr_array([self.saved[i][2] for i in range(lo, hi)])
-            _lib.call('vqvae_resstack_skip_wgrad', C.byref(d0), hi - lo, g_skip.ptr, zs,
-                      _lib.ptr_array(gWs[lo:hi]), _lib.ptr_array(gbs[lo:hi]), 0, ws_side.ptr,
-                      ws_side.nbytes, self._slot(3 * nb) if f16 else None, side)
+            _lib.call('vqvae_split', gWc_all.ptr + lo * d.Cd * Cc * 4, _lib.ptr_array(gWc[lo:hi]),
+                      hi - lo, d.Cd * Cc, 0, sw)
+            _lib.call('vqvae_split', gbc_all.ptr + lo * d.Cd * 4, _lib.ptr_array(gbc[lo:hi]),
+                      hi - lo, d.Cd, 0, sw)
+        if s.defer:
+            backend.defer_to_side([gWc_all, gbc_all, s.gP, lat, gWc, gbc, wsw], writes=[gWc_all, gbc_all] + gWc + gbc)
+        return gcond
 
-        pending = [nb]          # res-conv weight gradients are issued for blocks [lo, pending)
-
-        def flush_res(lo, stream=None, ws=None):
-            """gWr_l, gbr_l for blocks lo..pending-1 (their g_res_l exist once the chain has
-            passed block l+1)."""
-            stream = _S() if stream is None else stream
-            hi = pending[0]
-            if hi <= lo:
-                return
-            for i in range(lo, hi):
-                if g_ress[i] is not None:
-                    gWr[i] = _grad_out(in_vars[2 + 8 * i + 4], ins[2 + 8 * i + 4].shape)
-                    gbr[i] = _grad_out(in_vars[2 + 8 * i + 5], ins[2 + 8 * i + 5].shape)
-            for glo, ghi in _groups(hi - lo):
-                a, b = lo + glo, lo + ghi
-                wsm = ws if ws is not None else backend.workspace(_lib.load().vqvae_resstack_workspace_bytes(C.byref(d0), b - a))
-                zs = _lib.ptr_array([self.saved[i][2] for i in range(a, b)])
-                ram = None
-                if f16:      # g_res_l was published by block l + 1's backward-data launch
-                    ram = (C.c_void_p * (b - a))(*[None if g_ress[i] is None else self._slot(2 * nb + i)
-                                                   for i in range(a, b)])
-                _lib.call('vqvae_resstack_res_wgrad', C.byref(d0), b - a, _lib.ptr_array(g_ress[a:b]), zs,
-                          _lib.ptr_array(gWr[a:b]), _lib.ptr_array(gbr[a:b]), 0, wsm.ptr, wsm.nbytes, ram, stream)
-            pending[0] = lo
-
-        for i in range(nb - 1, -1, -1):
-            Wd, bd, Wc, bc, Wr, br, Ws, bs = ins[2 + 8 * i: 10 + 8 * i]
-            d = self.descs[i]
-            h, gates, z = self.saved[i]
-            prm = _lib.ResblockParams(Wd.ptr, bd.ptr, Wc.ptr, bc.ptr, Wr.ptr, br.ptr, Ws.ptr, bs.ptr)
-            need_gx = (i > 0) or (0 in indexes)
-            gx = DeviceArray(h.shape, np.float32) if need_gx else None
-            gp = [_grad_out(in_vars[2 + 8 * i + j], ins[2 + 8 * i + j].shape) for j in range(4)]
-            g_ress[i] = g_res                  # None for the last block: residual unused
-            gh = (DeviceArray((d.B, d.Cd, d.T), np.float32) if gh_all is None else
-                  gh_all.flat_view(i * d.B * d.Cd * d.T, d.B * d.Cd * d.T, (d.B, d.Cd, d.T)))
-            ws = _rb_workspace(d)
-            if lat is not None:
-                # chain on the main stream: gz, gate derivative -> gh, then gx
-                if self.packed is not None:
-                    am = None
-                    if f16:      # in: g_res_i, g_skip; out: gh_i and gx = g_res_{i-1}
-                        am = C.byref(_lib.ResblockAmax(
-                            None, None, None if g_res is None else self._slot(2 * nb + i), self._slot(3 * nb),
-                            self._slot(nb + i), self._slot(2 * nb + i - 1) if (gx is not None and i > 0) else None,
-                            None, None, self._slot(4 * nb + 1 + i) if hpre else None,
-                            (pb_part.ptr + i * (pb_part.nbytes // nb)) if pb_part is not None else None,
-                            tb['v0'].ptr, tb['w0'].ptr, tb['w1'].ptr, Tl))
-
-                    _lib.call('vqvae_resblock_bwd_packed', C.byref(d), C.byref(prm), h.ptr, gates.ptr,
-                              z.ptr, _p(g_res), g_skip.ptr, _p(gx), gh.ptr, ws.ptr, ws.nbytes,
-                              self.packed.ptr + i * self.packed_stride, am, _S())
-                else:
-                    none = _lib.ResblockGrads(*([None] * 8))
-                    _lib.call('vqvae_resblock_bwd', C.byref(d), C.byref(prm), h.ptr, None, gates.ptr,
-                              z.ptr, _p(g_res), g_skip.ptr, _p(gx), None, 0, gh.ptr, C.byref(none), 0,
-                              ws.ptr, ws.nbytes, _S())
-                ghs[i] = gh
-                gdil[i] = (gp[0], gp[1])
-                dil_pending.append(i)
-                if (len(dil_pending) >= dil_group or i == 0) and not (defer and i < DEFER_DIL_BLOCKS):
-                    flush_dil()               # waits (on the side stream) for the chain up to here
-                elif overlap:
-                    backend.wait_event(side, backend.Event().record(_S()))
-                if pb_part is not None or gh_all is not None:
-                    pass                       # done in the gate-derivative launch's epilogue and reduced below / one launch below
-                elif hpre:
-                    _lib.call('vqvae_upsample_linear_bwd_f16x2', gh.ptr, d.Cd * d.T, d.B, d.Cd, Tl, d.T,
-                              tb['w0'].ptr, tb['w1'].ptr, tb['lo0'].ptr, tb['hi0'].ptr, tb['lo1'].ptr,
-                              tb['hi1'].ptr, gP.ptr + i * d.Cd * Tl * 4, nb * d.Cd * Tl, self._slot(4 * nb + 1 + i), side)
-                else:
-                    _lib.call('vqvae_upsample_linear_bwd_bf16' if store & _lib.STORE_GH_BF16 else 'vqvae_upsample_linear_bwd',
-                              gh.ptr, d.Cd * d.T, d.B, d.Cd, Tl, d.T,
-                              tb['w0'].ptr, tb['w1'].ptr, tb['lo0'].ptr, tb['hi0'].ptr, tb['lo1'].ptr,
-                              tb['hi1'].ptr, gP.ptr + i * d.Cd * Tl * 4, nb * d.Cd * Tl, side)
-                gp[2] = gp[3] = None           # condition_proj grads: one latent-rate conv, below
-            else:
-                grd = _lib.ResblockGrads(*([_p(a) for a in gp] + [None] * 4))
-                _lib.call('vqvae_resblock_bwd', C.byref(d), C.byref(prm), h.ptr, cond.ptr, gates.ptr,
-                          z.ptr, _p(g_res), g_skip.ptr, _p(gx), None, 0, gh.ptr, C.byref(grd), 0,
-                          ws.ptr, ws.nbytes, _S())
-            gp += [None, None, None, None]     # res / skip conv grads: batched launches
-            grads[2 + 8 * i: 10 + 8 * i] = gp
-            ghs[i] = gh
-            g_res = gx
-            if pending[0] - i >= grp:          # g_res of blocks i .. pending-1 are all available
-                flush_res(i)
-            # the fused pull-back's partial sums of the blocks the chain has passed, PB_REDUCE_GROUP at a time (round 5: ~15 us
-            # between two chip-filling launches instead of one launch over all blocks in the tail -- 52 us alone, 160 us beside
-            # the deferred weight gradients; round 6, with those 90 us shorter each: one launch behind the chain measures best)
-            if pb_part is not None and (i % PB_REDUCE_GROUP == 0):
-                hi_b = min(nb, i + PB_REDUCE_GROUP)
-                _lib.call('vqvae_pullback_reduce_into', pb_part.ptr + i * (pb_part.nbytes // nb), tb['v0'].ptr, hi_b - i,
-                          d0.B, d0.T, d0.Cd, Tl, gP.ptr + i * d0.Cd * Tl * 4, nb * d0.Cd * Tl, _S())
+    def _gcond_backward(self, s):
+        """Materialised condition: its gradient sum_l Wc_l^T gh_l, one GEMM per group."""
         d = self.descs[0]
-        # weight gradients of the res convs of the blocks not yet covered (those nearest the input)
-        if defer:
-            sd = backend.side_stream()
-            backend.wait_event(sd, backend.Event().record(_S()))       # every gh, g_res of the chain is complete
-            flush_dil(sd, ws_defer)
-            flush_res(0, sd, ws_defer)
-            backend.defer_to_side([self.saved, ghs, g_ress, gdil, ws_defer, self.packed, self.amax, g_skip],
-                                  writes=[a for pair in gdil.values() for a in pair] + gWr + gbr)
-        else:
-            flush_res(0)
-        if overlap:
-            # join: everything issued after this point on the main stream (and everything the
-            # caller issues after backward returns) is ordered behind the side stream's work
-            backend.wait_event(_S(), backend.Event().record(side))
-        if pb_part is not None:
-            pass                               # reduced group by group inside the chain (above)
-        elif gh_all is not None:
-            bf = 1 if store & _lib.STORE_GH_BF16 else 0
-            n = d.B * d.Cd * d.T
-            _lib.call('vqvae_upsample_linear_bwd_blocks', gh_all.ptr, bf, n * (2 if bf else 1), d.Cd * d.T, nb, d.B, d.Cd, Tl, d.T,
-                      tb['w0'].ptr, tb['w1'].ptr, tb['lo0'].ptr, tb['hi0'].ptr, tb['lo1'].ptr, tb['hi1'].ptr,
-                      gP.ptr, d.Cd * Tl, nb * d.Cd * Tl, _S())
-        if lat is not None:
-            # every block's gh has been pulled back to the latent rate (adjoint of the epilogue
-            # lerp) on the side stream; the (nb*Cd, Cc) 1x1 conv's own backward then gives
-            # gWc_l, gbc_l and the condition gradient
-            B, Cc, Tl = lat.shape
-            wsc = backend.workspace(_lib.load().vqvae_conv1d_workspace_bytes(C.byref(self.pdesc)))
-            # the condition gradient first: it is what the rest of the sweep (condition embed, quantiser, encoder) waits
-            # for; the projection's own weight gradient is a leaf -- on the side stream behind the other deferred ones
-            if 1 in indexes:
-                glat = DeviceArray(lat.shape, np.float32)
-                _lib.call('vqvae_conv1d_bwd_data_amax', C.byref(self.pdesc), self.Wc_all.ptr, gP.ptr,
-                          glat.ptr, 0, wsc.ptr, wsc.nbytes,
-                          C.byref(_lib.Conv1dAmax(None, None, None, _p(getattr(self, '_cslab_b', None)))), _S())
-                grads[1] = F.LatentGrad(cond.shape, glat)
-            sw, wsw = _S(), wsc
-            if defer:
-                sw, wsw = backend.side_stream(), ws_defer
-                backend.wait_event(sw, backend.Event().record(_S()))        # gP is complete
-            gWc_all = DeviceArray(self.Wc_all.shape, np.float32)
-            gbc_all = DeviceArray((nb * d.Cd,), np.float32)
-            _lib.call('vqvae_conv1d_bwd_weight', C.byref(self.pdesc), lat.ptr, gP.ptr, gWc_all.ptr,
-                      gbc_all.ptr, 0, wsw.ptr, wsw.nbytes, sw)
-            gWc = [_grad_out(in_vars[2 + 8 * i + 2], ins[2 + 8 * i + 2].shape) for i in range(nb)]
-            gbc = [_grad_out(in_vars[2 + 8 * i + 3], ins[2 + 8 * i + 3].shape) for i in range(nb)]
-            for lo, hi in _groups(nb):
-                _lib.call('vqvae_split', gWc_all.ptr + lo * d.Cd * Cc * 4, _lib.ptr_array(gWc[lo:hi]),
-                          hi - lo, d.Cd * Cc, 0, sw)
-                _lib.call('vqvae_split', gbc_all.ptr + lo * d.Cd * 4, _lib.ptr_array(gbc[lo:hi]),
-                          hi - lo, d.Cd, 0, sw)
-            if defer:
-                backend.defer_to_side([gWc_all, gbc_all, gP, lat, gWc, gbc, wsw], writes=[gWc_all, gbc_all] + gWc + gbc)
-            for i in range(nb):
-                grads[2 + 8 * i + 2] = gWc[i]
-                grads[2 + 8 * i + 3] = gbc[i]
-        elif 1 in indexes:
-            gcond = DeviceArray(cond.shape, np.float32)
-            for lo, hi in _groups(nb):
-                ws = backend.workspace(_lib.load().vqvae_resstack_workspace_bytes(C.byref(d), hi - lo))
-                Wc = _lib.ptr_array([ins[2 + 8 * i + 2] for i in range(lo, hi)])
-                _lib.call('vqvae_resstack_gcond_bwd', C.byref(d), hi - lo, Wc, _lib.ptr_array(ghs[lo:hi]),
-                          gcond.ptr, 0 if lo == 0 else 1, ws.ptr, ws.nbytes, _S())
-            grads[1] = gcond
-        for i in range(nb):
-            grads[2 + 8 * i + 4] = gWr[i]
-            grads[2 + 8 * i + 5] = gbr[i]
-            grads[2 + 8 * i + 6] = gWs[i]
-            grads[2 + 8 * i + 7] = gbs[i]
-        if f16 and self.packed is not None and lat is not None:
-            self._check_contract(nb, hpre)
-        self.saved = None                      # release activations
-        self.packed = None
-        self.amax = None
-        grads[0] = g_res if 0 in indexes else None
-        return tuple(grads)
+        gcond = DeviceArray(s.cond.shape, np.float32)
+        for lo, hi in _groups(len(self.descs)):
+            ws = backend.workspace(_lib.load().vqvae_resstack_workspace_bytes(C.byref(d), hi - lo))
+            _lib.call('vqvae_resstack_gcond_bwd', C.byref(d), hi - lo, _lib.ptr_array([b.Wc for b in s.blocks[lo:hi]]),
+                      _lib.ptr_array(s.ghs[lo:hi]), gcond.ptr, 0 if lo == 0 else 1, ws.ptr, ws.nbytes, _S())
+        return gcond
 
 
 class ResidualBlock(Chain):
@@ -687,8 +730,8 @@ class ResidualBlock(Chain):
                 'every BASELINE config trains with 0 (params.py:42)')
 
     def param_list(self):
-        return [self.conv.W, self.conv.b, self.condition_proj.W, self.condition_proj.b,
-                self.res.W, self.res.b, self.skip.W, self.skip.b]
+        return list(BlockParams(Wd=self.conv.W, bd=self.conv.b, Wc=self.condition_proj.W, bc=self.condition_proj.b,
+                                Wr=self.res.W, br=self.res.b, Ws=self.skip.W, bs=self.skip.b))
 
     def __call__(self, x, condition):
         residual, skip_connection = ResidualBlockFunction(self.dilation).apply(
@@ -707,6 +750,8 @@ class ResidualNet(ChainList):
             self.add_link(ResidualBlock(
                 filter_size, dilation, residual_channels, dilated_channels, skip_channels,
                 condition_dim, dropout_zero_rate))
+        self._prepacked = None        # prepack_async's Prepack, until the next forward takes it
+        self._cproj_shape = None      # (B, Cc, Tl) of the last forward's latent-rate projection: the next prepack_async packs for it
 
     def __call__(self, x, condition):
         return self._forward(x, condition, False)
@@ -720,12 +765,12 @@ class ResidualNet(ChainList):
         args = [x, condition]
         for b in blocks:
             args += b.param_list()
-        pre, self._prepacked = getattr(self, '_prepacked', None), None
-        if pre is not None and pre[6] != _owner_steps(args[2:]):       # an optimizer step between the pack and this forward
+        pre, self._prepacked = self._prepacked, None
+        if pre is not None and pre.owner_steps != _owner_steps(args[2:]):       # an optimizer step between the pack and this forward
             pre = None
         fn = ResidualStackFunction([b.dilation for b in blocks], relu_out=relu, prepacked=pre)
         out = fn.apply(args)[0]
-        self._cproj_shape = getattr(fn, 'cproj_shape', None)     # (B, Cc, Tl) of the latent-rate projection: the next prepack_async packs for it
+        self._cproj_shape = fn.cproj_shape
         return out
 
     def prepack_async(self, B, T, after=None):
@@ -736,45 +781,47 @@ class ResidualNet(ChainList):
         parameters); None: the main stream as it is now.  VAE.__call__ records that event when the step starts but calls this
         AFTER it has enqueued the encoder: launches reach the GPU in the order they are issued -- from Python and from a
         replayed hipGraph alike (ROCm enqueues a graph's nodes one by one, in capture order) -- so 25 side-stream launches
-        issued in front of the first encoder conv delayed the whole critical path by the time it takes to ISSUE them."""
+        issued in front of the first encoder conv delayed the whole critical path by the time it takes to ISSUE them.
+        Each of the three parts below allocates (from the pool, as it is at this call) and then launches."""
         if not (PACK_ONCE and PREPACK_ASYNC):
             return
-        blocks = list(self.children())
-        params = [p.data for b in blocks for p in b.param_list()]
+        pvars = [p for b in self.children() for p in b.param_list()]
+        params = [p.data for p in pvars]
         if any(not isinstance(p, DeviceArray) for p in params):
             return
-        Wd, Wc, Ws = params[0], params[2], params[6]
-        d0 = _lib.ResblockDesc(B, T, Wd.shape[1], Wd.shape[0], Ws.shape[0], Wc.shape[1], Wd.shape[2], blocks[0].dilation)
+        blocks = _per_block(params)
+        nb, b0 = len(blocks), blocks[0]
+        Cd, Cc = b0.Wc.shape[:2]
+        d0 = _lib.ResblockDesc(B, T, b0.Wd.shape[1], b0.Wd.shape[0], b0.Ws.shape[0], Cc, b0.Wd.shape[2],
+                               next(self.children()).dilation)
         side = backend.side_stream()
         backend.wait_event(side, after if after is not None else backend.Event().record(_S()))       # the optimizer's last write of the parameters
-        packed, per = _pack_stack(params, d0, len(blocks), side)
+        packed, per = _pack_stack(blocks, d0, side)
         # ... and, when the last forward projected the condition at the latent rate, that projection's weight / bias
         # (three concats and an add over the blocks' parameters) and its packed slabs for both directions
-        cp, shape = None, getattr(self, '_cproj_shape', None)
+        cp, shape = None, self._cproj_shape
         if shape is not None:
-            nb, Cd = len(blocks), Wc.shape[0]
-            Wc_all, bc_all, bd_all = _build_cproj(params, nb, side)
-            slab_f = slab_b = None
-            if shape[0] == B and shape[1] == Wc.shape[1]:
+            cp = _build_cproj(blocks, side)
+            if shape[0] == B and shape[1] == Cc:
                 lib = _lib.load()
                 descs = (_lib.Conv1dDesc * 2)()
                 for i in range(2):
                     C.pointer(descs[i])[0] = _lib.Conv1dDesc(B, shape[1], shape[2], nb * Cd, shape[2], 1, 1, 0, 1, 0)
-                slab_f = DeviceArray((int(lib.vqvae_conv1d_packed_bytes(C.byref(descs[0]), 0)) // 4,), np.float32)
-                slab_b = DeviceArray((int(lib.vqvae_conv1d_packed_bytes(C.byref(descs[1]), 1)) // 4,), np.float32)
-                _lib.call('vqvae_conv1d_pack', 2, descs, (C.c_void_p * 2)(Wc_all.ptr, Wc_all.ptr), (C.c_int * 2)(0, 1),
-                          (C.c_void_p * 2)(slab_f.ptr, slab_b.ptr), side)
-            cp = (Wc_all, bc_all, bd_all, slab_f, slab_b, tuple(shape) if slab_f is not None else None)
+                cp = cp._replace(
+                    slab_f=DeviceArray((int(lib.vqvae_conv1d_packed_bytes(C.byref(descs[0]), 0)) // 4,), np.float32),
+                    slab_b=DeviceArray((int(lib.vqvae_conv1d_packed_bytes(C.byref(descs[1]), 1)) // 4,), np.float32),
+                    shape=tuple(shape))
+                _lib.call('vqvae_conv1d_pack', 2, descs, (C.c_void_p * 2)(cp.Wc_all.ptr, cp.Wc_all.ptr), (C.c_int * 2)(0, 1),
+                          (C.c_void_p * 2)(cp.slab_f.ptr, cp.slab_b.ptr), side)
         # ... and the skip sum's weight slabs and bias sums (one contraction over all blocks: vqvae_resstack_skip_prepare)
         skipws = None
-        if len(blocks) <= _lib.MAX_STACK_GROUP:
-            nbytes = _lib.load().vqvae_resstack_workspace_bytes(C.byref(d0), len(blocks))
+        if nb <= _lib.MAX_STACK_GROUP:
+            nbytes = _lib.load().vqvae_resstack_workspace_bytes(C.byref(d0), nb)
             skipws = DeviceArray((int(nbytes) // 4 + 1,), np.float32)
-            _lib.call('vqvae_resstack_skip_prepare', C.byref(d0), len(blocks),
-                      _lib.ptr_array([params[8 * i + 6] for i in range(len(blocks))]),
-                      _lib.ptr_array([params[8 * i + 7] for i in range(len(blocks))]), skipws.ptr, skipws.nbytes, side)
-        self._prepacked = (_pack_key(params, d0), packed, per, backend.Event().record(side), cp, skipws,
-                           _owner_steps([p for b in blocks for p in b.param_list()]))
+            _lib.call('vqvae_resstack_skip_prepare', C.byref(d0), nb, _lib.ptr_array([b.Ws for b in blocks]),
+                      _lib.ptr_array([b.bs for b in blocks]), skipws.ptr, skipws.nbytes, side)
+        self._prepacked = Prepack(_value_key(params), _pack_key(params, d0), packed, per, backend.Event().record(side),
+                                  cp, skipws, _owner_steps(pvars))
 
 
 class WaveNet(Chain):

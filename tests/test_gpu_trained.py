@@ -74,19 +74,22 @@ def trained(gpu):
 
 def _looseness(nb):
     """log2(bound / actual maximum) of every pre-split tensor of the last backward sweep, from the chain's own words
-    (wavenet.ResidualStackFunction._slot: x_l at l, gh_l at nb + l, scale words of x_l at 3 nb + 1 + l, of gh_l at 4 nb + 1 + l)."""
+    (one row per group of words, numbered by wavenet.ChainWords.index)."""
     from vqvae_amd import wavenet
     n, words = wavenet.LAST_CONTRACT_WORDS
     assert n == nb
+
+    def row(what, l):
+        return words[wavenet.ChainWords.index(nb, what, l)]
 
     def f(u):
         return float(np.array([u], np.uint32).view(np.float32)[0])
     lx, lg = {}, {}
     for l in range(nb):
-        bx, mx = f(words[3 * nb + 1 + l][0]), f(words[l].max())
+        bx, mx = f(row('x_scale', l)[0]), f(row('x', l).max())
         if bx > 0 and mx > 0:
             lx[l] = float(np.log2(bx / mx))
-        bg, mg = f(words[4 * nb + 1 + l][0]), f(words[nb + l].max())
+        bg, mg = f(row('gh_scale', l)[0]), f(row('gh', l).max())
         if bg > 0 and mg > 0:
             lg[l] = float(np.log2(bg / mg))
     return lx, lg
