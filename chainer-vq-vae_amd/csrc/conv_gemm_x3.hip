@@ -1,7 +1,8 @@
 // conv_gemm_x3.hip -- matmul modes 1-3: forward and backward-data of every conv on the 16-bit matrix pipe
 // (conv_gemm_x3_kernel: NP = 3 six bf16 products of an exact split, NP = 2 three fp16 products of a scaled split, NP = 1
 // operands rounded to bf16), the streaming residual 1x1 (lin128_stream_kernel), the split-K reduce, and launch_gemm, which
-// picks the kernel of a launch in every mode.
+// picks the kernel of a launch in every mode (the chain's float32x2 gate-derivative launch with the fused pull-back goes to
+// gate_bwd_strip.hip's streaming kernel; its tiled instantiation here serves every other gate-derivative launch).
 #include "gemm_common.h"
 
 namespace vq {
@@ -1009,6 +1010,9 @@ int launch_gemm(GemmArgs& g, int tag, hipStream_t st) {
       if (g.pb_part) VQ_REQUIRE(g.M == 128 && g.Tout % BN == 0 && g.lerp.v0 && g.lerp.w0 && g.lerp.w1 && (long)g.Tout >= 64L * g.lerp.Tl,
                                 "conv_gemm: the fused latent pull-back serves 128 gate channels, T %% 128 == 0, T >= 64 Tl");
       const int out = (g.h16 ? 1 : 0) | (g.pb_part ? 2 : 0);
+      // ResidualNet's chain (pre-split gh + pull-back, g_res | g_skip): the column-strip streaming kernel, 16 waves per CU.
+      // Same bits; every other launch (the stack's last block has no g_res, OUT = 1 / 2) stays on the tiles below
+      if (out == 3 && tap2 && gate_bwd_strip_shape(g)) return launch_gate_bwd_strip(g, attach ? tag : 0, st);
 #define GB_LAUNCH(OUTv)                                                                                                  \
       do {                                                                                                                \
         if (tap2) LG_LAUNCH((conv_gemm_x3_kernel<EPI_GATE_BWD, 2, 1, 2, true, 0, OUTv>), dim3((unsigned)grid), dim3(256), g); \

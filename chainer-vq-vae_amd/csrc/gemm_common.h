@@ -4,6 +4,7 @@
 //   conv_gemm_x3.hip     conv_gemm_x3_kernel (modes 1-3: fwd and bwd-data of every conv, gate / gate-derivative GEMMs),
 //                        lin128_stream_kernel, the split-K reduce, launch_gemm
 //   conv_gemm_fp32.hip   conv_gemm_kernel (mode 0: v_mfma_f32_32x32x2_f32)
+//   gate_bwd_strip.hip   gate_bwd_strip_kernel (mode 3: the chain's gate-derivative GEMM with the fused pull-back, streaming)
 //   wgrad.hip            wgrad3_kernel / wgrad2_kernel / wgrad_kernel, their reduce, plan_wgrad, launch_wgrad
 //   conv_api.hip         weight packing, maxima and norms (pack / wamax / absmax / wl1 kernels) and the C ABI of the conv,
 //                        ResidualBlock and ResidualNet entry points
@@ -1069,6 +1070,10 @@ size_t ksplit_partial_floats(int M, int Tout, int B, int nk);
 // conv_gemm_fp32.hip: the mode-0 kernel of a launch_gemm<EPI> call (wm: 4 = 256-row tiles, 2 = 128-row); tag != 0: timed by
 // the dispatch's own events
 template <int EPI> int launch_gemm_fp32(const GemmArgs& g, int wm, unsigned grid, int tag, hipStream_t st);
+// gate_bwd_strip.hip: the column-strip streaming form of the float32x2 gate-derivative GEMM with the fused pull-back (same
+// bits as conv_gemm_x3_kernel's); launch_gemm<EPI_GATE_BWD> asks _shape first.  tag != 0: timed by the dispatch's own events
+bool gate_bwd_strip_shape(const GemmArgs& g);
+int launch_gate_bwd_strip(const GemmArgs& g, int tag, hipStream_t st);
 // wgrad.hip
 WgradPlan plan_wgrad(int M, int B, int Tout, const int* cins, int nseg, bool wide = false);
 bool wgrad_dma_shape(int M, int Tout, const int* cins, int nseg);     // float32x2 with both operands pre-split: does this shape run on wgrad3_dma_kernel?
