@@ -129,8 +129,9 @@ __global__ void pack_kernel(const PackArgs pa) {
 // workgroups per ResidualBlock, once per step beside pack_kernel:
 //   out[0] = max_r (sum_c |Wr[r][c]| + |br[r]|)   bounds |Wr z + br| for |z| <= 1                (x_{l+1}'s bound)
 //   out[1] = max_c sum_r |Wr[r][c]|,  out[2] = max_c sum_s |Ws[s][c]|   bound |Wr^T g|, |Ws^T g| per unit max |g|  (gh_l's bound)
-// Wr (Cr, Ch), Ws (Cs, Ch) row-major (Chainer (Cout, Cin, 1, 1)).  fp32 sums of <= 256 magnitudes: relative error
-// 2^-16, inside bound_margin's 2^-10.
+// Wr (Cr, Ch), Ws (Cs, Ch) row-major (Chainer (Cout, Cin, 1, 1)).  fp32 sums of n non-negative magnitudes: relative error
+// below (n - 1) 2^-24 whatever the order -- rows Ch <= 256 terms (2^-16), columns Cr, Cs <= 512 terms (2^-15, the
+// 512-channel decoder) -- inside bound_margin's 2^-10.
 // ---------------------------------------------------------------------------
 // grid (blocks of the stack, 3): y = 0 the row norms of Wr (a wave per row: lanes across the contiguous c axis), y = 1 / 2 the
 // column norms of Wr / Ws (a thread per column, coalesced across c, the rows split over the workgroup's thread groups)
@@ -669,7 +670,7 @@ static int bf16_storage_supported(const vqvae_resblock_desc* d) {
 }
 
 // matmul mode 3 (float32x2): the tensors of the packed chain that can be kept PRE-SPLIT (see presplit_pair) -- the
-// configs-sized blocks whose two-tap GEMMs run the 256 x 128-tile loop and whose residual 1x1 runs the streaming kernel.
+// blocks whose two-tap GEMMs run the 256 x 128-tile loop and whose residual 1x1 runs a streaming kernel.
 // vqvae_set_presplit(0) makes the library report none.
 static int g_presplit = 7;           // (vqvae_set_presplit) bit 0: gh, bit 1: the residual stream, bit 2: sigmoid + z instead of tanh + sigmoid + z
 static int f16x2_storage_supported(const vqvae_resblock_desc* d) {
@@ -677,7 +678,12 @@ static int f16x2_storage_supported(const vqvae_resblock_desc* d) {
   static const int lin128 = getenv("VQVAE_LIN128") ? atoi(getenv("VQVAE_LIN128")) : 32;
   static const int lean = getenv("VQVAE_X3_LEAN") ? atoi(getenv("VQVAE_X3_LEAN")) : X3_LEAN;
   if (!on || g_matmul_dtype != 3 || g_wgrad_impl == 1 || !lean) return 0;
-  if (!(d->K == 2 && d->Cd == 256 && d->Cr == 256 && d->T % 128 == 0 && d->dil < d->T &&
+  // the two shape classes the chain is built for: the configs-sized blocks (256 channels) and the reference's default
+  // decoder (params.py: 512 residual / dilated channels, 256 or 512 skip channels), whose residual 1x1 streams through
+  // lin256_stream_kernel
+  const bool base = d->Cd == 256 && d->Cr == 256;
+  const bool wide = d->Cd == 512 && d->Cr == 512 && (d->Cs == 256 || d->Cs == 512);
+  if (!(d->K == 2 && (base || wide) && d->T % 128 == 0 && d->dil < d->T &&
         (long)d->B * d->Cd * d->T * 4 < (1L << 31))) return 0;
   int m = 0;
   if (on & 1) m |= VQVAE_STORE_GH_F16X2;
@@ -732,6 +738,12 @@ extern "C" int vqvae_set_presplit(int mask) {
 extern "C" int vqvae_resblock_f16x2_storage(const vqvae_resblock_desc* d) {
   if (!d || d->Cd <= 0) return 0;
   return f16x2_storage_supported(d);
+}
+// Can the float32x2 gate-derivative launch of this block carry the latent pull-back of gh (vqvae_resblock_amax::pb_part)?
+// A workgroup leaves the sums of ALL 2 Ch gh channels under its 128-column tile, i.e. gz is one 128-row tile: 128 gate
+// channels (launch_gemm<EPI_GATE_BWD>).  The 512-channel decoder pulls gh back with vqvae_upsample_linear_bwd_f16x2.
+extern "C" int vqvae_get_fused_pullback(const vqvae_resblock_desc* d) {
+  return (d && g_matmul_dtype == 3 && d->Cd == 2 * 128 && d->T > 0 && d->T % BN == 0) ? 1 : 0;
 }
 
 extern "C" size_t vqvae_resblock_workspace_bytes(const vqvae_resblock_desc* d) {

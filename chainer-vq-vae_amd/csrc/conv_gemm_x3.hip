@@ -880,6 +880,8 @@ int launch_gemm(GemmArgs& g, int tag, hipStream_t st) {
   if constexpr (EPI == EPI_LINEAR) {
     static const int lin128 = getenv("VQVAE_LIN128") ? atoi(getenv("VQVAE_LIN128")) : 32;   // 0: off; 32 / 64: column tile
     const Seg& s0 = g.seg[0];
+    // the 512-channel decoder's pre-split chain (K = 256 -> 512 rows): lin_stream_wide.hip's kernel, two row slices per column tile
+    if (lin128 && mode == 3 && lin_wide_shape(g)) return launch_lin_wide(g, attach ? tag : 0, st);
     if (lin128 && mode != 0 && g.nseg == 1 && g.M == 256 && s0.cin == 128 && g.out[1].y == nullptr &&
         !g.out[0].relu && !g.out[0].accumulate && !g.out[0].add_is_mask && s0.tmul == 1 && s0.tdiv == 1 && s0.toff == 0 && s0.Tin == g.Tout &&
         s0.x_cstride == g.Tout && g.Tout % 64 == 0 && s0.vec && s0.ldw >= 256 && g.lerp.P == nullptr &&

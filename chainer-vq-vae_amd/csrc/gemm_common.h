@@ -5,6 +5,7 @@
 //                        lin128_stream_kernel, the split-K reduce, launch_gemm
 //   conv_gemm_fp32.hip   conv_gemm_kernel (mode 0: v_mfma_f32_32x32x2_f32)
 //   gate_bwd_strip.hip   gate_bwd_strip_kernel (mode 3: the chain's gate-derivative GEMM with the fused pull-back, streaming)
+//   lin_stream_wide.hip  lin256_stream_kernel (mode 3: the residual 1x1 of the 512-channel decoder's pre-split chain, streaming)
 //   wgrad.hip            wgrad3_kernel / wgrad2_kernel / wgrad_kernel, their reduce, plan_wgrad, launch_wgrad
 //   conv_api.hip         weight packing, maxima and norms (pack / wamax / absmax / wl1 kernels) and the C ABI of the conv,
 //                        ResidualBlock and ResidualNet entry points
@@ -1074,6 +1075,10 @@ template <int EPI> int launch_gemm_fp32(const GemmArgs& g, int wm, unsigned grid
 // bits as conv_gemm_x3_kernel's); launch_gemm<EPI_GATE_BWD> asks _shape first.  tag != 0: timed by the dispatch's own events
 bool gate_bwd_strip_shape(const GemmArgs& g);
 int launch_gate_bwd_strip(const GemmArgs& g, int tag, hipStream_t st);
+// lin_stream_wide.hip: the streaming residual 1x1 of the 512-channel decoder's pre-split chain (256 -> 512 rows, x_{l+1} stored
+// pre-split); launch_gemm<EPI_LINEAR> asks _shape first.  tag != 0: timed by the dispatch's own events
+bool lin_wide_shape(const GemmArgs& g);
+int launch_lin_wide(const GemmArgs& g, int tag, hipStream_t st);
 // wgrad.hip
 WgradPlan plan_wgrad(int M, int B, int Tout, const int* cins, int nseg, bool wide = false);
 bool wgrad_dma_shape(int M, int Tout, const int* cins, int nseg);     // float32x2 with both operands pre-split: does this shape run on wgrad3_dma_kernel?

@@ -160,6 +160,7 @@ PROTOTYPES = {
     'vqvae_resblock_bf16_storage': (c_int, [C.POINTER(ResblockDesc)]),
     'vqvae_resblock_f16x2_storage': (c_int, [C.POINTER(ResblockDesc)]),
     'vqvae_set_presplit': (c_int, [c_int]),
+    'vqvae_get_fused_pullback': (c_int, [C.POINTER(ResblockDesc)]),
     'vqvae_pullback_reduce': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     'vqvae_pullback_reduce_into': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     'vqvae_f32x2_contract_check': (c_int, [c_int, PP, PP, c_int, P, P]),

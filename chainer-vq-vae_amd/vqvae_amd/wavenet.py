@@ -510,7 +510,10 @@ class ResidualStackFunction(FunctionNode):
         # (vqvae_resblock_amax.pb_part) and a reduce launch finishes PB_REDUCE_GROUP blocks; FUSE_PULLBACK = False: a launch
         # per block.  (Measured in the bf16 mode too: the gate-derivative kernel of that mode loses more than the launch
         # costs -- configs[4] 18.8 -> 20.4 ms -- so it keeps its pull-back launches)
-        if w is not None and FUSE_PULLBACK and d0.Cd == 256 and d0.T % 128 == 0 and d0.T >= 64 * s.Tl:
+        # -- where the library's gate-derivative launch can carry it (128 gate channels; the 512-channel decoder's gh_l are pulled
+        # back by a launch per block on the side stream, below)
+        if (w is not None and FUSE_PULLBACK and _lib.load().vqvae_get_fused_pullback(C.byref(d0))
+                and d0.T >= 64 * s.Tl):
             s.pb_part = DeviceArray((nb, d0.B, d0.T // 128, d0.Cd, 4), np.float32)
         # where the pull-back stays a kernel of its own (bf16 mode, float32x3, fp32 MFMA): ONE launch over all blocks' gh when
         # the chain is done (vqvae_upsample_linear_bwd_blocks) instead of a launch per block -- the gh_l then are the

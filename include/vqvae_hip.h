@@ -263,6 +263,10 @@ int vqvae_resblock_f16x2_storage(const vqvae_resblock_desc* d);
 /* which tensors vqvae_resblock_f16x2_storage may offer: bit 0 = gh, bit 1 = the residual stream, bit 2 = GATES_SIG
  * (default 7; 0 = every tensor of the chain stays fp32 -- the A/B switch of the pre-split tests) */
 int vqvae_set_presplit(int mask);
+/* 1 when vqvae_resblock_bwd_packed can pull gh back to the latent rate inside its gate-derivative launch for this block
+ * shape in the current matmul mode (vqvae_resblock_amax::pb_part: mode 3, 128 gate channels, T % 128 == 0), else 0 -- the
+ * caller then pulls gh back with vqvae_upsample_linear_bwd* (the 512-channel decoder does)                          */
+int vqvae_get_fused_pullback(const vqvae_resblock_desc* d);
 
 typedef struct {            /* parameters, Chainer layouts (modules.py:13-22)     */
   const float *Wd, *bd;     /* conv            (Cd, Cr, K, 1), (Cd)               */
