@@ -604,6 +604,8 @@ struct RbLayout {
 
 enum { HDR_D = 0, HDR_O = AMAX_SLOTS, HDR_GZ_R = 2 * AMAX_SLOTS, HDR_GZ_S = 3 * AMAX_SLOTS, HDR_BD = 4 * AMAX_SLOTS, HDR_N = 5,   // word offsets into RbLayout::hdr
        HDR_L1 = HDR_N * AMAX_SLOTS, HDR_L1_WORDS = 16 };       // wl1_kernel's three floats (pre-split bounds), behind the maxima
+// the maxima words HDR_x of the block whose workspace slice starts at w
+static const unsigned* hdr_words(const float* w, const RbLayout& L, int hdr_x) { return reinterpret_cast<const unsigned*>(w + L.hdr) + hdr_x; }
 
 static RbLayout rb_layout(const vqvae_resblock_desc* d) {
   RbLayout L;
@@ -661,10 +663,8 @@ static bool gates_bf16(const vqvae_resblock_desc* d) {
 static int bf16_storage_supported(const vqvae_resblock_desc* d) {
   int m = 0;
   if (gates_bf16(d) && d->K == 2 && d->Cd == 256) m |= VQVAE_STORE_GH_BF16;
-  static const int lin128 = getenv("VQVAE_LIN128") ? atoi(getenv("VQVAE_LIN128")) : 32;
   // (the gate GEMM reads a bf16 x in its 256 x 128-tile two-tap form only: not offered when an A/B switch turns that form off)
-  static const int lean = getenv("VQVAE_X3_LEAN") ? atoi(getenv("VQVAE_X3_LEAN")) : X3_LEAN;
-  if (lin128 && lean && gates_bf16(d) && d->K == 2 && d->Cd == 256 && d->T % 128 == 0) m |= VQVAE_STORE_X_BF16 | VQVAE_STORE_RES_BF16;
+  if (lin128_tile() && x3_lean_enabled() && gates_bf16(d) && d->K == 2 && d->Cd == 256 && d->T % 128 == 0) m |= VQVAE_STORE_X_BF16 | VQVAE_STORE_RES_BF16;
   if (gates_bf16(d) && d->K == 2 && d->Cd == 256 && d->Cs == d->Cr && d->T % 128 == 0) m |= VQVAE_STORE_GX_BF16 | VQVAE_STORE_GRES_BF16;
   return m;
 }
@@ -675,9 +675,7 @@ static int bf16_storage_supported(const vqvae_resblock_desc* d) {
 static int g_presplit = 7;           // (vqvae_set_presplit) bit 0: gh, bit 1: the residual stream, bit 2: sigmoid + z instead of tanh + sigmoid + z
 static int f16x2_storage_supported(const vqvae_resblock_desc* d) {
   const int on = g_presplit;
-  static const int lin128 = getenv("VQVAE_LIN128") ? atoi(getenv("VQVAE_LIN128")) : 32;
-  static const int lean = getenv("VQVAE_X3_LEAN") ? atoi(getenv("VQVAE_X3_LEAN")) : X3_LEAN;
-  if (!on || g_matmul_dtype != 3 || g_wgrad_impl == 1 || !lean) return 0;
+  if (!on || g_matmul_dtype != 3 || g_wgrad_impl == 1 || !x3_lean_enabled()) return 0;
   // the two shape classes the chain is built for: the configs-sized blocks (256 channels) and the reference's default
   // decoder (params.py: 512 residual / dilated channels, 256 or 512 skip channels), whose residual 1x1 streams through
   // lin256_stream_kernel
@@ -687,7 +685,7 @@ static int f16x2_storage_supported(const vqvae_resblock_desc* d) {
         (long)d->B * d->Cd * d->T * 4 < (1L << 31))) return 0;
   int m = 0;
   if (on & 1) m |= VQVAE_STORE_GH_F16X2;
-  if ((on & 2) && lin128) m |= VQVAE_STORE_X_F16X2 | VQVAE_STORE_RES_F16X2;
+  if ((on & 2) && lin128_tile()) m |= VQVAE_STORE_X_F16X2 | VQVAE_STORE_RES_F16X2;
   if (on & 4) m |= VQVAE_STORE_GATES_SIG;
   return m;
 }
@@ -809,10 +807,8 @@ static int resblock_fwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
     const int rp = slab_rows(d->Cr);
     for (int j = 0; j < d->K; ++j) {
       Seg& sg = g.seg[j];
-      sg.x = x; sg.x_bstride = (long)d->Cr * T; sg.x_cstride = T; sg.cin = d->Cr; sg.Tin = T;
-      sg.tmul = 1; sg.toff = -(d->K - 1 - j) * d->dil; sg.tdiv = 1;
-      sg.w = w + L.pk_d + (size_t)j * rp * ldd; sg.ldw = ldd;
-      if (f16) { sg.amax = am->x; sg.wamax = reinterpret_cast<const unsigned*>(w + L.hdr) + HDR_D; }
+      seg_stride1(sg, x, d->Cr, T, -(d->K - 1 - j) * d->dil, w + L.pk_d + (size_t)j * rp * ldd, ldd);
+      if (f16) { sg.amax = am->x; sg.wamax = hdr_words(w, L, HDR_D); }
     }
     g.f16x2 = f16 ? 1 : 0;
     if (cproj) {      // condition projection (incl. its bias) arrives pre-computed at latent rate
@@ -821,8 +817,7 @@ static int resblock_fwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
       g.lerp.fold = 1; g.lerp.amax = cproj->P_amax;       // a request: launch_gemm decides (kernel form, shape)
     } else {
       Seg& sc = g.seg[d->K];
-      sc.x = cond; sc.x_bstride = (long)d->Cc * T; sc.x_cstride = T; sc.cin = d->Cc; sc.Tin = T;
-      sc.tmul = 1; sc.toff = 0; sc.tdiv = 1; sc.w = w + L.pk_c; sc.ldw = ldd;
+      seg_stride1(sc, cond, d->Cc, T, 0, w + L.pk_c, ldd);
     }
     g.M = d->Cd; g.Tout = T; g.B = d->B;
     g.out[0].y = gates; g.out[0].y_bstride = (long)d->Cd * T; g.out[0].bias = (cproj && cproj->P_has_bd) ? nullptr : p->bd;
@@ -841,9 +836,8 @@ static int resblock_fwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
     GemmArgs g; memset(&g, 0, sizeof(g));
     g.nseg = 1;
     Seg& sg = g.seg[0];
-    sg.x = z; sg.x_bstride = (long)Ch * T; sg.x_cstride = T; sg.cin = Ch; sg.Tin = T;
-    sg.tmul = 1; sg.toff = 0; sg.tdiv = 1; sg.w = w + L.pk_o; sg.ldw = ldo;
-    if (f16) { sg.amax_static = 1.f; sg.wamax = reinterpret_cast<const unsigned*>(w + L.hdr) + HDR_O; g.f16x2 = 1; }   // |z| = |tanh * sigmoid| <= 1
+    seg_stride1(sg, z, Ch, T, 0, w + L.pk_o, ldo);
+    if (f16) { sg.amax_static = 1.f; sg.wamax = hdr_words(w, L, HDR_O); g.f16x2 = 1; }   // |z| = |tanh * sigmoid| <= 1
     g.M = Mo; g.Tout = T; g.B = d->B;
     int o = 0;
     if (res) {
@@ -865,7 +859,7 @@ static int resblock_fwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
       g.bound_l1 = w + L.hdr + HDR_L1;
       if (cproj && cproj->P_amax) {          // the next block's gate GEMM adds its condition as a K step: leave it room
         g.floor_p = cproj->P_amax;
-        g.floor_w = reinterpret_cast<const unsigned*>(w + (L.slabs - L.pk_d) + L.hdr) + HDR_D;      // the next block's slice of the packed slabs
+        g.floor_w = hdr_words(w + (L.slabs - L.pk_d), L, HDR_D);      // the next block's slice of the packed slabs
       }
     }
     if (g.add16 || g.y16) VQ_REQUIRE(!skip, "resblock_fwd: a bf16 residual stream (desc.storage) is served by the chain form only (no per-block skip output)");
@@ -993,14 +987,12 @@ static int resblock_bwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
     int n = 0;
     if (g_res) {
       Seg& sg = g.seg[n++];
-      sg.x = g_res; sg.x_bstride = (long)d->Cr * T; sg.x_cstride = T; sg.cin = d->Cr; sg.Tin = T;
-      sg.tmul = 1; sg.toff = 0; sg.tdiv = 1; sg.w = wpk + L.pk_gz_r; sg.ldw = ldz;
-      if (f16) { sg.amax = am->g_res; sg.wamax = reinterpret_cast<const unsigned*>(wpk + L.hdr) + HDR_GZ_R; }
+      seg_stride1(sg, g_res, d->Cr, T, 0, wpk + L.pk_gz_r, ldz);
+      if (f16) { sg.amax = am->g_res; sg.wamax = hdr_words(wpk, L, HDR_GZ_R); }
     }
     Seg& ss = g.seg[n++];
-    ss.x = g_skip; ss.x_bstride = (long)d->Cs * T; ss.x_cstride = T; ss.cin = d->Cs; ss.Tin = T;
-    ss.tmul = 1; ss.toff = 0; ss.tdiv = 1; ss.w = wpk + L.pk_gz_s; ss.ldw = ldz;
-    if (f16) { ss.amax = am->g_skip; ss.wamax = reinterpret_cast<const unsigned*>(wpk + L.hdr) + HDR_GZ_S; }
+    seg_stride1(ss, g_skip, d->Cs, T, 0, wpk + L.pk_gz_s, ldz);
+    if (f16) { ss.amax = am->g_skip; ss.wamax = hdr_words(wpk, L, HDR_GZ_S); }
     g.f16x2 = f16 ? 1 : 0;
     g.nseg = n;
     g.M = Ch; g.Tout = T; g.B = d->B;
@@ -1027,10 +1019,8 @@ static int resblock_bwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
     const int rp = slab_rows(d->Cd);
     for (int j = 0; j < d->K; ++j) {
       Seg& sg = g.seg[j];
-      sg.x = gh; sg.x_bstride = (long)d->Cd * T; sg.x_cstride = T; sg.cin = d->Cd; sg.Tin = T;
-      sg.tmul = 1; sg.toff = (d->K - 1 - j) * d->dil; sg.tdiv = 1;
-      sg.w = wpk + L.pk_bd + (size_t)j * rp * ldr; sg.ldw = ldr;
-      if (f16) { sg.amax = hpre ? am->gh_scale : am->gh; sg.wamax = reinterpret_cast<const unsigned*>(wpk + L.hdr) + HDR_BD; }
+      seg_stride1(sg, gh, d->Cd, T, (d->K - 1 - j) * d->dil, wpk + L.pk_bd + (size_t)j * rp * ldr, ldr);
+      if (f16) { sg.amax = hpre ? am->gh_scale : am->gh; sg.wamax = hdr_words(wpk, L, HDR_BD); }
     }
     g.f16x2 = f16 ? 1 : 0;
     g.M = d->Cr; g.Tout = T; g.B = d->B;
@@ -1046,8 +1036,7 @@ static int resblock_bwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
     GemmArgs g; memset(&g, 0, sizeof(g));
     g.nseg = 1;
     Seg& sg = g.seg[0];
-    sg.x = gh; sg.x_bstride = (long)d->Cd * T; sg.x_cstride = T; sg.cin = d->Cd; sg.Tin = T;
-    sg.tmul = 1; sg.toff = 0; sg.tdiv = 1; sg.w = w + L.pk_bc; sg.ldw = ldc;
+    seg_stride1(sg, gh, d->Cd, T, 0, w + L.pk_bc, ldc);
     g.M = d->Cc; g.Tout = T; g.B = d->B;
     g.out[0].y = gcond; g.out[0].y_bstride = (long)d->Cc * T; g.out[0].rows = d->Cc;
     g.out[0].accumulate = gcond_accumulate;
@@ -1060,14 +1049,12 @@ static int resblock_bwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
     wa.nseg = d->K + (cond ? 1 : 0);
     for (int j = 0; j < d->K; ++j) {
       WSeg& sg = wa.seg[j];
-      sg.x = x; sg.x_bstride = (long)d->Cr * T; sg.x_cstride = T; sg.cin = d->Cr; sg.Tin = T;
-      sg.tmul = 1; sg.toff = -(d->K - 1 - j) * d->dil; sg.tdiv = 1;
+      wseg_stride1(sg, x, d->Cr, T, -(d->K - 1 - j) * d->dil);
       sg.gw = gr->gWd ? gr->gWd + j : nullptr; sg.gw_co_stride = (long)d->Cr * d->K; sg.gw_ci_stride = d->K;
     }
     if (cond) {
       WSeg& sc = wa.seg[d->K];
-      sc.x = cond; sc.x_bstride = (long)d->Cc * T; sc.x_cstride = T; sc.cin = d->Cc; sc.Tin = T;
-      sc.tmul = 1; sc.toff = 0; sc.tdiv = 1;
+      wseg_stride1(sc, cond, d->Cc, T, 0);
       sc.gw = gr->gWc; sc.gw_co_stride = d->Cc; sc.gw_ci_stride = 1;
     }
     wa.seg[0].gb = gr->gbd; wa.seg[0].gb2 = gr->gbc; wa.accumulate = grads_accumulate;
@@ -1088,8 +1075,7 @@ static int resblock_bwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
     wa.gy = gy; wa.gy_bstride = (long)M * T; wa.M = M; wa.Tout = T; wa.B = d->B;
     wa.nseg = 1;
     WSeg& sg = wa.seg[0];
-    sg.x = z; sg.x_bstride = (long)Ch * T; sg.x_cstride = T; sg.cin = Ch; sg.Tin = T;
-    sg.tmul = 1; sg.toff = 0; sg.tdiv = 1;
+    wseg_stride1(sg, z, Ch, T, 0);
     sg.gw = gW; sg.gw_co_stride = Ch; sg.gw_ci_stride = 1;
     wa.seg[0].gb = gb; wa.accumulate = grads_accumulate;
     wa.x16 = z_bf16(d) ? 1 : 0;
@@ -1217,8 +1203,7 @@ static int resstack_skip_impl(const vqvae_resblock_desc* d, int nblocks, const f
   g.nseg = nblocks;
   for (int l = 0; l < nblocks; ++l) {
     Seg& sg = g.seg[l];
-    sg.x = z[l]; sg.x_bstride = (long)Ch * T; sg.x_cstride = T; sg.cin = Ch; sg.Tin = T;
-    sg.tmul = 1; sg.toff = 0; sg.tdiv = 1; sg.w = w + (size_t)l * rp * ld; sg.ldw = ld;
+    seg_stride1(sg, z[l], Ch, T, 0, w + (size_t)l * rp * ld, ld);
     if (f16) { sg.amax_static = 1.f; sg.wamax = wam + l * AMAX_SLOTS; }
   }
   g.f16x2 = f16 ? 1 : 0;
@@ -1254,8 +1239,7 @@ extern "C" int vqvae_resstack_gcond_bwd(const vqvae_resblock_desc* d, int nblock
   g.nseg = nblocks;
   for (int l = 0; l < nblocks; ++l) {
     Seg& sg = g.seg[l];
-    sg.x = gh[l]; sg.x_bstride = (long)d->Cd * T; sg.x_cstride = T; sg.cin = d->Cd; sg.Tin = T;
-    sg.tmul = 1; sg.toff = 0; sg.tdiv = 1; sg.w = w + (size_t)l * rp * ld; sg.ldw = ld;
+    seg_stride1(sg, gh[l], d->Cd, T, 0, w + (size_t)l * rp * ld, ld);
   }
   g.M = d->Cc; g.Tout = T; g.B = d->B;
   g.out[0].y = gcond; g.out[0].y_bstride = (long)d->Cc * T; g.out[0].rows = d->Cc;
@@ -1281,8 +1265,7 @@ extern "C" int vqvae_resstack_skip_wgrad(const vqvae_resblock_desc* d, int nbloc
   wa.nseg = nblocks;
   for (int l = 0; l < nblocks; ++l) {
     WSeg& sg = wa.seg[l];
-    sg.x = z[l]; sg.x_bstride = (long)Ch * T; sg.x_cstride = T; sg.cin = Ch; sg.Tin = T;
-    sg.tmul = 1; sg.toff = 0; sg.tdiv = 1;
+    wseg_stride1(sg, z[l], Ch, T, 0);
     sg.gw = gWs[l]; sg.gw_co_stride = Ch; sg.gw_ci_stride = 1;
     wa.gbl[l] = gbs ? gbs[l] : nullptr;
     sg.amax_x_static = 1.f;                                   // |z| <= 1
@@ -1313,8 +1296,7 @@ extern "C" int vqvae_resstack_res_wgrad(const vqvae_resblock_desc* d, int nblock
     if (!g_res[l] || !gWr[l]) continue;
     WSeg& sg = wa.seg[n];
     sg.gy = g_res[l];
-    sg.x = z[l]; sg.x_bstride = (long)Ch * T; sg.x_cstride = T; sg.cin = Ch; sg.Tin = T;
-    sg.tmul = 1; sg.toff = 0; sg.tdiv = 1;
+    wseg_stride1(sg, z[l], Ch, T, 0);
     sg.gw = gWr[l]; sg.gw_co_stride = Ch; sg.gw_ci_stride = 1;
     sg.gb = gbr ? gbr[l] : nullptr;
     sg.amax_x_static = 1.f;                                   // |z| <= 1
@@ -1350,8 +1332,7 @@ extern "C" int vqvae_resblock_wgrad(const vqvae_resblock_desc* d, const float* x
   wa.nseg = d->K;
   for (int j = 0; j < d->K; ++j) {
     WSeg& sg = wa.seg[j];
-    sg.x = x; sg.x_bstride = (long)d->Cr * T; sg.x_cstride = T; sg.cin = d->Cr; sg.Tin = T;
-    sg.tmul = 1; sg.toff = -(d->K - 1 - j) * d->dil; sg.tdiv = 1;
+    wseg_stride1(sg, x, d->Cr, T, -(d->K - 1 - j) * d->dil);
     sg.gw = gWd ? gWd + j : nullptr; sg.gw_co_stride = (long)d->Cr * d->K; sg.gw_ci_stride = d->K;
   }
   wa.seg[0].gb = gbd;
@@ -1382,8 +1363,7 @@ extern "C" int vqvae_resstack_dil_wgrad(const vqvae_resblock_desc* d, int nblock
     for (int j = 0; j < d->K; ++j) {
       WSeg& sg = wa.seg[n];
       sg.gy = gh[l];
-      sg.x = x[l]; sg.x_bstride = (long)d->Cr * T; sg.x_cstride = T; sg.cin = d->Cr; sg.Tin = T;
-      sg.tmul = 1; sg.toff = -(d->K - 1 - j) * dils[l]; sg.tdiv = 1;
+      wseg_stride1(sg, x[l], d->Cr, T, -(d->K - 1 - j) * dils[l]);
       sg.gw = gWd[l] ? gWd[l] + j : nullptr; sg.gw_co_stride = (long)d->Cr * d->K; sg.gw_ci_stride = d->K;
       sg.gb = (j == 0 && gbd) ? gbd[l] : nullptr;
       sg.amax_x = x_amax ? x_amax[l] : nullptr;

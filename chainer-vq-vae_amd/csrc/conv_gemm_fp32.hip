@@ -275,15 +275,8 @@ __global__ __launch_bounds__(128 * WM, (WM == 2 ? (EPI == EPI_LINEAR ? 3 : 4) : 
 
 template <int EPI>
 int launch_gemm_fp32(const GemmArgs& g, int wm, unsigned grid, int tag, hipStream_t st) {
-  hipEvent_t pe0 = nullptr, pe1 = nullptr;
-  const bool attach = tag != 0 && prof_attach(tag, &pe0, &pe1);
-  if (wm == 4) {
-    if (attach) hipExtLaunchKernelGGL((conv_gemm_kernel<EPI, 4, false>), dim3(grid), dim3(512), 0, st, pe0, pe1, 0, g);
-    else hipLaunchKernelGGL((conv_gemm_kernel<EPI, 4, false>), dim3(grid), dim3(512), 0, st, g);
-  } else {
-    if (attach) hipExtLaunchKernelGGL((conv_gemm_kernel<EPI, 2, false>), dim3(grid), dim3(256), 0, st, pe0, pe1, 0, g);
-    else hipLaunchKernelGGL((conv_gemm_kernel<EPI, 2, false>), dim3(grid), dim3(256), 0, st, g);
-  }
+  if (wm == 4) launch_tagged(conv_gemm_kernel<EPI, 4, false>, dim3(grid), dim3(512), st, tag, g);
+  else launch_tagged(conv_gemm_kernel<EPI, 2, false>, dim3(grid), dim3(256), st, tag, g);
   VQ_LAUNCH_CHECK();
   return 0;
 }

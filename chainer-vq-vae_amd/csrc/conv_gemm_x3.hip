@@ -1,8 +1,10 @@
 // conv_gemm_x3.hip -- matmul modes 1-3: forward and backward-data of every conv on the 16-bit matrix pipe
 // (conv_gemm_x3_kernel: NP = 3 six bf16 products of an exact split, NP = 2 three fp16 products of a scaled split, NP = 1
-// operands rounded to bf16), the streaming residual 1x1 (lin128_stream_kernel), the split-K reduce, and launch_gemm, which
-// picks the kernel of a launch in every mode (the chain's float32x2 gate-derivative launch with the fused pull-back goes to
-// gate_bwd_strip.hip's streaming kernel; its tiled instantiation here serves every other gate-derivative launch).
+// operands rounded to bf16), the streaming residual 1x1 (lin128_stream_kernel with lin128_shape / launch_lin128), the split-K
+// reduce, and launch_gemm, the dispatch of a launch in every mode: prepare_gemm normalises the argument block, select_gemm
+// walks the kernel forms in their order of precedence, launch_gemm launches the one named (the chain's float32x2
+// gate-derivative launch with the fused pull-back goes to gate_bwd_strip.hip's streaming kernel; its tiled instantiation
+// here serves every other gate-derivative launch).
 #include "gemm_common.h"
 
 namespace vq {
@@ -788,6 +790,52 @@ __global__ __launch_bounds__(512, 1) void lin128_stream_kernel(const Lin128Args 
 #undef L128_TILE
 }
 
+// the launches lin128_stream_kernel serves: one stride-1 segment z (B, 128, T) -> 256 rows, T % 64 == 0, nothing in the
+// epilogue but the bias and the residual add
+static bool lin128_shape(const GemmArgs& g, int mode) {
+  const Seg& s0 = g.seg[0];
+  return mode != 0 && g.nseg == 1 && g.M == 256 && s0.cin == 128 && g.out[1].y == nullptr &&
+         !g.out[0].relu && !g.out[0].accumulate && !g.out[0].add_is_mask && s0.tmul == 1 && s0.tdiv == 1 && s0.toff == 0 && s0.Tin == g.Tout &&
+         s0.x_cstride == g.Tout && g.Tout % 64 == 0 && s0.vec && s0.ldw >= 256 && g.lerp.P == nullptr &&
+         g.skip_flag == nullptr && g.ksplit == 1;
+}
+
+static int launch_lin128(const GemmArgs& g, int mode, int tag, hipStream_t st) {
+  const Seg& s0 = g.seg[0];
+  Lin128Args la;
+  la.w = reinterpret_cast<const uint4*>(s0.w); la.ldw = s0.ldw;
+  la.z = s0.x; la.z_bstride = s0.x_bstride;
+  la.add = g.out[0].add; la.add_bstride = g.out[0].add_bstride;
+  la.y = g.out[0].y; la.y_bstride = g.out[0].y_bstride;
+  la.bias = g.out[0].bias;
+  la.T = g.Tout;
+  la.wamax = s0.wamax; la.z_amax = s0.amax; la.z_amax_static = s0.amax_static; la.amax_out = g.out[0].amax_out;
+  la.add16 = g.add16; la.y16 = g.y16;
+  la.add_scale = g.add_scale; la.add_amax = g.add_amax; la.l1 = g.bound_l1; la.scale_out = g.scale_out;
+  la.floor_w = g.floor_w; la.floor_p = g.floor_p;
+  const int nc = (lin128_tile() == 32 || g.z16) ? 32 : 64;
+  la.tiles_per_b = g.Tout / nc; la.ntiles = la.tiles_per_b * g.B;
+  static int n_cu = 0;
+  if (n_cu == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
+  }
+  const unsigned nwg = (unsigned)(la.ntiles < n_cu ? la.ntiles : n_cu);
+  const bool add = la.add != nullptr;
+  void (*k)(Lin128Args);
+  if (mode == 2) k = nc == 32 ? (add ? lin128_stream_kernel<3, 32, true> : lin128_stream_kernel<3, 32, false>)
+                              : (add ? lin128_stream_kernel<3, 64, true> : lin128_stream_kernel<3, 64, false>);
+  else if (mode == 3 && (g.add16 || g.y16)) k = g.add16 ? lin128_stream_kernel<2, 32, true, false, true, true> : lin128_stream_kernel<2, 32, true, false, false, true>;
+  else if (mode == 3) k = add ? lin128_stream_kernel<2, 32, true> : lin128_stream_kernel<2, 32, false>;
+  else if (g.add16 || g.y16) k = g.add16 ? lin128_stream_kernel<1, 32, true, true, true, true> : lin128_stream_kernel<1, 32, true, true, false, true>;
+  else if (g.z16) k = add ? lin128_stream_kernel<1, 32, true, true> : lin128_stream_kernel<1, 32, false, true>;
+  else k = nc == 32 ? (add ? lin128_stream_kernel<1, 32, true> : lin128_stream_kernel<1, 32, false>)
+                    : (add ? lin128_stream_kernel<1, 64, true> : lin128_stream_kernel<1, 64, false>);
+  launch_tagged(k, dim3(nwg), dim3(512), st, tag, la);
+  VQ_LAUNCH_CHECK();
+  return 0;
+}
+
 // sums the split-K partial tiles in split order and applies the linear epilogue
 // (bias, residual add, accumulate, relu) of conv_gemm_kernel<EPI_LINEAR>
 __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const GemmArgs a) {
@@ -835,18 +883,60 @@ size_t ksplit_partial_floats(int M, int Tout, int B, int nk) {
   return s > 1 ? (size_t)s * cdiv(M, 128) * cdiv(Tout, BN) * B * 128 * 128 : 0;
 }
 
+// The two environment switches of the dispatch below, each read once per process (declared in gemm_common.h: conv_api.hip's
+// storage predicates promise a caller only what select_gemm will serve under the same two values).
+int lin128_tile() {
+  static const int v = getenv("VQVAE_LIN128") ? atoi(getenv("VQVAE_LIN128")) : 32;   // 0: off; 32 / 64: column tile
+  return v;
+}
+bool x3_lean_enabled() {
+  static const int v = getenv("VQVAE_X3_LEAN") ? atoi(getenv("VQVAE_X3_LEAN")) : X3_LEAN;   // 0: the 256 x 256-tile two-tap kernel, the A/B alternate
+  return v && X3_LEAN;
+}
+
+// ---------------------------------------------------------------------------
+// launch_gemm<EPI>: prepare_gemm normalises the argument block, select_gemm names the kernel form that serves it (or says
+// why none does), launch_gemm launches that form.  A new kernel form is one more entry in select_gemm's ordered list.
+// ---------------------------------------------------------------------------
 template <int EPI>
-int launch_gemm(GemmArgs& g, int tag, hipStream_t st) {
-  // the arithmetic of THIS launch: mode 3 is float32x2 (NP = 2) where the caller provided maxima and a format-3 slab
-  // for every segment, mode 2's six-product kernels everywhere else
-  const int mode = g_matmul_dtype == 3 ? (g.f16x2 ? 3 : 2) : g_matmul_dtype;
+static bool rows256(const GemmArgs& g) { return (g.M % 256 == 0) && (EPI != EPI_GATE_BWD); }    // 256-row tiles (8 waves)
+
+// what the tiled kernels' choice hangs on, from a block whose segments and split-K plan are final
+struct TileTraits { bool big, tap2, lean, wide; };
+template <int EPI>
+static TileTraits tile_traits(const GemmArgs& g, int mode) {
+  TileTraits t;
+  t.big = rows256<EPI>(g);
+  // two taps of one tensor: interleave them channel group by channel group (TAP2).  The choice depends
+  // on the contraction only, never on the tile shape, so that a result does not change with the batch size.
+  t.tap2 = mode != 0 && g.nseg == 2 && g.ksplit == 1 &&
+           g.seg[0].cin == g.seg[1].cin && g.seg[0].cin % BK == 0 &&
+           g.seg[0].x_cstride == g.seg[1].x_cstride && g.seg[0].x_bstride == g.seg[1].x_bstride &&
+           g.seg[0].Tin == g.seg[1].Tin && g.seg[0].tmul == g.seg[1].tmul && g.seg[0].tdiv == g.seg[1].tdiv &&
+           g.seg[0].ldw == g.seg[1].ldw && g.seg[1].w >= g.seg[0].w &&          // second slab addressed off the first's descriptor
+           (reinterpret_cast<const char*>(g.seg[1].w) - reinterpret_cast<const char*>(g.seg[0].w)) < (1L << 30);
+  // Two taps, two or more pieces per operand: 256 x 128 tiles whose loop fits 128 VGPRs (LEAN in conv_gemm_x3_kernel), TWO
+  // workgroups per CU -- one tile's epilogue beside the other's K loop: gate kernel 211 -> 197 us, backward-data
+  // 217 -> 198 us at configs[1] against the 256 x 256 tiles, which stay for every other contraction.  Same K
+  // order and products as the 256 x 256-tile two-tap kernel (x3_lean_enabled() off: the A/B alternate): the choice never changes a result.
+  t.lean = x3_lean_enabled() && t.tap2 && t.big && mode != 0 && EPI != EPI_GATE_BWD;   // mode 1: the 256 x 128 kernel needs 122 VGPRs as it is
+  // 256-column tiles when they still give every CU a workgroup (measured at configs[1]: dilated conv
+  // forward and backward-data -6.5 %, the short 1x1 contractions unchanged)
+  const long nblk2 = (long)g.ntile_m * cdiv(g.Tout, 2 * BN) * g.B;
+  t.wide = mode != 0 && t.big && !t.lean && nblk2 >= 256;
+  return t;
+}
+
+// Everything that writes into g or rejects a malformed g; no later stage mutates it.  (An empty launch returns 0 half way:
+// launch_gemm stops there too.)
+template <int EPI>
+static int prepare_gemm(GemmArgs& g, int mode) {
   VQ_REQUIRE(!g.f16x2 || g_matmul_dtype == 3, "conv_gemm: float32x2 launch outside matmul mode 3");
   if (mode == 3)
     for (int i = 0; i < g.nseg; ++i)
       VQ_REQUIRE(g.seg[i].wamax && (g.seg[i].amax || g.seg[i].amax_static > 0.f), "conv_gemm: float32x2 segment %d without its maxima", i);
-  const bool big = (g.M % 256 == 0) && (EPI != EPI_GATE_BWD);    // 256-row tiles (8 waves)
-  const int bm = big ? 256 : 128;
-  g.ntile_m = cdiv(g.M, bm);
+  const bool big = rows256<EPI>(g);
+  g.ntile_m = cdiv(g.M, big ? 256 : 128);
   g.ntile_n = cdiv(g.Tout, BN);
   for (int i = 0; i < g.nseg; ++i) g.seg[i].vec = seg_vec_ok(g.seg[i]) ? 1 : 0;
   if (EPI == EPI_LINEAR && g.out[1].y != nullptr)
@@ -866,83 +956,6 @@ int launch_gemm(GemmArgs& g, int tag, hipStream_t st) {
     const int sp = plan_ksplit(g.M, g.Tout, g.B, nk);
     if (sp > 1) { g.ksplit = sp; g.ksteps_per_split = cdiv(nk, sp); }
   }
-  const long grid = nblk * g.ksplit;
-  // timing (vqvae_prof_*): the GEMM kernel of this call is timed by its own dispatch's events (a split-K reduce behind it is not)
-  hipEvent_t pe0 = nullptr, pe1 = nullptr;
-  const bool attach = prof_enabled(tag);     // (the pair is registered in front of the launch itself: every check below may still return)
-  ProfScope ps(attach ? 0 : tag, st);
-#define LG_LAUNCH(KERNEL, GRID, BLOCK, ARG)                                                                    \
-  do {                                                                                                          \
-    if (attach && prof_attach(tag, &pe0, &pe1)) hipExtLaunchKernelGGL(KERNEL, GRID, BLOCK, 0, st, pe0, pe1, 0, ARG); \
-    else hipLaunchKernelGGL(KERNEL, GRID, BLOCK, 0, st, ARG);                                                   \
-  } while (0)
-  // the K = 128 -> 256-row projection with residual add (the ResidualBlock `res` conv): streaming kernel
-  if constexpr (EPI == EPI_LINEAR) {
-    static const int lin128 = getenv("VQVAE_LIN128") ? atoi(getenv("VQVAE_LIN128")) : 32;   // 0: off; 32 / 64: column tile
-    const Seg& s0 = g.seg[0];
-    // the 512-channel decoder's pre-split chain (K = 256 -> 512 rows): lin_stream_wide.hip's kernel, two row slices per column tile
-    if (lin128 && mode == 3 && lin_wide_shape(g)) return launch_lin_wide(g, attach ? tag : 0, st);
-    if (lin128 && mode != 0 && g.nseg == 1 && g.M == 256 && s0.cin == 128 && g.out[1].y == nullptr &&
-        !g.out[0].relu && !g.out[0].accumulate && !g.out[0].add_is_mask && s0.tmul == 1 && s0.tdiv == 1 && s0.toff == 0 && s0.Tin == g.Tout &&
-        s0.x_cstride == g.Tout && g.Tout % 64 == 0 && s0.vec && s0.ldw >= 256 && g.lerp.P == nullptr &&
-        g.skip_flag == nullptr && g.ksplit == 1) {
-      Lin128Args la;
-      la.w = reinterpret_cast<const uint4*>(s0.w); la.ldw = s0.ldw;
-      la.z = s0.x; la.z_bstride = s0.x_bstride;
-      la.add = g.out[0].add; la.add_bstride = g.out[0].add_bstride;
-      la.y = g.out[0].y; la.y_bstride = g.out[0].y_bstride;
-      la.bias = g.out[0].bias;
-      la.T = g.Tout;
-      la.wamax = s0.wamax; la.z_amax = s0.amax; la.z_amax_static = s0.amax_static; la.amax_out = g.out[0].amax_out;
-      la.add16 = g.add16; la.y16 = g.y16;
-      la.add_scale = g.add_scale; la.add_amax = g.add_amax; la.l1 = g.bound_l1; la.scale_out = g.scale_out;
-      la.floor_w = g.floor_w; la.floor_p = g.floor_p;
-      const int nc = (lin128 == 32 || g.z16) ? 32 : 64;
-      la.tiles_per_b = g.Tout / nc; la.ntiles = la.tiles_per_b * g.B;
-      static int n_cu = 0;
-      if (n_cu == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-      }
-      const unsigned nwg = (unsigned)(la.ntiles < n_cu ? la.ntiles : n_cu);
-#define L128_LAUNCH(NPv, NCv)                                                                                        \
-      do {                                                                                                           \
-        if (la.add) LG_LAUNCH((lin128_stream_kernel<NPv, NCv, true>), dim3(nwg), dim3(512), la);     \
-        else LG_LAUNCH((lin128_stream_kernel<NPv, NCv, false>), dim3(nwg), dim3(512), la);           \
-      } while (0)
-      if (mode == 2) { if (nc == 32) L128_LAUNCH(3, 32); else L128_LAUNCH(3, 64); }
-      else if (mode == 3 && (g.add16 || g.y16)) {
-        VQ_REQUIRE(la.add && g.y16 && g.add_amax && g.bound_l1 && g.scale_out && (!g.add16 || g.add_scale),
-                   "conv_gemm: a pre-split residual stream needs the residual add, a pre-split output and its bound's inputs");
-        if (g.add16) LG_LAUNCH((lin128_stream_kernel<2, 32, true, false, true, true>), dim3(nwg), dim3(512), la);
-        else LG_LAUNCH((lin128_stream_kernel<2, 32, true, false, false, true>), dim3(nwg), dim3(512), la);
-      }
-      else if (mode == 3) L128_LAUNCH(2, 32);
-      else if (g.add16 || g.y16) {
-        VQ_REQUIRE(g.z16 && la.add && g.y16, "conv_gemm: a bf16 residual stream needs matmul mode 1's bf16 z, the residual add and a bf16 output");
-        if (g.add16) LG_LAUNCH((lin128_stream_kernel<1, 32, true, true, true, true>), dim3(nwg), dim3(512), la);
-        else LG_LAUNCH((lin128_stream_kernel<1, 32, true, true, false, true>), dim3(nwg), dim3(512), la);
-      }
-      else if (g.z16) {
-        if (la.add) LG_LAUNCH((lin128_stream_kernel<1, 32, true, true>), dim3(nwg), dim3(512), la);
-        else LG_LAUNCH((lin128_stream_kernel<1, 32, false, true>), dim3(nwg), dim3(512), la);
-      }
-      else { if (nc == 32) L128_LAUNCH(1, 32); else L128_LAUNCH(1, 64); }
-#undef L128_LAUNCH
-      VQ_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  VQ_REQUIRE(mode == 3 || g_matmul_dtype != 3 || (!g.x16 && !g.h16 && !g.add16 && !g.y16), "conv_gemm: pre-split tensors need a float32x2 launch (every segment with its maxima)");
-  if (g.add16 || g.y16)
-    VQ_REQUIRE(EPI == EPI_LINEAR && mode == 1 && big && g.Tout % BN == 0 && g.M % 256 == 0 && g.out[1].y == nullptr && !g.out[0].bias &&
-               !g.out[0].relu && !g.out[0].accumulate && g.ksplit == 1,
-               "conv_gemm: a bf16 residual / gradient stream needs matmul mode 1, whole 256-row tiles and a plain (acc + add) epilogue");
-  // 256-column tiles when they still give every CU a workgroup (measured at configs[1]: dilated conv
-  // forward and backward-data -6.5 %, the short 1x1 contractions unchanged)
-  const long nblk2 = (long)g.ntile_m * cdiv(g.Tout, 2 * BN) * g.B;
-  // two taps of one tensor: interleave them channel group by channel group (TAP2).  The choice depends
-  // on the contraction only, never on the tile shape, so that a result does not change with the batch size.
   // A 1x1 conv over >= 64 channels into 256-row tiles (proj1 / proj2 and their backward-data, the latent-rate condition
   // projection): ONE segment, so it used to miss the two-tap loop and run 256 x 256 tiles, one workgroup per CU, 16 K steps
   // between a prologue and a 256 KB epilogue -- 16 GFLOP in 105 us, 0.18 of the three-product ceiling.  Its contraction is
@@ -950,6 +963,7 @@ int launch_gemm(GemmArgs& g, int tag, hipStream_t st) {
   // first one's upper K steps), which the TAP2 / LEAN loop interleaves like two taps: two workgroups per CU, one tile's
   // epilogue beside the other's loop.  Depends on the contraction only (never on B or T); the K order changes, the products do not.
   // (proj1 / proj2 forward and backward-data 105 -> ~70 us each, the step 14.87 -> 14.73 ms: same box, two interleaved rounds)
+  // (Never a launch the streaming 1x1 forms claim: lin_wide_shape needs y16, lin128_shape this very M and K.)
   if constexpr (EPI == EPI_LINEAR) {
     Seg& s0 = g.seg[0];
     if (big && (mode == 2 || mode == 3) && g.nseg == 1 && g.ksplit == 1 && s0.cin >= 64 && s0.cin % 32 == 0 &&
@@ -964,37 +978,57 @@ int launch_gemm(GemmArgs& g, int tag, hipStream_t st) {
       g.nseg = 2;
     }
   }
-  const bool tap2 = mode != 0 && g.nseg == 2 && g.ksplit == 1 &&
-                    g.seg[0].cin == g.seg[1].cin && g.seg[0].cin % BK == 0 &&
-                    g.seg[0].x_cstride == g.seg[1].x_cstride && g.seg[0].x_bstride == g.seg[1].x_bstride &&
-                    g.seg[0].Tin == g.seg[1].Tin && g.seg[0].tmul == g.seg[1].tmul && g.seg[0].tdiv == g.seg[1].tdiv &&
-                    g.seg[0].ldw == g.seg[1].ldw && g.seg[1].w >= g.seg[0].w &&          // second slab addressed off the first's descriptor
-                    (reinterpret_cast<const char*>(g.seg[1].w) - reinterpret_cast<const char*>(g.seg[0].w)) < (1L << 30);
-  // Two taps, two or more pieces per operand: 256 x 128 tiles whose loop fits 128 VGPRs (LEAN in conv_gemm_x3_kernel), TWO
-  // workgroups per CU -- one tile's epilogue beside the other's K loop: gate kernel 211 -> 197 us, backward-data
-  // 217 -> 198 us at configs[1] against the 256 x 256 tiles, which stay for every other contraction.  Same K
-  // order and products as the 256 x 256-tile two-tap kernel (VQVAE_X3_LEAN=0, the A/B alternate): the choice never changes a result.
-  static const int x3_lean = getenv("VQVAE_X3_LEAN") ? atoi(getenv("VQVAE_X3_LEAN")) : X3_LEAN;
-  const bool lean = x3_lean && X3_LEAN && tap2 && big && mode != 0 && EPI != EPI_GATE_BWD;   // mode 1: the 256 x 128 kernel needs 122 VGPRs as it is
-  const bool wide = mode != 0 && big && !lean && nblk2 >= 256;
+  const TileTraits t = tile_traits<EPI>(g, mode);
   if constexpr (EPI == EPI_GATE) {       // the latent-rate condition as one more K step: the 256 x 128-tile two-tap loop, modes 2 / 3 (see the kernel)
-    g.lerp.fold = (g.lerp.fold && g.lerp.P && lean && (mode == 2 || (mode == 3 && g.lerp.amax)) && g.Tout % BN == 0 &&
+    g.lerp.fold = (g.lerp.fold && g.lerp.P && t.lean && (mode == 2 || (mode == 3 && g.lerp.amax)) && g.Tout % BN == 0 &&
                    (long)g.Tout >= 26L * g.lerp.Tl) ? 1 : 0;
   }
-  if (wide) g.ntile_n = cdiv(g.Tout, 2 * BN);
-#define X3_LAUNCH(WMv, NBv, NPv, blocks, threads)                                                                    \
-  do {                                                                                                                \
-    if (tap2) LG_LAUNCH((conv_gemm_x3_kernel<EPI, WMv, NBv, NPv, true>), dim3((unsigned)(blocks)), dim3(threads), g);  \
-    else LG_LAUNCH((conv_gemm_x3_kernel<EPI, WMv, NBv, NPv, false>), dim3((unsigned)(blocks)), dim3(threads), g);      \
-  } while (0)
-#define X3_LAUNCH_MODE(WMv, NBv, blocks, threads)                                                                    \
-  do {                                                                                                                \
-    if (mode == 2) X3_LAUNCH(WMv, NBv, 3, blocks, threads);                                                           \
-    else if (mode == 3) X3_LAUNCH(WMv, NBv, 2, blocks, threads);                                                      \
-    else X3_LAUNCH(WMv, NBv, 1, blocks, threads);                                                                     \
-  } while (0)
-  // the gate-derivative epilogue always runs 128-row tiles (`big` is false): its 256-row variants are
-  // not instantiated
+  if (t.wide) g.ntile_n = cdiv(g.Tout, 2 * BN);
+  return 0;
+}
+
+// The kernel form of a launch.  GEMM_TILED: conv_gemm_x3_kernel<EPI, WM, NB, NP, TAP2, X16, OUT> on `grid` workgroups of
+// `threads`; GEMM_FP32: conv_gemm_kernel<EPI, WM> likewise; the streaming forms size their own grids from the CU count.
+enum GemmFamily { GEMM_LIN_WIDE, GEMM_LIN128, GEMM_GATE_STRIP, GEMM_TILED, GEMM_FP32 };
+struct GemmForm {
+  GemmFamily family;
+  int WM, NB, NP; bool TAP2; int X16, OUT;
+  unsigned grid, threads;
+};
+static GemmForm tiled_form(int wm, int nb, int np, bool tap2, int x16, int out, long grid) {
+  return GemmForm{GEMM_TILED, wm, nb, np, tap2, x16, out, (unsigned)grid, 128u * wm};
+}
+
+// Which form serves the prepared g in this mode: the forms in their order of precedence, each with the checks that it can
+// serve the storage flags the caller set.  No side effect but the error text, no HIP call.
+template <int EPI>
+static int select_gemm(const GemmArgs& g, int mode, GemmForm& f) {
+  f = GemmForm{};
+  // the K = 128 -> 256-row projection with residual add (the ResidualBlock `res` conv): streaming kernels
+  if constexpr (EPI == EPI_LINEAR) {
+    if (lin128_tile() != 0) {
+      // the 512-channel decoder's pre-split chain (K = 256 -> 512 rows): lin_stream_wide.hip's kernel, two row slices per column tile
+      if (mode == 3 && lin_wide_shape(g)) { f.family = GEMM_LIN_WIDE; return 0; }
+      if (lin128_shape(g, mode)) {
+        if (mode == 3 && (g.add16 || g.y16))
+          VQ_REQUIRE(g.out[0].add && g.y16 && g.add_amax && g.bound_l1 && g.scale_out && (!g.add16 || g.add_scale),
+                     "conv_gemm: a pre-split residual stream needs the residual add, a pre-split output and its bound's inputs");
+        if (mode == 1 && (g.add16 || g.y16))
+          VQ_REQUIRE(g.z16 && g.out[0].add && g.y16, "conv_gemm: a bf16 residual stream needs matmul mode 1's bf16 z, the residual add and a bf16 output");
+        f.family = GEMM_LIN128;
+        return 0;
+      }
+    }
+  }
+  const TileTraits t = tile_traits<EPI>(g, mode);
+  const bool big = t.big, tap2 = t.tap2, lean = t.lean, wide = t.wide;
+  VQ_REQUIRE(mode == 3 || g_matmul_dtype != 3 || (!g.x16 && !g.h16 && !g.add16 && !g.y16), "conv_gemm: pre-split tensors need a float32x2 launch (every segment with its maxima)");
+  if (g.add16 || g.y16)
+    VQ_REQUIRE(EPI == EPI_LINEAR && mode == 1 && big && g.Tout % BN == 0 && g.M % 256 == 0 && g.out[1].y == nullptr && !g.out[0].bias &&
+               !g.out[0].relu && !g.out[0].accumulate && g.ksplit == 1,
+               "conv_gemm: a bf16 residual / gradient stream needs matmul mode 1, whole 256-row tiles and a plain (acc + add) epilogue");
+  // workgroups: one per tile (prepare_gemm left 256-column tiles in ntile_n where they run) and split
+  const long grid = (long)g.ntile_m * g.ntile_n * g.B * g.ksplit;
   // activations stored as bf16 (matmul mode 1): a linear GEMM over z tensors (z16: every segment), or the caller's mask
   const int xm = (EPI == EPI_LINEAR && g.z16) ? 3 : g.x16;
   if (mode == 3 && (xm != 0 || g.h16 || (EPI == EPI_GATE_BWD && g.pb_part))) {       // float32x2 with pre-split tensors (see presplit_pair) / the fused pull-back
@@ -1002,11 +1036,11 @@ int launch_gemm(GemmArgs& g, int tag, hipStream_t st) {
     if constexpr (EPI == EPI_GATE) {
       VQ_REQUIRE(tap2 && lean && xm == 3 && g.seg[0].amax == g.seg[1].amax && g.seg[0].wamax == g.seg[1].wamax,
                  "conv_gemm: gate GEMM over a pre-split x: both taps of one tensor, 256 x 128 tiles");
-      LG_LAUNCH((conv_gemm_x3_kernel<EPI_GATE, 4, 1, 2, true, 3>), dim3((unsigned)nblk), dim3(512), g);
+      f = tiled_form(4, 1, 2, true, 3, 0, grid);
     } else if constexpr (EPI == EPI_LINEAR) {
       VQ_REQUIRE(tap2 && lean && xm == 3 && g.seg[0].amax == g.seg[1].amax && g.seg[0].wamax == g.seg[1].wamax && !g.add16 && !g.y16,
                  "conv_gemm: backward-data GEMM over a pre-split gh: both taps of one tensor, 256 x 128 tiles");
-      LG_LAUNCH((conv_gemm_x3_kernel<EPI_LINEAR, 4, 1, 2, true, 3>), dim3((unsigned)nblk), dim3(512), g);
+      f = tiled_form(4, 1, 2, true, 3, 0, grid);
     } else {
       VQ_REQUIRE(xm == 0 && (!g.h16 || (g.bound_l1 && g.scale_out)), "conv_gemm: gate-derivative GEMM storing a pre-split gh needs its bound's inputs (fp32 operands)");
       if (g.pb_part) VQ_REQUIRE(g.M == 128 && g.Tout % BN == 0 && g.lerp.v0 && g.lerp.w0 && g.lerp.w1 && (long)g.Tout >= 64L * g.lerp.Tl,
@@ -1014,16 +1048,9 @@ int launch_gemm(GemmArgs& g, int tag, hipStream_t st) {
       const int out = (g.h16 ? 1 : 0) | (g.pb_part ? 2 : 0);
       // ResidualNet's chain (pre-split gh + pull-back, g_res | g_skip): the column-strip streaming kernel, 16 waves per CU.
       // Same bits; every other launch (the stack's last block has no g_res, OUT = 1 / 2) stays on the tiles below
-      if (out == 3 && tap2 && gate_bwd_strip_shape(g)) return launch_gate_bwd_strip(g, attach ? tag : 0, st);
-#define GB_LAUNCH(OUTv)                                                                                                  \
-      do {                                                                                                                \
-        if (tap2) LG_LAUNCH((conv_gemm_x3_kernel<EPI_GATE_BWD, 2, 1, 2, true, 0, OUTv>), dim3((unsigned)grid), dim3(256), g); \
-        else LG_LAUNCH((conv_gemm_x3_kernel<EPI_GATE_BWD, 2, 1, 2, false, 0, OUTv>), dim3((unsigned)grid), dim3(256), g);  \
-      } while (0)
-      if (out == 1) GB_LAUNCH(1); else if (out == 2) GB_LAUNCH(2); else GB_LAUNCH(3);
-#undef GB_LAUNCH
+      if (out == 3 && tap2 && gate_bwd_strip_shape(g)) { f.family = GEMM_GATE_STRIP; return 0; }
+      f = tiled_form(2, 1, 2, tap2, 0, out, grid);        // conv_gemm_x3_kernel<EPI_GATE_BWD, 2, 1, 2, TAP2, 0, OUT>
     }
-    VQ_LAUNCH_CHECK();
     return 0;
   }
   if (xm != 0) {
@@ -1031,42 +1058,86 @@ int launch_gemm(GemmArgs& g, int tag, hipStream_t st) {
     for (int i = 0; i < g.nseg; ++i) VQ_REQUIRE(g.seg[i].tmul == 1 && g.seg[i].tdiv == 1, "conv_gemm: bf16-stored activations: stride-1 segments only");
     if constexpr (EPI == EPI_LINEAR) {
       VQ_REQUIRE(big && xm == 3, "conv_gemm: bf16-stored activations of a linear GEMM: every segment, 256-row tiles");
-      if (tap2 && lean) LG_LAUNCH((conv_gemm_x3_kernel<EPI_LINEAR, 4, 1, 1, true, 3>), dim3((unsigned)nblk), dim3(512), g);
-      else if (wide) LG_LAUNCH((conv_gemm_x3_kernel<EPI_LINEAR, 4, 2, 1, false, 1>), dim3((unsigned)nblk2), dim3(512), g);
-      else LG_LAUNCH((conv_gemm_x3_kernel<EPI_LINEAR, 4, 1, 1, false, 1>), dim3((unsigned)nblk), dim3(512), g);
+      if (tap2 && lean) f = tiled_form(4, 1, 1, true, 3, 0, grid);
+      else f = tiled_form(4, wide ? 2 : 1, 1, false, 1, 0, grid);
     } else if constexpr (EPI == EPI_GATE_BWD) {
       VQ_REQUIRE(tap2 && xm == 1, "conv_gemm: gate-derivative GEMM with a bf16-stored g_res: [g_res | g_skip] of one shape");
-      LG_LAUNCH((conv_gemm_x3_kernel<EPI_GATE_BWD, 2, 1, 1, true, 1>), dim3((unsigned)grid), dim3(256), g);
+      f = tiled_form(2, 1, 1, true, 1, 0, grid);
     } else if constexpr (EPI == EPI_GATE) {
       VQ_REQUIRE(tap2 && lean && xm == 3, "conv_gemm: gate GEMM over a bf16-stored x: both taps, 256 x 128 tiles");
-      LG_LAUNCH((conv_gemm_x3_kernel<EPI_GATE, 4, 1, 1, true, 3>), dim3((unsigned)nblk), dim3(512), g);
+      f = tiled_form(4, 1, 1, true, 3, 0, grid);
     } else {
       VQ_REQUIRE(false, "conv_gemm: bf16-stored activations are not built for this epilogue");
     }
-    VQ_LAUNCH_CHECK();
     return 0;
   }
-  if constexpr (EPI != EPI_GATE_BWD) {
-    if (big && mode != 0) {
-      if (wide) X3_LAUNCH_MODE(4, 2, nblk2, 512);
-      else X3_LAUNCH_MODE(4, 1, nblk, 512);
-    } else if (big) {
-      if (int e = launch_gemm_fp32<EPI>(g, 4, (unsigned)nblk, attach ? tag : 0, st)) return e;
-    }
-    if (!big) {
-      if (mode != 0) X3_LAUNCH_MODE(2, 1, grid, 256);
-      else if (int e = launch_gemm_fp32<EPI>(g, 2, (unsigned)grid, attach ? tag : 0, st)) return e;
+  // every other launch: 256-row tiles where M allows (the gate-derivative epilogue always runs 128-row tiles: its 256-row
+  // variants are not instantiated), the fp32 MFMA kernel in mode 0
+  f = tiled_form(big ? 4 : 2, wide ? 2 : 1, mode == 2 ? 3 : (mode == 3 ? 2 : 1), tap2, 0, 0, grid);
+  if (mode == 0) f.family = GEMM_FP32;
+  return 0;
+}
+
+// The instantiation a GEMM_TILED form names.  Only these exist: 256-column tiles for 256-row tiles, stored (X16) and
+// pre-split-output (OUT) variants for the shapes select_gemm sends to them.
+using GemmKernel = void (*)(GemmArgs);
+template <int EPI, int WM, int NB>
+static GemmKernel tiled_kernel_plain(const GemmForm& f) {
+  if (f.NP == 3) return f.TAP2 ? conv_gemm_x3_kernel<EPI, WM, NB, 3, true> : conv_gemm_x3_kernel<EPI, WM, NB, 3, false>;
+  if (f.NP == 2) return f.TAP2 ? conv_gemm_x3_kernel<EPI, WM, NB, 2, true> : conv_gemm_x3_kernel<EPI, WM, NB, 2, false>;
+  return f.TAP2 ? conv_gemm_x3_kernel<EPI, WM, NB, 1, true> : conv_gemm_x3_kernel<EPI, WM, NB, 1, false>;
+}
+// ... of the gate-derivative GEMM (128-row tiles only): OUTv != 0, float32x2: gh stored pre-split (bit 0) / the fused latent
+// pull-back (bit 1); OUTv == 0: a bf16-stored g_res (X16), or plain operands
+template <int OUTv>
+static GemmKernel gate_bwd_kernel(const GemmForm& f) {
+  if constexpr (OUTv != 0) {
+    return f.TAP2 ? conv_gemm_x3_kernel<EPI_GATE_BWD, 2, 1, 2, true, 0, OUTv> : conv_gemm_x3_kernel<EPI_GATE_BWD, 2, 1, 2, false, 0, OUTv>;
+  } else {
+    if (f.X16 != 0) return conv_gemm_x3_kernel<EPI_GATE_BWD, 2, 1, 1, true, 1>;
+    return tiled_kernel_plain<EPI_GATE_BWD, 2, 1>(f);
+  }
+}
+template <int EPI>
+static GemmKernel tiled_kernel(const GemmForm& f) {
+  if constexpr (EPI == EPI_GATE_BWD) {
+    switch (f.OUT) {
+      case 1: return gate_bwd_kernel<1>(f);
+      case 2: return gate_bwd_kernel<2>(f);
+      case 3: return gate_bwd_kernel<3>(f);
+      default: return gate_bwd_kernel<0>(f);
     }
   } else {
-    if (mode != 0) X3_LAUNCH_MODE(2, 1, grid, 256);
-    else if (int e = launch_gemm_fp32<EPI>(g, 2, (unsigned)grid, attach ? tag : 0, st)) return e;
+    if (f.X16 == 3) return f.NP == 2 ? conv_gemm_x3_kernel<EPI, 4, 1, 2, true, 3> : conv_gemm_x3_kernel<EPI, 4, 1, 1, true, 3>;
+    if constexpr (EPI == EPI_LINEAR) {
+      if (f.X16 == 1) return f.NB == 2 ? conv_gemm_x3_kernel<EPI_LINEAR, 4, 2, 1, false, 1> : conv_gemm_x3_kernel<EPI_LINEAR, 4, 1, 1, false, 1>;
+    }
+    if (f.WM == 4) return f.NB == 2 ? tiled_kernel_plain<EPI, 4, 2>(f) : tiled_kernel_plain<EPI, 4, 1>(f);
+    return tiled_kernel_plain<EPI, 2, 1>(f);
   }
-#undef X3_LAUNCH_MODE
-#undef X3_LAUNCH
-#undef LG_LAUNCH
+}
+
+template <int EPI>
+int launch_gemm(GemmArgs& g, int tag, hipStream_t st) {
+  // the arithmetic of THIS launch: mode 3 is float32x2 (NP = 2) where the caller provided maxima and a format-3 slab
+  // for every segment, mode 2's six-product kernels everywhere else
+  const int mode = g_matmul_dtype == 3 ? (g.f16x2 ? 3 : 2) : g_matmul_dtype;
+  if (int e = prepare_gemm<EPI>(g, mode)) return e;
+  if ((long)g.ntile_m * g.ntile_n * g.B <= 0) return 0;
+  GemmForm f;
+  if (int e = select_gemm<EPI>(g, mode, f)) return e;
+  // timing (vqvae_prof_*): the GEMM kernel of this call is timed by its own dispatch's events (a split-K reduce behind it is not)
+  ProfScope ps(prof_enabled(tag) ? 0 : tag, st);
+  switch (f.family) {
+    case GEMM_LIN_WIDE: return launch_lin_wide(g, tag, st);
+    case GEMM_LIN128: return launch_lin128(g, mode, tag, st);
+    case GEMM_GATE_STRIP: return launch_gate_bwd_strip(g, tag, st);
+    case GEMM_FP32: if (int e = launch_gemm_fp32<EPI>(g, f.WM, f.grid, tag, st)) return e; break;
+    case GEMM_TILED: launch_tagged(tiled_kernel<EPI>(f), dim3(f.grid), dim3(f.threads), st, tag, g); break;
+  }
   VQ_LAUNCH_CHECK();
   if (g.ksplit > 1) {
-    const long total = nblk * 128 * 128;
+    const long total = (long)g.ntile_m * g.ntile_n * g.B * 128 * 128;
     int nb = (int)((total + 255) / 256);
     if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(nb), dim3(256), 0, st, g);

@@ -295,9 +295,7 @@ bool gate_bwd_strip_shape(const GemmArgs& g) {
 
 int launch_gate_bwd_strip(const GemmArgs& g, int tag, hipStream_t st) {
   const unsigned grid = (unsigned)cdiv(g.ntile_n * g.B, 4);
-  hipEvent_t pe0 = nullptr, pe1 = nullptr;
-  if (tag != 0 && prof_attach(tag, &pe0, &pe1)) hipExtLaunchKernelGGL(gate_bwd_strip_kernel, dim3(grid), dim3(64 * GS_WAVES), 0, st, pe0, pe1, 0, g);
-  else hipLaunchKernelGGL(gate_bwd_strip_kernel, dim3(grid), dim3(64 * GS_WAVES), 0, st, g);
+  launch_tagged(gate_bwd_strip_kernel, dim3(grid), dim3(64 * GS_WAVES), st, tag, g);
   VQ_LAUNCH_CHECK();
   return 0;
 }

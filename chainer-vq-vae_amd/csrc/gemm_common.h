@@ -2,11 +2,12 @@
 // float32x2 scale bookkeeping, buffer / LDS-DMA plumbing, the cache-policy choices, the operand splits and the epilogues.
 // Kernel families (one translation unit each, so that they build in parallel):
 //   conv_gemm_x3.hip     conv_gemm_x3_kernel (modes 1-3: fwd and bwd-data of every conv, gate / gate-derivative GEMMs),
-//                        lin128_stream_kernel, the split-K reduce, launch_gemm
+//                        lin128_stream_kernel, the split-K reduce, launch_gemm (prepare_gemm -> select_gemm -> launch)
 //   conv_gemm_fp32.hip   conv_gemm_kernel (mode 0: v_mfma_f32_32x32x2_f32)
 //   gate_bwd_strip.hip   gate_bwd_strip_kernel (mode 3: the chain's gate-derivative GEMM with the fused pull-back, streaming)
 //   lin_stream_wide.hip  lin256_stream_kernel (mode 3: the residual 1x1 of the 512-channel decoder's pre-split chain, streaming)
-//   wgrad.hip            wgrad3_kernel / wgrad2_kernel / wgrad_kernel, their reduce, plan_wgrad, launch_wgrad
+//   wgrad.hip            wgrad3_kernel / wgrad2_kernel / wgrad_kernel, their reduce, plan_wgrad, launch_wgrad (prepare_wgrad ->
+//                        select_wgrad -> launch)
 //   conv_api.hip         weight packing, maxima and norms (pack / wamax / absmax / wl1 kernels) and the C ABI of the conv,
 //                        ResidualBlock and ResidualNet entry points
 #pragma once
@@ -1060,6 +1061,25 @@ static bool seg_vec_ok(const Seg& s) {
          (((uintptr_t)s.x) % 16 == 0);
 }
 
+// Launch kernel(arg); when profiling is on for `tag` (prof_attach; never for tag 0) the launch is timed by the events of its
+// own dispatch.
+template <typename Arg>
+static inline void launch_tagged(void (*kernel)(Arg), dim3 grid, dim3 block, hipStream_t st, int tag, const Arg& arg) {
+  hipEvent_t pe0 = nullptr, pe1 = nullptr;
+  if (prof_attach(tag, &pe0, &pe1)) hipExtLaunchKernelGGL(kernel, grid, block, 0, st, pe0, pe1, 0, arg);
+  else hipLaunchKernelGGL(kernel, grid, block, 0, st, arg);
+}
+
+// The descriptors' common case: a (B, C, T) tensor read at stride 1, t_in = t_out + toff (the fields set here and no others)
+static inline void seg_stride1(Seg& s, const float* x, int C, int T, int toff, const float* w, int ldw) {
+  s.x = x; s.x_bstride = (long)C * T; s.x_cstride = T; s.cin = C; s.Tin = T;
+  s.tmul = 1; s.toff = toff; s.tdiv = 1; s.w = w; s.ldw = ldw;
+}
+static inline void wseg_stride1(WSeg& s, const float* x, int C, int T, int toff) {
+  s.x = x; s.x_bstride = (long)C * T; s.x_cstride = T; s.cin = C; s.Tin = T;
+  s.tmul = 1; s.toff = toff; s.tdiv = 1;
+}
+
 struct WgradPlan { int ntile_m, ntile_n, steps_per_b, steps_per_split, nsplit, nseg; size_t slab_floats, bslab_floats; int wide; };
 // wide: the splits are chosen for wgrad3_dma_kernel (one 256 x 256-tile workgroup per CU) -- see wgrad_dma_shape
 
@@ -1068,15 +1088,20 @@ struct WgradPlan { int ntile_m, ntile_n, steps_per_b, steps_per_split, nsplit, n
 template <int EPI> int launch_gemm(GemmArgs& g, int tag, hipStream_t st);
 int plan_ksplit(int M, int Tout, int B, int nk);
 size_t ksplit_partial_floats(int M, int Tout, int B, int nk);
-// conv_gemm_fp32.hip: the mode-0 kernel of a launch_gemm<EPI> call (wm: 4 = 256-row tiles, 2 = 128-row); tag != 0: timed by
-// the dispatch's own events
+// ... and the two environment switches of launch_gemm's dispatch, each read once per process by its accessor:
+// conv_api.hip's storage predicates offer a caller only what select_gemm serves under them.  (Library-internal: not exported.)
+__attribute__((visibility("hidden"))) int lin128_tile();        // 0: the streaming residual 1x1 kernels are off; 32 (default) / 64: lin128_stream_kernel's column tile
+__attribute__((visibility("hidden"))) bool x3_lean_enabled();   // the 256 x 128-tile two-tap loop (default: the compile-time X3_LEAN, which also gates it)
+// The kernel forms select_gemm walks that live in other files: a pure predicate *_shape on the prepared block and a launch_*.
+// A tag that profiling is on for times the launch by its dispatch's own events (launch_tagged).
+// conv_gemm_fp32.hip: the mode-0 kernel (wm: 4 = 256-row tiles, 2 = 128-row)
 template <int EPI> int launch_gemm_fp32(const GemmArgs& g, int wm, unsigned grid, int tag, hipStream_t st);
 // gate_bwd_strip.hip: the column-strip streaming form of the float32x2 gate-derivative GEMM with the fused pull-back (same
-// bits as conv_gemm_x3_kernel's); launch_gemm<EPI_GATE_BWD> asks _shape first.  tag != 0: timed by the dispatch's own events
+// bits as conv_gemm_x3_kernel's); select_gemm<EPI_GATE_BWD> asks _shape before the tiled form
 bool gate_bwd_strip_shape(const GemmArgs& g);
 int launch_gate_bwd_strip(const GemmArgs& g, int tag, hipStream_t st);
 // lin_stream_wide.hip: the streaming residual 1x1 of the 512-channel decoder's pre-split chain (256 -> 512 rows, x_{l+1} stored
-// pre-split); launch_gemm<EPI_LINEAR> asks _shape first.  tag != 0: timed by the dispatch's own events
+// pre-split); select_gemm<EPI_LINEAR> asks _shape first
 bool lin_wide_shape(const GemmArgs& g);
 int launch_lin_wide(const GemmArgs& g, int tag, hipStream_t st);
 // wgrad.hip

@@ -224,15 +224,7 @@ int launch_lin_wide(const GemmArgs& g, int tag, hipStream_t st) {
   int pairs = n_cu / 2 < la.ntiles ? n_cu / 2 : la.ntiles;
   pairs = (pairs + 7) / 8 * 8;
   const dim3 grid((unsigned)(2 * pairs)), block(512);
-  hipEvent_t pe0 = nullptr, pe1 = nullptr;
-  const bool attach = tag != 0 && prof_attach(tag, &pe0, &pe1);
-  if (g.add16) {
-    if (attach) hipExtLaunchKernelGGL(lin256_stream_kernel<true>, grid, block, 0, st, pe0, pe1, 0, la);
-    else hipLaunchKernelGGL(lin256_stream_kernel<true>, grid, block, 0, st, la);
-  } else {
-    if (attach) hipExtLaunchKernelGGL(lin256_stream_kernel<false>, grid, block, 0, st, pe0, pe1, 0, la);
-    else hipLaunchKernelGGL(lin256_stream_kernel<false>, grid, block, 0, st, la);
-  }
+  launch_tagged(g.add16 ? lin256_stream_kernel<true> : lin256_stream_kernel<false>, grid, block, st, tag, la);
   VQ_LAUNCH_CHECK();
   return 0;
 }

@@ -1255,7 +1255,11 @@ WgradPlan plan_wgrad(int M, int B, int Tout, const int* cins, int nseg, bool wid
   return p;
 }
 
-int launch_wgrad(WgradArgs& w, const WgradPlan& p, float* ws, int tag, hipStream_t st) {
+// ---------------------------------------------------------------------------
+// launch_wgrad: prepare_wgrad fills the fields of w the kernels read and says whether the 16-byte-LDS kernels can run
+// (`fast`), select_wgrad names the kernel form, launch_wgrad launches it and the reduce.
+// ---------------------------------------------------------------------------
+static int prepare_wgrad(WgradArgs& w, const WgradPlan& p, float* ws, bool& fast) {
   w.ntile_m = p.ntile_m; w.ntile_n = p.ntile_n;
   w.steps_per_b = p.steps_per_b; w.steps_per_split = p.steps_per_split; w.nsplit = p.nsplit;
   w.slabs = ws;
@@ -1285,60 +1289,99 @@ int launch_wgrad(WgradArgs& w, const WgradPlan& p, float* ws, int tag, hipStream
     sg.vec = (sg.tmul == 1 && sg.tdiv == 1 && w.Tout % 4 == 0) ? 1 : 0;
   }
   // fp32, stride-1 segments, 16-B aligned output-gradient rows: the 16-byte-LDS kernel
-  bool fast = av && g_wgrad_impl != 1;
+  fast = av && g_wgrad_impl != 1;
   for (int i = 0; i < w.nseg; ++i) fast = fast && w.seg[i].tmul == 1 && w.seg[i].tdiv == 1;
   // wgrad3_kernel addresses both operands with 32-bit buffer offsets from the tensor base
   fast = fast && (g_matmul_dtype == 0 || (long)w.B * w.gy_bstride * 4 < (1L << 31));
   for (int i = 0; i < w.nseg; ++i) fast = fast && (g_matmul_dtype == 0 || (long)w.B * w.seg[i].x_bstride * 4 < (1L << 31));
-  // the arithmetic of this launch (see launch_gemm): float32x2 when the caller gave every segment its maxima and the
-  // shape runs on wgrad3_kernel; both operands are activations, so falling back to mode 2 needs nothing re-packed
   VQ_REQUIRE(!w.f16x2 || g_matmul_dtype == 3, "wgrad: float32x2 launch outside matmul mode 3");
   if (w.f16x2)
     for (int i = 0; i < w.nseg; ++i)
       VQ_REQUIRE((w.seg[i].amax_x || w.seg[i].amax_x_static > 0.f) && (w.seg[i].gy ? w.seg[i].amax_gy != nullptr : w.amax_gy != nullptr),
                  "wgrad: float32x2 segment %d without its maxima", i);
+  return 0;
+}
+
+// The kernel form of a launch.  WG_W3: wgrad3_kernel<WM, 1, NP, X16, G16>; WG_DMA: wgrad3_dma_kernel<NP == 1> (both operands
+// stored as bf16 / pre-split, through LDS-DMA); WG_W2: wgrad2_kernel<WM> (mode 0); WG_GENERIC: wgrad_kernel<NP == 1>.
+// NP: pieces per operand as in conv_gemm_x3_kernel (0: fp32 operands).
+enum WgradFamily { WG_W3, WG_DMA, WG_W2, WG_GENERIC };
+struct WgradForm {
+  WgradFamily family;
+  int WM, NP; bool X16, G16;
+  dim3 grid; unsigned threads;
+};
+
+// Which form serves the prepared w under plan p, in the forms' order of precedence.  No side effect but the error text.
+static int select_wgrad(const WgradArgs& w, const WgradPlan& p, bool fast, WgradForm& f) {
+  // the arithmetic of this launch (see launch_gemm): float32x2 when the caller gave every segment its maxima and the
+  // shape runs on wgrad3_kernel; both operands are activations, so falling back to mode 2 needs nothing re-packed
   const int mode = g_matmul_dtype == 3 ? ((w.f16x2 && fast) ? 3 : 2) : g_matmul_dtype;
-  ProfScope ps(tag, st);
+  const bool big = w.M % 256 == 0;
+  bool dma_shape = false;         // both operands stored: does the shape run on wgrad3_dma_kernel? (with any plan; the caller asks for a wide one when it knows)
+  if (w.x16 && w.g16) {
+    int cins[MAXSEG];
+    for (int i = 0; i < w.nseg; ++i) cins[i] = w.seg[i].cin;
+    dma_shape = wgrad_dma_shape(w.M, w.Tout, cins, w.nseg);
+  }
+  f = WgradForm{WG_W3, big ? 4 : 2, 0, false, false, dim3(), 0};
   if (g_matmul_dtype == 3 && (w.x16 || w.g16)) {        // pre-split operands (see presplit_pair): their `amax` words are scale words
-    VQ_REQUIRE(fast && mode == 3 && w.M % 256 == 0, "wgrad: pre-split operands need a float32x2 launch on 256-row tiles");
-    const dim3 grid((p.ntile_m / 2) * p.ntile_n * p.nsplit);
-    int cins_[MAXSEG];
-    for (int i = 0; i < w.nseg; ++i) cins_[i] = w.seg[i].cin;
-    const bool dma = w.x16 && w.g16 && wgrad_dma_shape(w.M, w.Tout, cins_, w.nseg);     // (with any plan; the caller asks for a wide one when it knows)
-    if (dma) hipLaunchKernelGGL(wgrad3_dma_kernel<false>, dim3((p.ntile_m / 2) * w.ntile_p * p.nsplit), dim3(1024), 0, st, w);
-    else if (w.x16 && w.g16) hipLaunchKernelGGL((wgrad3_kernel<4, 1, 2, true, true>), grid, dim3(512), 0, st, w);
-    else if (w.g16) hipLaunchKernelGGL((wgrad3_kernel<4, 1, 2, false, true>), grid, dim3(512), 0, st, w);
-    else hipLaunchKernelGGL((wgrad3_kernel<4, 1, 2, true, false>), grid, dim3(512), 0, st, w);
-  } else if (fast && mode == 3 && w.M % 256 == 0) {
-    hipLaunchKernelGGL((wgrad3_kernel<4, 1, 2>), dim3((p.ntile_m / 2) * p.ntile_n * p.nsplit), dim3(512), 0, st, w);
+    VQ_REQUIRE(fast && mode == 3 && big, "wgrad: pre-split operands need a float32x2 launch on 256-row tiles");
+    f.NP = 2; f.X16 = w.x16 != 0; f.G16 = w.g16 != 0;
+    if (dma_shape) f.family = WG_DMA;
   } else if (fast && mode == 3) {
-    hipLaunchKernelGGL((wgrad3_kernel<2, 1, 2>), dim3(p.ntile_m * p.ntile_n * p.nsplit), dim3(256), 0, st, w);
-  } else if (fast && mode == 2 && w.M % 256 == 0) {
-    hipLaunchKernelGGL((wgrad3_kernel<4, 1, 3>), dim3((p.ntile_m / 2) * p.ntile_n * p.nsplit), dim3(512), 0, st, w);
+    f.NP = 2;
   } else if (fast && mode == 2) {
-    hipLaunchKernelGGL((wgrad3_kernel<2, 1, 3>), dim3(p.ntile_m * p.ntile_n * p.nsplit), dim3(256), 0, st, w);
+    f.NP = 3;
   } else if (w.x16 || w.g16) {
-    bool ok16 = fast && mode == 1 && w.M % 256 == 0 && w.Tout % W2K == 0;
+    bool ok16 = fast && mode == 1 && big && w.Tout % W2K == 0;
     if (w.x16) for (int i = 0; i < w.nseg; ++i) ok16 = ok16 && w.seg[i].Tin == w.Tout;
     VQ_REQUIRE(ok16, "wgrad: bf16-stored operands need matmul mode 1, stride-1 segments, 256-row tiles and T %% 16 == 0");
-    const dim3 grid((p.ntile_m / 2) * p.ntile_n * p.nsplit);
-    int cins_[MAXSEG];
-    for (int i = 0; i < w.nseg; ++i) cins_[i] = w.seg[i].cin;
-    if (w.x16 && w.g16 && wgrad_dma_shape(w.M, w.Tout, cins_, w.nseg) && w.Tout % 64 == 0 && p.steps_per_b % 2 == 0 && p.steps_per_split % 2 == 0)
-      hipLaunchKernelGGL(wgrad3_dma_kernel<true>, dim3((p.ntile_m / 2) * w.ntile_p * p.nsplit), dim3(1024), 0, st, w);
-    else if (w.x16 && w.g16) hipLaunchKernelGGL((wgrad3_kernel<4, 1, 1, true, true>), grid, dim3(512), 0, st, w);
-    else if (w.g16) hipLaunchKernelGGL((wgrad3_kernel<4, 1, 1, false, true>), grid, dim3(512), 0, st, w);
-    else hipLaunchKernelGGL((wgrad3_kernel<4, 1, 1, true>), grid, dim3(512), 0, st, w);
-  } else if (fast && mode == 1 && w.M % 256 == 0) {
-    hipLaunchKernelGGL((wgrad3_kernel<4, 1, 1>), dim3((p.ntile_m / 2) * p.ntile_n * p.nsplit), dim3(512), 0, st, w);
+    f.NP = 1; f.X16 = w.x16 != 0; f.G16 = w.g16 != 0;
+    // (wgrad3_dma_kernel<BF> takes two plan steps, 64 positions, at a time)
+    if (dma_shape && w.Tout % 64 == 0 && p.steps_per_b % 2 == 0 && p.steps_per_split % 2 == 0) f.family = WG_DMA;
   } else if (fast && mode == 1) {
-    hipLaunchKernelGGL((wgrad3_kernel<2, 1, 1>), dim3(p.ntile_m * p.ntile_n * p.nsplit), dim3(256), 0, st, w);
-  } else if (fast && w.M % 256 == 0) {
-    hipLaunchKernelGGL(wgrad2_kernel<4>, dim3((p.ntile_m / 2) * p.ntile_n * p.nsplit), dim3(512), 0, st, w);
+    f.NP = 1;
   } else if (fast) {
-    hipLaunchKernelGGL(wgrad2_kernel<2>, dim3(p.ntile_m * p.ntile_n * p.nsplit), dim3(256), 0, st, w);
-  } else if (mode == 1) hipLaunchKernelGGL(wgrad_kernel<true>, dim3(p.ntile_m * p.ntile_n, p.nsplit), dim3(NT), 0, st, w);
-  else hipLaunchKernelGGL(wgrad_kernel<false>, dim3(p.ntile_m * p.ntile_n, p.nsplit), dim3(NT), 0, st, w);
+    f.family = WG_W2;
+  } else {
+    f.family = WG_GENERIC; f.NP = mode == 1 ? 1 : 0;
+  }
+  // workgroups: the plan's 128 x 128 tiles (256-row kernels take two tile rows each) times its splits
+  if (f.family == WG_GENERIC) { f.grid = dim3(p.ntile_m * p.ntile_n, p.nsplit); f.threads = NT; }
+  else if (f.family == WG_DMA) { f.grid = dim3((p.ntile_m / 2) * w.ntile_p * p.nsplit); f.threads = 1024; }
+  else { f.grid = dim3((big ? p.ntile_m / 2 : p.ntile_m) * p.ntile_n * p.nsplit); f.threads = 128 * f.WM; }
+  return 0;
+}
+
+// The instantiation a form names.  Only these exist: stored operands (X16 / G16) on 256-row tiles, in modes 1 and 3.
+using WgradKernelFn = void (*)(WgradArgs);
+static WgradKernelFn wgrad_form_kernel(const WgradForm& f) {
+  const bool both = f.X16 && f.G16;
+  if (f.family == WG_DMA && f.NP == 2) return wgrad3_dma_kernel<false>;
+  if (f.family == WG_W3 && f.NP == 2) {
+    if (both) return wgrad3_kernel<4, 1, 2, true, true>;
+    if (f.X16 || f.G16) return f.G16 ? wgrad3_kernel<4, 1, 2, false, true> : wgrad3_kernel<4, 1, 2, true, false>;
+    return f.WM == 4 ? wgrad3_kernel<4, 1, 2> : wgrad3_kernel<2, 1, 2>;
+  }
+  if (f.family == WG_W3 && f.NP == 3) return f.WM == 4 ? wgrad3_kernel<4, 1, 3> : wgrad3_kernel<2, 1, 3>;
+  if (f.family == WG_DMA) return wgrad3_dma_kernel<true>;
+  if (f.family == WG_W3) {
+    if (both) return wgrad3_kernel<4, 1, 1, true, true>;
+    if (f.X16 || f.G16) return f.G16 ? wgrad3_kernel<4, 1, 1, false, true> : wgrad3_kernel<4, 1, 1, true>;
+    return f.WM == 4 ? wgrad3_kernel<4, 1, 1> : wgrad3_kernel<2, 1, 1>;
+  }
+  if (f.family == WG_W2) return f.WM == 4 ? wgrad2_kernel<4> : wgrad2_kernel<2>;
+  return f.NP == 1 ? wgrad_kernel<true> : wgrad_kernel<false>;
+}
+
+int launch_wgrad(WgradArgs& w, const WgradPlan& p, float* ws, int tag, hipStream_t st) {
+  bool fast = false;
+  if (int e = prepare_wgrad(w, p, ws, fast)) return e;
+  ProfScope ps(tag, st);
+  WgradForm f;
+  if (int e = select_wgrad(w, p, fast, f)) return e;
+  hipLaunchKernelGGL(wgrad_form_kernel(f), f.grid, dim3(f.threads), 0, st, w);
   VQ_LAUNCH_CHECK();
   const long total = (long)p.ntile_m * BM * p.ntile_n * BN + (long)p.nseg * p.ntile_m * BM;
   int nb = (int)((total + 63) / 64);

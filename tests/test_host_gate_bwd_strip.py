@@ -76,4 +76,8 @@ def test_launch_gemm_asks_the_strip_kernel_first():
     src = open(os.path.join(CSRC, 'conv_gemm_x3.hip')).read()
     i, j = src.index('gate_bwd_strip_shape(g)'), src.index('conv_gemm_x3_kernel<EPI_GATE_BWD, 2, 1, 2, true, 0, OUTv>')
     assert i < j
+    # ... inside select_gemm's ordered list of forms: the strip form is asked before the tiled OUT form is named
+    select = src[src.index('static int select_gemm('):src.index('using GemmKernel')]
+    assert select.index('gate_bwd_strip_shape(g)') < select.index('f = tiled_form(2, 1, 2, tap2, 0, out, grid)')
+    assert 'case GEMM_GATE_STRIP: return launch_gate_bwd_strip(g, tag, st);' in src
     assert 'gate_bwd_strip.hip' in open(os.path.join(CSRC, 'Makefile')).read()
