@@ -4,6 +4,7 @@ hand-written HIP (gfx950) in libvqvae_hip.so reached through a C ABI."""
 from . import _lib, backend, core, functions, links, optimizers, reporting  # noqa: F401
 from .core import (Chain, ChainList, FunctionNode, Link, Parameter, Variable,  # noqa: F401
                    config, report, using_config)
+from .codebook import CodebookMonitor  # noqa: F401
 from .net import VAE, ConditionEmbed, Encoder  # noqa: F401
 from .updaters import (VQVAE_ParallelUpdater, VQVAE_StandardUpdater,  # noqa: F401
                        concat_examples)

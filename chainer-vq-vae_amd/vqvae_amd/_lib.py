@@ -219,6 +219,16 @@ PROTOTYPES = {
     'vqvae_graph_destroy': (c_int, [P]),
 }
 
+# include/vqvae_codebook.h: codebook statistics and re-seeding, a table (and a version) of its own beside the ABI above
+CODEBOOK_PROTOTYPES = {
+    'vqvae_codebook_abi_version': (c_int, []),
+    'vqvae_codebook_observe': (c_int, [P, P, c_int, c_int, c_int, c_int, c_float, C.c_uint64, P, P, P, P, P, P]),
+    'vqvae_codebook_reseed': (c_int, [P, P, P, c_int, c_int, P, P, c_float, c_float, P, P, P]),
+}
+CODEBOOK_ABI_VERSION = 1          # vqvae_codebook_abi_version()
+CODEBOOK_STATS_WORDS = 8          # VQVAE_CODEBOOK_STATS_WORDS
+CODEBOOK_LDS_MAX_K = 16384        # VQVAE_CODEBOOK_LDS_MAX_K
+
 # elementwise op codes / profiler tags (mirror the header)
 MAX_STACK_GROUP = 24              # blocks per resstack call (MAXSEG in csrc/gemm_common.h)
 STORE_X_BF16, STORE_RES_BF16 = 2, 4
@@ -261,13 +271,17 @@ def load():
     # Must be in the environment before the HSA runtime initialises (first HIP call).
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(lib, name)           # AttributeError if the symbol is missing
-        fn.restype = res
-        fn.argtypes = args
+    for table in (PROTOTYPES, CODEBOOK_PROTOTYPES):
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)           # AttributeError if the symbol is missing
+            fn.restype = res
+            fn.argtypes = args
     if lib.vqvae_abi_version() != ABI_VERSION:    # the ctypes structs below mirror ONE layout of include/vqvae_hip.h
         raise ImportError('libvqvae_hip.so at %s has ABI %d, this package binds ABI %d: rebuild it (__graft_entry__.build())'
                           % (LIB_PATH, lib.vqvae_abi_version(), ABI_VERSION))
+    if lib.vqvae_codebook_abi_version() != CODEBOOK_ABI_VERSION:
+        raise ImportError('libvqvae_hip.so at %s has codebook ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
+                          % (LIB_PATH, lib.vqvae_codebook_abi_version(), CODEBOOK_ABI_VERSION))
     _lib = lib
     return lib
 

@@ -111,8 +111,9 @@ def report_scope(observation):
 # adopted yet.  'load' advances when a serializer overwrites parameter values, so value-keyed
 # caches (VQ search reuse, packed generation weights) drop what they hold.  'layout' advances
 # when an optimizer moves parameters into (new) arenas: raw device pointers captured before
-# that (GenerationState) are stale.
-_epochs = {'init': 0, 'load': 0, 'layout': 0}
+# that (GenerationState) are stale.  'monitor' advances when a codebook monitor is attached to or
+# detached from a VQ link: a recorded step holds (or lacks) that monitor's launches.
+_epochs = {'init': 0, 'load': 0, 'layout': 0, 'monitor': 0}
 
 
 def param_epoch(kind):

@@ -10,13 +10,15 @@ DictionarySerializer strips the leading '/' of namedparams paths]:
     updater/optimizer:main/<link path>/<param>/{m,v,t}  Adam state per parameter
     updater/optimizer:main/{t,epoch}                  optimizer counters
     updater/iteration                                 updater counter
+    updater/codebook:main/<vq link path>/{usage,steps_seen,seed,decay}
+                                                      codebook.CodebookMonitor state, ONLY when one is attached
 
 Parameter shapes equal Chainer's ((Cout,Cin,K,1) convs, (n,G) EmbedID, (k,d) VQ), so
 a snapshot written here loads in the reference's generate.py and vice versa.
 """
 import numpy as np
 
-from . import core
+from . import codebook, core
 from .backend import DeviceArray
 from .core import Link
 
@@ -57,6 +59,9 @@ def save_npz(file, obj, compression=True):
         state.update(model_state(opt.target))
         state.update(optimizer_state(opt))
         state['updater/iteration'] = np.asarray(getattr(obj, 'iteration', 0), np.int32)
+        for path, mon in codebook.attached_monitors(opt.target):
+            for key, value in mon.state().items():
+                state[codebook.SNAPSHOT_PREFIX + (path + '/' if path else '') + key] = value
     (np.savez_compressed if compression else np.savez)(file, **state)
 
 
@@ -82,6 +87,9 @@ def load_npz(file, obj, path='', strict=True):
             opt.t = int(f[OPT_PREFIX + 't'])
         if 'updater/iteration' in f:
             obj.iteration = int(f['updater/iteration'])
+        for path, mon in codebook.attached_monitors(opt.target):
+            key = codebook.SNAPSHOT_PREFIX + (path + '/' if path else '')
+            mon.load_state({k: f[key + k] for k in ('usage', 'steps_seen', 'seed', 'decay') if key + k in f})
 
 
 def _load_link(f, link, prefix, strict):

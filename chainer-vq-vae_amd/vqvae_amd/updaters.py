@@ -100,8 +100,8 @@ class StandardUpdater(object):
     def _step_key(self, in_arrays, optimizer):
         from . import _lib
         sig = tuple((type(a).__name__, tuple(a.shape), str(a.dtype)) for a in in_arrays)
-        return (sig, core.param_epoch('layout'), core.param_epoch('init'), _lib.load().vqvae_get_matmul_dtype(),
-                backend.overlap_enabled(), id(optimizer),
+        return (sig, core.param_epoch('layout'), core.param_epoch('init'), core.param_epoch('monitor'),
+                _lib.load().vqvae_get_matmul_dtype(), backend.overlap_enabled(), id(optimizer),
                 optimizer.capture_key() if hasattr(optimizer, 'capture_key') else None)
 
     def _run_step(self, in_arrays, body):

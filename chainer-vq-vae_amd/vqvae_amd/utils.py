@@ -163,7 +163,8 @@ def straight_through(x, W):
 
 
 class VQ(Link):
-    """utils.py:239-255."""
+    """utils.py:239-255.  ``vq.monitor = CodebookMonitor(vq)`` (codebook.py) opts into usage statistics: in train
+    mode every application that ran the nearest-code search hands its latents and indices to the monitor."""
 
     def __init__(self, k, d=None, initialW=None):
         super(VQ, self).__init__()
@@ -193,9 +194,22 @@ class VQ(Link):
         if preset is None and isinstance(x.data, DeviceArray):
             self._cache = (weakref.ref(key[0]), weakref.ref(key[1]), self._w_version(),
                            (node.indexes, y.data))
+            if self._monitor is not None and core.config.train:     # once per step: the second application is a preset
+                self._monitor.observe(x.data, node.indexes)
         return y
 
     _cache = None
+    _monitor = None
+
+    @property
+    def monitor(self):
+        return self._monitor
+
+    @monitor.setter
+    def monitor(self, mon):
+        if mon is not self._monitor:
+            self._monitor = mon
+            core.bump_param_epoch('monitor')      # a recorded step was captured with (or without) the old one
 
     def _w_version(self):
         opt = getattr(self.W, '_owner_step', None)
