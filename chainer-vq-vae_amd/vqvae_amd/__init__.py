@@ -5,6 +5,7 @@ from . import _lib, backend, core, functions, links, optimizers, reporting  # no
 from .core import (Chain, ChainList, FunctionNode, Link, Parameter, Variable,  # noqa: F401
                    config, report, using_config)
 from .codebook import CodebookMonitor  # noqa: F401
+from .codebook_ema import EMACodebook  # noqa: F401
 from .net import VAE, ConditionEmbed, Encoder  # noqa: F401
 from .updaters import (VQVAE_ParallelUpdater, VQVAE_StandardUpdater,  # noqa: F401
                        concat_examples)

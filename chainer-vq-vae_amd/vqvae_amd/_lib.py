@@ -229,6 +229,19 @@ CODEBOOK_ABI_VERSION = 1          # vqvae_codebook_abi_version()
 CODEBOOK_STATS_WORDS = 8          # VQVAE_CODEBOOK_STATS_WORDS
 CODEBOOK_LDS_MAX_K = 16384        # VQVAE_CODEBOOK_LDS_MAX_K
 
+# include/vqvae_vq_ema.h: EMA codebook updates, again a table and a version of their own
+VQ_EMA_PROTOTYPES = {
+    'vqvae_vq_ema_abi_version': (c_int, []),
+    'vqvae_vq_ema_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'vqvae_vq_ema_accumulate': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
+    'vqvae_vq_ema_apply': (c_int, [P, P, P, P, c_int, c_int, c_float, c_float, P]),
+    'vqvae_vq_ema_reset': (c_int, [P, P, P, c_int, c_int, P, P]),
+}
+VQ_EMA_ABI_VERSION = 1            # vqvae_vq_ema_abi_version()
+VQ_EMA_PIECE = 512                # VQVAE_VQ_EMA_PIECE
+VQ_EMA_SMALL_MAX_N = 4096         # VQVAE_VQ_EMA_SMALL_MAX_N
+VQ_EMA_MAX_N = 1 << 24            # VQVAE_VQ_EMA_MAX_N
+
 # elementwise op codes / profiler tags (mirror the header)
 MAX_STACK_GROUP = 24              # blocks per resstack call (MAXSEG in csrc/gemm_common.h)
 STORE_X_BF16, STORE_RES_BF16 = 2, 4
@@ -271,7 +284,7 @@ def load():
     # Must be in the environment before the HSA runtime initialises (first HIP call).
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     lib = C.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, CODEBOOK_PROTOTYPES):
+    for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)           # AttributeError if the symbol is missing
             fn.restype = res
@@ -282,6 +295,9 @@ def load():
     if lib.vqvae_codebook_abi_version() != CODEBOOK_ABI_VERSION:
         raise ImportError('libvqvae_hip.so at %s has codebook ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
                           % (LIB_PATH, lib.vqvae_codebook_abi_version(), CODEBOOK_ABI_VERSION))
+    if lib.vqvae_vq_ema_abi_version() != VQ_EMA_ABI_VERSION:
+        raise ImportError('libvqvae_hip.so at %s has EMA-codebook ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
+                          % (LIB_PATH, lib.vqvae_vq_ema_abi_version(), VQ_EMA_ABI_VERSION))
     _lib = lib
     return lib
 

@@ -146,7 +146,8 @@ class CodebookMonitor(object):
     def reseed(self, optimizer=None, threshold=1e-3, revived_usage=None, comm=None):
         """Replaces every code whose running usage is below ``threshold`` by its reservoir row (a latent the encoder
         produced at the last step), zeroes the Adam moments of the replaced rows (stale moments would drag the fresh vector
-        back towards the dead one) and sets their usage to ``revived_usage`` (default: ``threshold``, so a revived code is
+        back towards the dead one; with an EMACodebook on the link, its state of those rows restarts at N = 1, m = W for
+        the same reason) and sets their usage to ``revived_usage`` (default: ``threshold``, so a revived code is
         not replaced again before it had a chance).  Returns the number of codes replaced.
 
         With a communicator of more than one rank the decision is taken on the usage summed over ranks, and code j takes
@@ -182,6 +183,9 @@ class CodebookMonitor(object):
         _lib.call('vqvae_codebook_reseed', W.ptr, None if m is None else m.ptr, None if v is None else v.ptr, self.k, self.d,
                   self.usage_dev.ptr, reservoir.ptr, float(threshold), revived, n.ptr, mask.ptr, backend.stream())
         core.bump_param_epoch('load')        # value-keyed caches (VQ search reuse, generation state) are stale; W did not move
+        ema = getattr(self.vq, 'codebook_ema', None)
+        if ema is not None:
+            ema.reset(mask=mask)             # replaced rows restart at N = 1, m = W (else the next step pulls them back)
         self.threshold = float(threshold)
         self.last_mask = mask.get()
         return int(n.get()[0])

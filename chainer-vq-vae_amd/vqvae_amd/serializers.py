@@ -12,13 +12,15 @@ DictionarySerializer strips the leading '/' of namedparams paths]:
     updater/iteration                                 updater counter
     updater/codebook:main/<vq link path>/{usage,steps_seen,seed,decay}
                                                       codebook.CodebookMonitor state, ONLY when one is attached
+    updater/codebook_ema:main/<vq link path>/{decay,eps,count,sum}
+                                                      codebook_ema.EMACodebook state, ONLY when one is attached
 
 Parameter shapes equal Chainer's ((Cout,Cin,K,1) convs, (n,G) EmbedID, (k,d) VQ), so
 a snapshot written here loads in the reference's generate.py and vice versa.
 """
 import numpy as np
 
-from . import codebook, core
+from . import codebook, codebook_ema, core
 from .backend import DeviceArray
 from .core import Link
 
@@ -62,6 +64,9 @@ def save_npz(file, obj, compression=True):
         for path, mon in codebook.attached_monitors(opt.target):
             for key, value in mon.state().items():
                 state[codebook.SNAPSHOT_PREFIX + (path + '/' if path else '') + key] = value
+        for path, ema in codebook_ema.attached_emas(opt.target):
+            for key, value in ema.state().items():
+                state[codebook_ema.SNAPSHOT_PREFIX + (path + '/' if path else '') + key] = value
     (np.savez_compressed if compression else np.savez)(file, **state)
 
 
@@ -90,6 +95,9 @@ def load_npz(file, obj, path='', strict=True):
         for path, mon in codebook.attached_monitors(opt.target):
             key = codebook.SNAPSHOT_PREFIX + (path + '/' if path else '')
             mon.load_state({k: f[key + k] for k in ('usage', 'steps_seen', 'seed', 'decay') if key + k in f})
+        for path, ema in codebook_ema.attached_emas(opt.target):
+            key = codebook_ema.SNAPSHOT_PREFIX + (path + '/' if path else '')
+            ema.load_state({k: f[key + k] for k in codebook_ema.STATE_KEYS if key + k in f})
 
 
 def _load_link(f, link, prefix, strict):

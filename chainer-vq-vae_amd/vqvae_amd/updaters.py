@@ -6,7 +6,7 @@ that provide the attributes the reference's ``update_core`` bodies use
 import os
 import numpy as np
 
-from . import backend, core
+from . import backend, codebook_ema, core
 from .comm import SingleCommunicator, shard as strided_shard
 
 
@@ -209,6 +209,13 @@ class _codebook_share_discarded(object):
         return False
 
 
+def _ema_codebook(model):
+    """Whether ``model.vq`` moves by the EMA rule (codebook_ema.EMACodebook).  The codebook loss then has no one to train
+    and is not back-propagated: its backward and the fp64 scatter of utils.py:227-228 leave the step, W's gradient stays
+    the zero ``model.vq.cleargrads()`` left."""
+    return getattr(getattr(model, 'vq', None), 'codebook_ema', None) is not None
+
+
 def three_loss_backward(model, losses, merged=None):
     """The gradient routing of the reference's updaters (updaters.py:14-18, 58-69):
     clear everything, back-propagate the reconstruction loss, throw away what it put on the
@@ -222,7 +229,8 @@ def three_loss_backward(model, losses, merged=None):
             else:
                 loss1.backward()
         model.vq.cleargrads()
-        loss2.backward()
+        if not _ema_codebook(model):
+            loss2.backward()
         if not _merged_sweep(losses, merged):
             loss3.backward()
 
@@ -239,6 +247,7 @@ class VQVAE_StandardUpdater(StandardUpdater):
             self.last_losses = loss_func(*arrays)
             three_loss_backward(optimizer.target, self.last_losses)
             optimizer.update()
+            codebook_ema.step_attached(optimizer.target)
         self._run_step(in_arrays, body)
 
 
@@ -340,6 +349,7 @@ class VQVAE_ParallelUpdater(StandardUpdater):
         if exchange:
             self.comm.allreduce_grad(optimizer.grads)       # sum over ranks, in place
         optimizer.update()
+        codebook_ema.step_attached(model, self.comm)
 
     def loss_func_model(self, model):
         """The link whose .encoder / .vq the three losses route into: ``loss_func`` when it is such a link (a custom
@@ -383,10 +393,12 @@ class VQVAE_ParallelUpdater(StandardUpdater):
         backend.wait_event(side, backend.Event().record(main))      # loss1's gradients are complete
         for off, size in early:
             self.comm.allreduce_grad(optimizer.grads.flat_view(off, size), stream=side)
-        loss2.backward()
+        if not _ema_codebook(model):
+            loss2.backward()
         if not merged:
             loss3.backward()
         for off, size in late:
             self.comm.allreduce_grad(optimizer.grads.flat_view(off, size))
         backend.wait_event(main, backend.Event().record(side))      # join before the optimizer reads the arena
         optimizer.update()
+        codebook_ema.step_attached(model, self.comm)

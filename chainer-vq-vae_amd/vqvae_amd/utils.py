@@ -164,7 +164,9 @@ def straight_through(x, W):
 
 class VQ(Link):
     """utils.py:239-255.  ``vq.monitor = CodebookMonitor(vq)`` (codebook.py) opts into usage statistics: in train
-    mode every application that ran the nearest-code search hands its latents and indices to the monitor."""
+    mode every application that ran the nearest-code search hands its latents and indices to the monitor.
+    ``vq.codebook_ema = EMACodebook(vq)`` (codebook_ema.py) opts into the EMA codebook rule: the same applications hand
+    the same pair to ``accumulate``, and the updaters call ``step`` behind ``optimizer.update()``."""
 
     def __init__(self, k, d=None, initialW=None):
         super(VQ, self).__init__()
@@ -196,10 +198,13 @@ class VQ(Link):
                            (node.indexes, y.data))
             if self._monitor is not None and core.config.train:     # once per step: the second application is a preset
                 self._monitor.observe(x.data, node.indexes)
+            if self._codebook_ema is not None and core.config.train:
+                self._codebook_ema.accumulate(x.data, node.indexes)
         return y
 
     _cache = None
     _monitor = None
+    _codebook_ema = None
 
     @property
     def monitor(self):
@@ -210,6 +215,16 @@ class VQ(Link):
         if mon is not self._monitor:
             self._monitor = mon
             core.bump_param_epoch('monitor')      # a recorded step was captured with (or without) the old one
+
+    @property
+    def codebook_ema(self):
+        return self._codebook_ema
+
+    @codebook_ema.setter
+    def codebook_ema(self, ema):
+        if ema is not self._codebook_ema:
+            self._codebook_ema = ema
+            core.bump_param_epoch('monitor')      # as for the monitor: the recorded step has other launches now
 
     def _w_version(self):
         opt = getattr(self.W, '_owner_step', None)
