@@ -19,8 +19,15 @@ already launched (`python -m torch.distributed.run --nproc-per-node N bench.py
 a "step" is one nearest-codebook search + gather over N latent rows; the line
 reports the expansion-form MFMA rate and the algorithmic HBM GB/s side by side.
 
-Prints ONE JSON line on rank 0.  Extra objects:
-  roofline     -- the north star's kernel (ResidualBlock forward: dilated conv +
+Prints ONE JSON line on rank 0.  A plain run does what the headline needs and no more: set-up, the warm-up steps, the
+timed steps, --dump-outputs, the line (metric, value, unit, ms_per_step, dtype, the job's description and what the
+timed steps themselves left: the last step's losses, the float32x2 guard's count, the all-reduce times of N > 1 ranks,
+and `roofline` where the timed launches carried their own events: eager steps, c4).  --full adds, after the timed
+region and outside it, every measurement and check that takes a pass of its own, each as an object of the line:
+  ms_per_step_with_input -- the same steps with the input leg inside the step (a fresh host minibatch every step).
+  fp32_mfma_reference    -- the same job with --matmul float32.
+  c4: indices_match_reference_order_distance_on_64_rows -- exact host distances for 64 of the rows.
+  roofline     -- (of hipGraph replays, the default: an eager pass; roofline.kernels: always a pass) the north star's kernel (ResidualBlock forward: dilated conv +
                   condition step + gate): algorithmic FLOPs per launch / its mean
                   launch time from the dispatch's own HIP events.  It is no longer
                   the largest consumer of the step: roofline.kernels lists EVERY
@@ -476,15 +483,6 @@ def run_c4(args, rank, n, local):
         ach = flop / (avg_ms * 1e-3) / 1e12 if cnt.value else None
         gbs = byts / (avg_ms * 1e-3) / 1e9 if cnt.value else None
         traffic, tsrc = measured_traffic('c4_N%d' % N)
-        # sanity of the result itself on a bounded sample: exact reference distances for 64 rows
-        got = idx.get().reshape(-1)
-        pick = np.linspace(0, N - 1, 64).astype(np.int64)
-        ok = True
-        for r in pick:
-            dist = np.zeros(k, np.float32)
-            for c in range(d):
-                dist = dist + (rows[r, c] - W[:, c]) ** 2   # utils.py:189-203 summation order
-            ok = ok and int(np.argmin(dist)) == int(got[r])
         out = {
             'metric': 'VQ nearest-codebook lookups/sec (k=8192, d=128), whole job',
             'value': n * N * args.steps / dt, 'unit': 'latent rows/s', 'n_gpus': n,
@@ -495,7 +493,6 @@ def run_c4(args, rank, n, local):
                                    '(B=%d x T\'=120), half N(0,1) half near-codebook rows' % (N, B),
                        'parallelism': 'dp%d (independent rows per rank, no data-path collective)' % n},
             'rows_rechecked_exactly': int(nre.get()[0]),
-            'indices_match_reference_order_distance_on_64_rows': bool(ok),
             'matmul': mode,
             'roofline': {'bound': 'mfma', 'kernel': 'vqvae_vq_nearest_fwd (vq_wnorm + %s + vq_exact_batched_kernel '
                          '+ gather): MFMA pairwise distance, wavefront argmin, exact re-check of ambiguous rows'
@@ -511,6 +508,17 @@ def run_c4(args, rank, n, local):
                                  'frac': (gbs / 8000.0) if gbs else None,
                                  'algorithmic_bytes_per_launch': byts}},
         }
+        if args.full:
+            # sanity of the result itself on a bounded sample: exact reference distances for 64 rows
+            got = idx.get().reshape(-1)
+            pick = np.linspace(0, N - 1, 64).astype(np.int64)
+            ok = True
+            for r in pick:
+                dist = np.zeros(k, np.float32)
+                for c in range(d):
+                    dist = dist + (rows[r, c] - W[:, c]) ** 2   # utils.py:189-203 summation order
+                ok = ok and int(np.argmin(dist)) == int(got[r])
+            out['indices_match_reference_order_distance_on_64_rows'] = bool(ok)
         print(json.dumps(out))
     if n > 1 or args.force_comm:
         comm.barrier()
@@ -522,7 +530,13 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run every other measurement and check of the benchmark, outside the timed '
+                         'region: the gate kernel\'s roofline where the timed steps are hipGraph replays and the per-kernel table '
+                         '(eager passes with per-launch events), the same steps with a fresh host minibatch each, the fp32 MFMA '
+                         'reference, the CPU baseline; c4: the exact host re-check of 64 rows.  A plain run sets up, warms up, times '
+                         'the steps and prints the line')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip cpu_baseline and fp32_mfma_reference')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last of them left to its caller as DIR/<name>.npy (float32; '
                          'rank 0): the three losses, the parameter arena (trained values, then the EMA shadows) and the '
@@ -547,8 +561,8 @@ def main():
     ap.add_argument('--graph', action='store_true', help='replay the step as a hipGraph also with a communicator (n > 1)')
     ap.add_argument('--no-graph', action='store_true', help='eager launches every step')
     ap.add_argument('--no-fresh-input', action='store_true',
-                    help='skip the second timed region (ms_per_step_with_input: a fresh host minibatch every step)')
-    ap.add_argument('--no-kernel-table', action='store_true', help='skip roofline.kernels (the eager pass with every chain kernel timed)')
+                    help='--full: skip the second timed region (ms_per_step_with_input: a fresh host minibatch every step)')
+    ap.add_argument('--no-kernel-table', action='store_true', help='--full: skip roofline.kernels (the eager pass with every chain kernel timed)')
     ap.add_argument('--no-overlap', action='store_true',
                     help='single stream (the default since the float32x3 kernels; kept for the profile scripts)')
     ap.add_argument('--overlap', action='store_true',
@@ -670,7 +684,7 @@ def main():
     lib = _lib.load()
     lib.vqvae_prof_reset()
     if not use_graph:
-        lib.vqvae_prof_enable(1 << tag)      # (a replayed recording carries no per-launch events: timed below, eagerly)
+        lib.vqvae_prof_enable(1 << tag)      # (a replayed recording carries no per-launch events: --full times the kernel below, eagerly)
     timed_comm = hasattr(comm, 'time_comm')
     if timed_comm:
         comm.time_comm = True            # HIP events around every all-reduce, on the stream it runs on
@@ -684,11 +698,11 @@ def main():
     comm.barrier()
     dt = time.perf_counter() - t0
     lib.vqvae_prof_enable(0)
-    if args.dump_outputs and rank == 0:      # (here: the passes below step the model further)
-        dump_outputs(args.dump_outputs, {'losses': np.array([float(l.data.get()) for l in upd.last_losses]),
-                                         'params': opt.params.get(), 'grads': opt.grads.get()})
+    losses = [float(l.data.get()) for l in upd.last_losses]      # (here: the passes of --full step the model further)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'losses': np.array(losses), 'params': opt.params.get(), 'grads': opt.grads.get()})
     roofline_pass = 'the timed steps'
-    if use_graph:
+    if args.full and use_graph:
         # per-launch time of the gate kernel: the same job, the same kernels, launched eagerly with the dispatch's own
         # start / stop events (hipExtLaunchKernelGGL) right after the timed region
         upd.graph = False
@@ -713,15 +727,17 @@ def main():
     comm_ms_step_max = comm.max_scalar(comm_ms / args.steps)
     comm_ms_step_min = -comm.max_scalar(-comm_ms / args.steps)
 
-    import ctypes as C
-    tot = C.c_double(0)
-    cnt = C.c_int(0)
-    _lib.call('vqvae_prof_read', tag, C.byref(tot), C.byref(cnt))
-    losses = [float(l.data.get()) for l in upd.last_losses]
+    # `roofline` is in the line when the gate kernel's launches were timed: by the eager timed steps themselves, or by --full's pass above
+    gate_timed = args.full or not use_graph
+    if gate_timed:                          # (read before the kernel table's pass resets the profiler)
+        import ctypes as C
+        tot = C.c_double(0)
+        cnt = C.c_int(0)
+        _lib.call('vqvae_prof_read', tag, C.byref(tot), C.byref(cnt))
     seen = comm.ranks_seen()
     # every kernel family of the chain against ITS roofline (same job, eager, per-launch events; outside the timed region)
     ktable = None
-    if rank == 0 and n == 1 and not args.bf16 and not args.no_kernel_table:
+    if args.full and rank == 0 and n == 1 and not args.bf16 and not args.no_kernel_table:
         upd.graph = False
         upd.update()
         backend.synchronize()
@@ -731,7 +747,7 @@ def main():
     # memory when the previous step started -- page-locked double buffer, copy stream, binning on the device
     # (inputs.StreamingInputIterator).  Timed like the main region, reported beside it, never as `value`.
     fresh_ms = None
-    if index_input and not args.no_fresh_input:
+    if args.full and index_input and not args.no_fresh_input:
         from vqvae_amd.inputs import StreamingInputIterator
         for s in range(2, 8):               # eight distinct host minibatches, cycled
             ex = synth_examples(B, cfg, seed=71 + 1000 * rank + s)
@@ -754,7 +770,7 @@ def main():
         fresh_ms = 1e3 * comm.max_scalar(time.perf_counter() - t1) / args.steps
         upd._iterators['main'] = it
     ref_ms = None
-    if n == 1 and mode in PRODUCTS_PER_FP32 and not args.no_cpu_baseline:
+    if args.full and n == 1 and mode in PRODUCTS_PER_FP32 and not args.no_cpu_baseline:
         # the same step with the fp32 MFMA kernels, for reference (not part of the timed region above)
         upd.graph = False
         backend.set_matmul_dtype('float32')
@@ -774,21 +790,6 @@ def main():
         T = cfg['length']
         samples = n * B * T * args.steps
         value = samples / dt
-        # algorithmic FLOPs of one launch of the gate kernel (ResidualBlock forward), SURVEY 8(d):
-        # `dilconv1d` fwd = 2*B*T*Cout*Cin*K, plus -- now that the residual 1x1 conv runs inside the
-        # same launch -- its 2*B*T*Cr*(Cd/2); the condition projection is not in this kernel's
-        # contraction (computed once at the latent rate and lerped in the epilogue)
-        flop_conv = 2.0 * B * T * cfg['dilated'] * cfg['filter_size'] * cfg['residual']
-        flop = flop_conv + FUSED_RES_FLOP_PER_POS(cfg) * B * T
-        x3 = mode in PRODUCTS_PER_FP32
-        X3_PRODUCTS = PRODUCTS_PER_FP32.get(mode, 1)
-        # the pipe that bounds the kernel: fp32 MFMA; the 16-bit MFMA pipe ('bfloat16'); or that pipe doing
-        # X3_PRODUCTS products per algorithmic fp32 product ('float32x3': 6 bf16, 'float32x2': 3 fp16)
-        peak = PEAK_BF16_MFMA_TFLOPS if args.bf16 else (PEAK_BF16_MFMA_TFLOPS / X3_PRODUCTS if x3 else PEAK_FP32_MFMA_TFLOPS)
-        avg_ms = tot.value / max(cnt.value, 1)
-        ach = flop / (avg_ms * 1e-3) / 1e12 if cnt.value else None
-        key = ('c2' if args.workload == 'c2' else 'c5') + ('_bf16' if args.bf16 else {'float32x2': '', 'float32x3': '_x3', 'float32': '_fp32mfma'}[mode]) + '_B%d' % B
-        traffic, tsrc = measured_traffic(key)
         out = {
             'metric': 'audio samples/sec, VQ-VAE fwd+bwd+Adam step, 16 kHz mu-law (whole job)',
             'value': value, 'unit': 'samples/s', 'n_gpus': n, 'ranks_seen_by_rccl': seen,
@@ -797,11 +798,6 @@ def main():
             'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None,
             'step_execution': ('one hipGraph launch per step (recorded after two eager steps; bit-identical to the eager step)'
                                if use_graph else 'eager launches'),
-            'ms_per_step_with_input': fresh_ms,
-            'with_input_is': (None if fresh_ms is None else
-                              'the same %d steps with the input leg inside the step: each minibatch starts in host memory '
-                              '(8 distinct host minibatches, cycled), page-locked double buffer -> copy stream -> mu-law '
-                              'binning on the device (0.5 MB of waveform per step instead of the 125.8 MB one-hot)' % args.steps),
             'backward': ('loss1 + loss3 back-propagated in one sweep (the encoder walked once with g1 + g3 at z), then vq.cleargrads() and '
                          'loss2: the gradients of updaters.py:14-18, encoder to fp32 rounding, the rest bit for bit (DESIGN.md section 1)'
                          if V.updaters.MERGED_BACKWARD else "the reference's three sweeps (updaters.py:14-18)"),
@@ -843,45 +839,68 @@ def main():
                        'parallelism': 'dp%d (one process/GPU, RCCL all-reduce of the flat grad arena)' % n},
             'trainable_params': int(n_params),
             'losses_last_step': losses,
-            'roofline': {'bound': 'mfma', 'kernel': {'float32x3': ROOFLINE_KERNEL_X3, 'float32x2': ROOFLINE_KERNEL_X2, 'bfloat16': ROOFLINE_KERNEL_BF16}.get(mode, ROOFLINE_KERNEL),
-                         'achieved': ach, 'peak': peak, 'unit': 'TFLOP/s',
-                         'peak_is': ('dense bf16 MFMA peak' if args.bf16 else
-                                     ('dense 16-bit MFMA peak (2500) / %d MFMA products per fp32 product; achieved counts '
-                                      'algorithmic fp32 FLOPs' % X3_PRODUCTS if x3 else 'fp32 MFMA peak')),
-                         'frac': (ach / peak) if ach else None,
-                         'achieved_vs_fp32_mfma_peak': (ach / PEAK_FP32_MFMA_TFLOPS) if (ach and not args.bf16) else None,
-                         'achieved_vs_measured_sustained_mfma': ((ach * X3_PRODUCTS / SUSTAINED_MFMA_TFLOPS_REAL_DATA[mode])
-                                                                 if (ach and x3 and not args.bf16) else None),
-                         'sustained_is': ('%.0f TFLOP/s: the %d-product MFMA stream alone on real operands, whole chip '
-                                          '(tools/ubench/mfma_power.hip, f16x2_probe.hip; %.0f nominal)'
-                                          % (SUSTAINED_MFMA_TFLOPS_REAL_DATA[mode], X3_PRODUCTS, PEAK_BF16_MFMA_TFLOPS))
-                                         if (x3 and not args.bf16) else None,
-                         'hbm': {'achieved_algorithmic': (GATE_BYTES(cfg, B, args.bf16) / (avg_ms * 1e-3) / 1e9) if cnt.value else None,
-                                 'peak': 8000.0, 'unit': 'GB/s',
-                                 'frac': (GATE_BYTES(cfg, B, args.bf16) / (avg_ms * 1e-3) / 1e9 / 8000.0) if cnt.value else None,
-                                 'algorithmic_bytes_per_launch': GATE_BYTES(cfg, B, args.bf16),
-                                 'note': 'x read once, the saved gate values + z written once (float32x2: sigmoid and z, the backward takes tanh = z / sigmoid; other fp32 modes: tanh, sigmoid, z; --bf16: all as bf16), weights, latent-rate condition slice (DESIGN.md sections 3, 3a, 3c)'},
-                         'traffic': traffic, 'traffic_source': tsrc,
-                         'launches': cnt.value, 'avg_launch_ms': avg_ms, 'avg_launch_ms_measured_over': roofline_pass,
-                         'flop_per_launch': flop, 'flop_per_launch_dilconv1d_only': flop_conv,
-                         'kernels': None if ktable is None else ktable[0],
-                         'kernels_measured_over': None if ktable is None else (
-                             '%d eager steps of the same job (%.3f ms per step with the per-launch events on), outside the timed region; '
-                             'dispatch events per GEMM launch, stream events around a weight-gradient launch + its reduce; '
-                             'mfma peak as in roofline.peak_is, hbm peak 8000 GB/s; work = algorithmic FLOPs / bytes (SURVEY 8d)'
-                             % (min(args.steps, 10), ktable[1]))},
         }
         if mode == 'float32x2':
             # the run-time guard of the mode's pre-split storage: every backward sweep of this process so far --
             # warm-up, timed, with-input and eager steps -- compared each pre-split tensor's bound with its actual maximum on
             # the device; `violations` = tensors whose bound was more than 2^log2_limit above it (0 = the contract held)
             out['f32x2_contract'] = backend.f32x2_contract_violations()
-        if ref_ms is not None:
-            out['fp32_mfma_reference'] = {'ms_per_step': ref_ms, 'value': B * T / (ref_ms * 1e-3), 'unit': 'samples/s',
-                                          'note': "the same job with --matmul float32 (v_mfma_f32_32x32x2_f32), "
-                                                  "%d steps after 2 warm-up steps, outside the timed region" % min(args.steps, 5)}
-        if n == 1 and not args.no_cpu_baseline and args.workload == 'c2' and not args.bf16:
-            out['cpu_baseline'] = cpu_baseline(cfg)
+        if gate_timed:
+            # algorithmic FLOPs of one launch of the gate kernel (ResidualBlock forward), SURVEY 8(d):
+            # `dilconv1d` fwd = 2*B*T*Cout*Cin*K, plus -- now that the residual 1x1 conv runs inside the
+            # same launch -- its 2*B*T*Cr*(Cd/2); the condition projection is not in this kernel's
+            # contraction (computed once at the latent rate and lerped in the epilogue)
+            flop_conv = 2.0 * B * T * cfg['dilated'] * cfg['filter_size'] * cfg['residual']
+            flop = flop_conv + FUSED_RES_FLOP_PER_POS(cfg) * B * T
+            x3 = mode in PRODUCTS_PER_FP32
+            X3_PRODUCTS = PRODUCTS_PER_FP32.get(mode, 1)
+            # the pipe that bounds the kernel: fp32 MFMA; the 16-bit MFMA pipe ('bfloat16'); or that pipe doing
+            # X3_PRODUCTS products per algorithmic fp32 product ('float32x3': 6 bf16, 'float32x2': 3 fp16)
+            peak = PEAK_BF16_MFMA_TFLOPS if args.bf16 else (PEAK_BF16_MFMA_TFLOPS / X3_PRODUCTS if x3 else PEAK_FP32_MFMA_TFLOPS)
+            avg_ms = tot.value / max(cnt.value, 1)
+            ach = flop / (avg_ms * 1e-3) / 1e12 if cnt.value else None
+            key = ('c2' if args.workload == 'c2' else 'c5') + ('_bf16' if args.bf16 else {'float32x2': '', 'float32x3': '_x3', 'float32': '_fp32mfma'}[mode]) + '_B%d' % B
+            traffic, tsrc = measured_traffic(key)
+            out['roofline'] = {
+                'bound': 'mfma', 'kernel': {'float32x3': ROOFLINE_KERNEL_X3, 'float32x2': ROOFLINE_KERNEL_X2, 'bfloat16': ROOFLINE_KERNEL_BF16}.get(mode, ROOFLINE_KERNEL),
+                'achieved': ach, 'peak': peak, 'unit': 'TFLOP/s',
+                'peak_is': ('dense bf16 MFMA peak' if args.bf16 else
+                            ('dense 16-bit MFMA peak (2500) / %d MFMA products per fp32 product; achieved counts '
+                             'algorithmic fp32 FLOPs' % X3_PRODUCTS if x3 else 'fp32 MFMA peak')),
+                'frac': (ach / peak) if ach else None,
+                'achieved_vs_fp32_mfma_peak': (ach / PEAK_FP32_MFMA_TFLOPS) if (ach and not args.bf16) else None,
+                'achieved_vs_measured_sustained_mfma': ((ach * X3_PRODUCTS / SUSTAINED_MFMA_TFLOPS_REAL_DATA[mode])
+                                                        if (ach and x3 and not args.bf16) else None),
+                'sustained_is': ('%.0f TFLOP/s: the %d-product MFMA stream alone on real operands, whole chip '
+                                 '(tools/ubench/mfma_power.hip, f16x2_probe.hip; %.0f nominal)'
+                                 % (SUSTAINED_MFMA_TFLOPS_REAL_DATA[mode], X3_PRODUCTS, PEAK_BF16_MFMA_TFLOPS))
+                                if (x3 and not args.bf16) else None,
+                'hbm': {'achieved_algorithmic': (GATE_BYTES(cfg, B, args.bf16) / (avg_ms * 1e-3) / 1e9) if cnt.value else None,
+                        'peak': 8000.0, 'unit': 'GB/s',
+                        'frac': (GATE_BYTES(cfg, B, args.bf16) / (avg_ms * 1e-3) / 1e9 / 8000.0) if cnt.value else None,
+                        'algorithmic_bytes_per_launch': GATE_BYTES(cfg, B, args.bf16),
+                        'note': 'x read once, the saved gate values + z written once (float32x2: sigmoid and z, the backward takes tanh = z / sigmoid; other fp32 modes: tanh, sigmoid, z; --bf16: all as bf16), weights, latent-rate condition slice (DESIGN.md sections 3, 3a, 3c)'},
+                'traffic': traffic, 'traffic_source': tsrc,
+                'launches': cnt.value, 'avg_launch_ms': avg_ms, 'avg_launch_ms_measured_over': roofline_pass,
+                'flop_per_launch': flop, 'flop_per_launch_dilconv1d_only': flop_conv,
+                'kernels': None if ktable is None else ktable[0],
+                'kernels_measured_over': None if ktable is None else (
+                    '%d eager steps of the same job (%.3f ms per step with the per-launch events on), outside the timed region; '
+                    'dispatch events per GEMM launch, stream events around a weight-gradient launch + its reduce; '
+                    'mfma peak as in roofline.peak_is, hbm peak 8000 GB/s; work = algorithmic FLOPs / bytes (SURVEY 8d)'
+                    % (min(args.steps, 10), ktable[1]))}
+        if args.full:
+            out['ms_per_step_with_input'] = fresh_ms
+            out['with_input_is'] = (None if fresh_ms is None else
+                                    'the same %d steps with the input leg inside the step: each minibatch starts in host memory '
+                                    '(8 distinct host minibatches, cycled), page-locked double buffer -> copy stream -> mu-law '
+                                    'binning on the device (0.5 MB of waveform per step instead of the 125.8 MB one-hot)' % args.steps)
+            if ref_ms is not None:
+                out['fp32_mfma_reference'] = {'ms_per_step': ref_ms, 'value': B * T / (ref_ms * 1e-3), 'unit': 'samples/s',
+                                              'note': "the same job with --matmul float32 (v_mfma_f32_32x32x2_f32), "
+                                                      "%d steps after 2 warm-up steps, outside the timed region" % min(args.steps, 5)}
+            if n == 1 and not args.no_cpu_baseline and args.workload == 'c2' and not args.bf16:
+                out['cpu_baseline'] = cpu_baseline(cfg)
         print(json.dumps(out))
     if n > 1 or args.force_comm:
         comm.barrier()

@@ -78,6 +78,41 @@ def test_bench_self_spawn_reaches_rccl(gpu, tmp_path):
     assert dump['params'].size == 4 << 20 and sum(a.nbytes for a in dump.values()) <= 64e6
 
 
+def test_bench_plain_run_stops_at_the_headline_and_full_goes_on(gpu, tmp_path):
+    """`python bench.py --gpus 1 --steps N --warmup W` without --full: set-up, warm-up, the timed steps (hipGraph
+    replays), --dump-outputs, the line.  The line has the headline and none of the objects that take passes of their
+    own; its losses are the last TIMED step's, the ones --dump-outputs wrote.  With --full the same timed steps (the
+    same dumps, bit for bit) are followed by those passes, and the line carries their objects."""
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR'):
+        env.pop(k, None)
+    moved = ('roofline', 'ms_per_step_with_input', 'with_input_is', 'fp32_mfma_reference', 'cpu_baseline')
+    recs, dumps = {}, {}
+    for name, extra in (('plain', []), ('full', ['--full', '--no-cpu-baseline'])):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                              '--batch', '2', '--dump-outputs', str(tmp_path / name)] + extra,
+                             env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+        assert out.returncode == 0, out.stderr.decode()[-2000:]
+        lines = [l for l in out.stdout.decode().splitlines() if l.startswith('{')]
+        assert len(lines) == 1, out.stdout.decode()[-2000:]
+        rec = recs[name] = json.loads(lines[0])
+        assert rec['unit'] == 'samples/s' and rec['higher_is_better'] is True and rec['dtype'].startswith('f32')
+        assert rec['steps'] == 3 and rec['warmup'] == 1 and rec['step_execution'].startswith('one hipGraph launch')
+        assert rec['ms_per_step'] > 0 and abs(rec['value'] * rec['ms_per_step'] * 1e-3 / (2 * 7680) - 1) < 1e-9
+        assert rec['f32x2_contract']['violations'] == 0
+        assert sorted(os.listdir(str(tmp_path / name))) == ['grads.npy', 'losses.npy', 'params.npy']
+        dumps[name] = {f: np.load(str(tmp_path / name / f)) for f in ('grads.npy', 'losses.npy', 'params.npy')}
+        np.testing.assert_array_equal(dumps[name]['losses.npy'], np.array(rec['losses_last_step'], np.float32))
+    for key in moved:
+        assert key not in recs['plain'], key
+    full = recs['full']
+    assert full['roofline']['achieved'] > 0 and full['roofline']['kernels'] and full['ms_per_step_with_input'] > 0
+    assert 'cpu_baseline' not in full and 'fp32_mfma_reference' not in full          # --no-cpu-baseline
+    assert set(recs['plain']) == set(full) - set(moved)
+    for f in dumps['plain']:
+        np.testing.assert_array_equal(dumps['plain'][f], dumps['full'][f])
+
+
 def test_bench_two_ranks_spawned_from_bare_invocation(gpu):
     """`python bench.py --gpus 2` with no launcher: the parent spawns two ranks that rendezvous
     and call ncclCommInitRank.  On a one-GPU box rank 1 has no device of its own, so both are

@@ -21,7 +21,7 @@ bench.main()
 args = sys.argv[1]
 for rep in range(2):
     for var in sys.argv[2:]:
-        out = subprocess.run([sys.executable, '-c', RUN % (ROOT, ROOT, var, '--no-cpu-baseline --no-kernel-table --steps 20 --warmup 5 ' + args)],
+        out = subprocess.run([sys.executable, '-c', RUN % (ROOT, ROOT, var, '--full --no-cpu-baseline --no-kernel-table --steps 20 --warmup 5 ' + args)],
                              capture_output=True, text=True)
         line = [l for l in out.stdout.splitlines() if l.startswith('{')]
         if not line:

@@ -1,10 +1,12 @@
 #!/bin/bash
-# per-kernel rocprofv3 stats of a short bench run -> gpurun_out/kstats.csv and a top-10 print
+# per-kernel rocprofv3 stats of a short bench run (--full: the line's roofline is printed beside them) -> $OUT_DIR/kstats.csv
+# (default bench_out/) and a top-10 print
+ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=$(mkdir -p "${OUT_DIR:-$ROOT/bench_out}" && cd "${OUT_DIR:-$ROOT/bench_out}" && pwd)
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o r1 -- python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline "$@" > /tmp/b.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o r1 -- python $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline "$@" > /tmp/b.log 2>&1
 f=$(find /tmp/prof -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] || { echo "no stats"; tail -5 /tmp/b.log; exit 1; }
-mkdir -p $GRAFT_REPO_ROOT/gpurun_out; cp $f $GRAFT_REPO_ROOT/gpurun_out/kstats.csv
+cp $f $OUT/kstats.csv
 python - "$f" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))

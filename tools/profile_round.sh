@@ -1,15 +1,15 @@
 #!/bin/bash
-# One GPU visit that produces every profile artefact of the round under gpurun_out/prof_<tag>/:
-#   kernel-trace stats of bench.py for c2 (default), c4, c5 --bf16, and separate --pmc passes
+# One GPU visit that produces every profile artefact of the round under $OUT_DIR/prof_<tag>/ (default bench_out/):
+#   kernel-trace stats of bench.py --full for c2 (default), c4, c5 --bf16, and separate --pmc passes
 #   (FETCH_SIZE / WRITE_SIZE / MFMA busy / instruction mix) for the dominant kernel of each.
 # usage: bash tools/profile_round.sh <tag>
 TAG=${1:-r5}
-OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG; mkdir -p $OUT
+ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=${OUT_DIR:-$ROOT/bench_out}/prof_$TAG; mkdir -p $OUT; OUT=$(cd $OUT && pwd)
 cd /tmp && export TMPDIR=/tmp
 run_stats() {   # name, bench args...
   local name=$1; shift
   rm -rf /tmp/ps_$name
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ps_$name -o s -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline "$@" > $OUT/${name}_bench.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ps_$name -o s -- python $ROOT/bench.py --full --no-cpu-baseline "$@" > $OUT/${name}_bench.log 2>&1
   f=$(find /tmp/ps_$name -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $OUT/${name}_kernel_stats.csv || echo "no stats for $name"
   grep "^{" $OUT/${name}_bench.log | tail -1 > $OUT/${name}_bench_line.json
@@ -17,8 +17,8 @@ run_stats() {   # name, bench args...
 run_pmc() {     # name, counters, bench args...
   local name=$1; local ctr=$2; shift; shift
   rm -rf /tmp/pp_$name
-  timeout 300 rocprofv3 --pmc $ctr --output-format csv -d /tmp/pp_$name -o p -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline "$@" > /tmp/pp_$name.log 2>&1 || echo "pmc pass $name failed"
-  python $GRAFT_REPO_ROOT/tools/pmc_summary.py /tmp/pp_$name > $OUT/${name}.csv
+  timeout 300 rocprofv3 --pmc $ctr --output-format csv -d /tmp/pp_$name -o p -- python $ROOT/bench.py "$@" > /tmp/pp_$name.log 2>&1 || echo "pmc pass $name failed"
+  python $ROOT/tools/pmc_summary.py /tmp/pp_$name > $OUT/${name}.csv
 }
 # (--no-graph: eager launches, so that bench.py's own per-launch events and rocprofv3 time the same dispatches;
 #  --no-fresh-input: one timed region = `steps + warmup` steps in the stats)

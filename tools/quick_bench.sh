@@ -1,10 +1,10 @@
 #!/bin/bash
-# bench.py once, the line's essentials + the per-kernel table.  usage: bash tools/quick_bench.sh [bench args]
-cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" > gpurun_out/qb.json 2> gpurun_out/qb.err || tail -5 gpurun_out/qb.err
-python - <<'PY'
-import json
-d = json.loads([l for l in open('gpurun_out/qb.json') if l.startswith('{')][-1])
+# bench.py --full once, the line's essentials + the per-kernel table.  usage: bash tools/quick_bench.sh [bench args]
+cd "$(dirname "$0")/.."; OUT=${OUT_DIR:-bench_out}; mkdir -p $OUT
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline "$@" > $OUT/qb.json 2> $OUT/qb.err || tail -5 $OUT/qb.err
+python - $OUT/qb.json <<'PY'
+import json, sys
+d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])
 r = d['roofline']
 print('ms/step %.3f  with input %s  gate %.1f us frac %.3f' % (d['ms_per_step'], d.get('ms_per_step_with_input'), 1e3 * r['avg_launch_ms'], r['frac']))
 for k in (r.get('kernels') or []):

@@ -3,7 +3,7 @@
 # re-stamp profiles/roofline_traffic.json (bench.py's `roofline.traffic`) against the current kernel sources.
 TAG=${1:-r6}
 cd "$(dirname "$0")/.."
-P=gpurun_out/prof_$TAG
+P=${OUT_DIR:-bench_out}/prof_$TAG
 mkdir -p profiles/$TAG
 cp $P/*.csv $P/*_bench_line.json profiles/$TAG/
 [ -f $P/bench_default.json ] && cp $P/bench_default.json profiles/$TAG/

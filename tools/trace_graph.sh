@@ -1,14 +1,15 @@
 #!/bin/bash
 # bench.py with the recorded step (hipGraph replay) under rocprofv3 --kernel-trace: the last replayed step's launches with
-# their real gaps -> gpurun_out/<tag>_graph_laststep.csv and a sequence summary.  usage: bash tools/trace_graph.sh <tag> [bench args]
+# their real gaps -> $OUT_DIR/<tag>_graph_laststep.csv (default bench_out/) and a sequence summary.  --full: the step is picked by
+# counting back over the eager steps of the roofline pass.  usage: bash tools/trace_graph.sh <tag> [bench args]
 TAG=${1:-g}; shift
+ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=$(mkdir -p "${OUT_DIR:-$ROOT/bench_out}" && cd "${OUT_DIR:-$ROOT/bench_out}" && pwd)
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/tg_$TAG
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tg_$TAG -o t -- python $GRAFT_REPO_ROOT/bench.py --steps 6 --warmup 3 --no-fresh-input --no-cpu-baseline --no-kernel-table "$@" > /tmp/tg_$TAG.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tg_$TAG -o t -- python $ROOT/bench.py --full --steps 6 --warmup 3 --no-fresh-input --no-cpu-baseline --no-kernel-table "$@" > /tmp/tg_$TAG.log 2>&1
 t=$(find /tmp/tg_$TAG -name "*kernel_trace.csv" | head -1)
 [ -n "$t" ] || { echo "no trace"; tail -5 /tmp/tg_$TAG.log; exit 1; }
-mkdir -p $GRAFT_REPO_ROOT/gpurun_out
 grep "^{" /tmp/tg_$TAG.log | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms/step under the profiler', d['ms_per_step'], d['step_execution'][:30])"
-python - "$t" "$GRAFT_REPO_ROOT/gpurun_out/${TAG}_graph_laststep.csv" <<'PY'
+python - "$t" "$OUT/${TAG}_graph_laststep.csv" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 ks = sorted(((int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'], r.get('Queue_Id', ''), r['Grid_Size_X'], r['Workgroup_Size_X']) for r in rows), key=lambda t: t[0])
