@@ -2,6 +2,7 @@
 // launch: weight packing (pack_kernel), maxima and norms behind the float32x2 scales and bounds (wamax / absmax / wl1
 // kernels), the stride-2 phase split, the latent pull-back reduce.  The contraction kernels live in conv_gemm_x3.hip,
 // conv_gemm_fp32.hip and wgrad.hip (gemm_common.h).
+#include <algorithm>
 #include "gemm_common.h"
 #include <stdlib.h>
 #include <map>
@@ -261,11 +262,7 @@ static int check_conv_desc(const vqvae_conv1d_desc* d) {
   return 0;
 }
 
-static size_t conv_pack_floats(const vqvae_conv1d_desc* d) {
-  size_t f = (size_t)d->K * slab_rows(d->Cin) * pad128(d->Cout);
-  size_t b = (size_t)d->K * slab_rows(d->Cout) * pad128(d->Cin);
-  return f > b ? f : b;
-}
+static size_t wgrad_bytes(const WgradPlan& p) { return (p.slab_floats + p.bslab_floats) * sizeof(float); }      // launch_wgrad's slabs, from the workspace's start
 
 // Stride-2 convs (the encoder, net.py:14-28): their weight gradient contracts gy[t] with x[2 t + e].  The fast
 // weight-gradient kernels read 16-byte runs of consecutive t, so x is first split into its even and odd phases
@@ -274,9 +271,6 @@ static size_t conv_pack_floats(const vqvae_conv1d_desc* d) {
 static int phase_pitch(const vqvae_conv1d_desc* d) { return ((d->Tin + 1) / 2 + 3) & ~3; }
 static bool phase_split_ok(const vqvae_conv1d_desc* d) {
   return d->stride == 2 && d->dil == 1 && d->K <= MAXSEG && d->Tout % 4 == 0 && d->Tin >= 8;
-}
-static size_t phase_split_floats(const vqvae_conv1d_desc* d) {
-  return phase_split_ok(d) ? (size_t)2 * d->B * d->Cin * phase_pitch(d) + 64 : 0;
 }
 __global__ void phase_split_kernel(const float* __restrict__ x, long rows, int Tin, int Tp, float* __restrict__ xe,
                                    float* __restrict__ xo, const int32_t* __restrict__ skip_flag) {
@@ -323,22 +317,47 @@ extern "C" int vqvae_absmax(const float* x, size_t n, uint32_t* amax, vqvae_stre
   return launch_absmax(x, (long)n, amax, st);
 }
 
-extern "C" size_t vqvae_conv1d_workspace_bytes(const vqvae_conv1d_desc* d) {
-  if (!d) return 0;
+// The generic conv's workspace holds one of three layouts, each from its start:
+//   forward [0] / backward-data [1]: the packed weights, then (they may split K) the partial tiles
+//   backward-weight:                 launch_wgrad's slabs, then the even and the odd phase of x (stride-2 convs)
+// and, in its last 128 bytes, the maxima of a float32x2 launch: AMAX_SLOTS words for the activation operand, then as many
+// for the weights (backward-weight: for gy).  An entry point takes what the caller's ws_bytes covers: the partial tiles, the
+// phase split and the float32x2 launch each need their piece to fit.
+struct ConvPlan {
+  size_t slab_bytes[2], partial[2], partial_bytes[2];
+  WgradPlan wg;
+  size_t phase_e, phase_o, phase_end;        // phase_end: where the weight-gradient layout ends; 0 = this conv is not phase-split
+  size_t amax, total;
+};
+static ConvPlan conv_plan(const vqvae_conv1d_desc* d) {
+  ConvPlan c;
+  for (int back = 0; back < 2; ++back) {
+    const int Ci = back ? d->Cout : d->Cin, Co = back ? d->Cin : d->Cout, To = back ? d->Tin : d->Tout;
+    WsPlan w;
+    c.slab_bytes[back] = (size_t)d->K * slab_rows(Ci) * pad128(Co) * sizeof(float);
+    w.take(c.slab_bytes[back]);
+    c.partial_bytes[back] = ksplit_partial_floats(Co, To, d->B, d->K * cdiv(Ci, BK)) * sizeof(float);
+    c.partial[back] = w.take(c.partial_bytes[back]);
+  }
+  const int K = d->K < MAXTAPS ? d->K : MAXTAPS;      // (the query does not validate its desc)
   int cins[MAXTAPS];
-  for (int i = 0; i < d->K && i < MAXTAPS; ++i) cins[i] = d->Cin;
-  WgradPlan p = plan_wgrad(d->Cout, d->B, d->Tout, cins, d->K < MAXTAPS ? d->K : MAXTAPS);
-  size_t wg = (p.slab_floats + p.bslab_floats) * sizeof(float) + phase_split_floats(d) * sizeof(float);
-  size_t pk = conv_pack_floats(d) * sizeof(float);
-  // forward / backward-data may split K: packed weights first, then the partial tiles
-  size_t pf = ksplit_partial_floats(d->Cout, d->Tout, d->B, d->K * cdiv(d->Cin, BK));
-  size_t pb = ksplit_partial_floats(d->Cin, d->Tin, d->B, d->K * cdiv(d->Cout, BK));
-  size_t gm = align_up(pk, 256) + (pf > pb ? pf : pb) * sizeof(float);
-  return align_up(wg > gm ? wg : gm, 256) + 512;      // (the last 128 bytes: maxima of a float32x2 launch)
+  for (int i = 0; i < K; ++i) cins[i] = d->Cin;
+  c.wg = plan_wgrad(d->Cout, d->B, d->Tout, cins, K);
+  WsPlan w;
+  w.take(wgrad_bytes(c.wg));
+  const size_t plane = (size_t)d->B * d->Cin * phase_pitch(d) * sizeof(float);
+  c.phase_e = w.take(2 * plane);
+  c.phase_o = c.phase_e + plane;
+  c.phase_end = phase_split_ok(d) ? wgrad_bytes(c.wg) + 2 * plane + 256 : 0;      // (+ 256: room for phase_e's alignment)
+  // the total keeps the slack it has always had (callers hold workspaces of the queried size): the larger of the layouts,
+  // the packed side taken as the larger slab followed by the larger set of partial tiles, and 512 bytes for the maxima
+  const size_t wgb = c.phase_end ? c.phase_end : wgrad_bytes(c.wg);
+  const size_t gm = align_up(std::max(c.slab_bytes[0], c.slab_bytes[1]), 256) + std::max(c.partial_bytes[0], c.partial_bytes[1]);
+  c.total = align_up(std::max(wgb, gm), 256) + 512;
+  c.amax = c.total - 2 * AMAX_SLOTS * sizeof(unsigned);
+  return c;
 }
-static unsigned* conv_amax_slots(const vqvae_conv1d_desc* d, void* ws) {
-  return reinterpret_cast<unsigned*>((char*)ws + vqvae_conv1d_workspace_bytes(d) - 2 * AMAX_SLOTS * sizeof(unsigned));
-}
+extern "C" size_t vqvae_conv1d_workspace_bytes(const vqvae_conv1d_desc* d) { return d ? conv_plan(d).total : 0; }
 
 // ---- weights packed AHEAD of the launch that reads them (vqvae_conv1d_amax::packed).  The forward / backward-data entry
 // points re-lay W into their workspace in front of every GEMM: one or two small launches (wamax_kernel, pack_kernel) that a
@@ -346,13 +365,17 @@ static unsigned* conv_amax_slots(const vqvae_conv1d_desc* d, void* ws) {
 // critical path.  The weights only change in the optimizer, so a caller may pack all of a step's slabs at once, on
 // another stream, as soon as the optimizer is done (vqvae_amd/backend.py: PackPrefetch), and hand each launch its slab.
 // A packed buffer = the slab, then (256-byte aligned) the AMAX_SLOTS words of max |W| that a float32x2 launch reads.
-static size_t conv_slab_bytes(const vqvae_conv1d_desc* d, int backward) {
-  const size_t f = backward ? (size_t)d->K * slab_rows(d->Cout) * pad128(d->Cin) : (size_t)d->K * slab_rows(d->Cin) * pad128(d->Cout);
-  return align_up(f * sizeof(float), 256);
+struct PackedPlan { size_t slab, amax, total; };
+static PackedPlan conv_packed_plan(const vqvae_conv1d_desc* d, int backward) {
+  WsPlan w; PackedPlan p;
+  p.slab = w.take((size_t)d->K * slab_rows(backward ? d->Cout : d->Cin) * pad128(backward ? d->Cin : d->Cout) * sizeof(float));
+  p.amax = w.take(256);
+  p.total = w.total;
+  return p;
 }
 extern "C" size_t vqvae_conv1d_packed_bytes(const vqvae_conv1d_desc* d, int backward) {
   if (!d || d->K < 1 || d->K > MAXTAPS) return 0;
-  return conv_slab_bytes(d, backward) + 256;
+  return conv_packed_plan(d, backward).total;
 }
 extern "C" int vqvae_conv1d_pack(int n, const vqvae_conv1d_desc* descs, const float* const* W, const int* backward,
                                  void* const* packed, vqvae_stream_t s) {
@@ -367,7 +390,7 @@ extern "C" int vqvae_conv1d_pack(int n, const vqvae_conv1d_desc* descs, const fl
       if ((conv_f16x2(d) ? 1 : 0) != fmt3) continue;
       PackJob j = backward[i] ? pack_bwd_job((float*)packed[i], W[i], d->Cout, d->Cin, d->K, pad128(d->Cin))
                               : pack_fwd_job((float*)packed[i], W[i], d->Cout, d->Cin, d->K, 0, pad128(d->Cout), 0, pad128(d->Cout));
-      j.amax = fmt3 ? reinterpret_cast<unsigned*>((char*)packed[i] + conv_slab_bytes(d, backward[i])) : nullptr;
+      j.amax = fmt3 ? (unsigned*)((char*)packed[i] + conv_packed_plan(d, backward[i]).amax) : nullptr;
       pa.job[pa.njob++] = j;
       if (pa.njob == MAXSEG) { if (int e = launch_pack(pa, st, fmt3 ? 3 : -1)) return e; pa.njob = 0; }
     }
@@ -403,13 +426,14 @@ static int conv1d_fwd_impl(const vqvae_conv1d_desc* d, const float* x, const flo
   VQ_REQUIRE(x && W && y && ws, "conv1d_fwd: null pointer");
   hipStream_t st = (hipStream_t)s;
   const int ldw = pad128(d->Cout), rp = slab_rows(d->Cin);
-  if ((size_t)d->K * rp * ldw * sizeof(float) > ws_bytes) { set_error("conv1d_fwd: workspace too small"); return VQVAE_E_WORKSPACE; }
+  const ConvPlan c = conv_plan(d);
+  if (c.slab_bytes[0] > ws_bytes) { set_error("conv1d_fwd: workspace too small"); return VQVAE_E_WORKSPACE; }
   const void* pre = (cam && skip_flag == nullptr) ? cam->packed : nullptr;      // packed ahead (vqvae_conv1d_pack)
   float* pk = pre ? (float*)pre : (float*)ws;
-  const bool f16 = conv_f16x2(d) && skip_flag == nullptr && ws_bytes >= vqvae_conv1d_workspace_bytes(d);
+  const bool f16 = conv_f16x2(d) && skip_flag == nullptr && ws_bytes >= c.total;
   VQ_REQUIRE(!pre || f16 == conv_f16x2(d), "conv1d_fwd: workspace too small for the launch the packed slab was written for");
-  unsigned* am = f16 ? conv_amax_slots(d, ws) : nullptr;
-  unsigned* wam = !f16 ? nullptr : (pre ? reinterpret_cast<unsigned*>((char*)pre + conv_slab_bytes(d, 0)) : am + AMAX_SLOTS);
+  unsigned* am = f16 ? (unsigned*)((char*)ws + c.amax) : nullptr;
+  unsigned* wam = !f16 ? nullptr : (pre ? (unsigned*)((char*)pre + conv_packed_plan(d, 0).amax) : am + AMAX_SLOTS);
   const unsigned* xam = am;          // the operand's maximum: the caller's (it travelled with the tensor) or a scan
   if (f16 && cam && cam->x) xam = cam->x;
   else if (f16) {
@@ -437,11 +461,7 @@ static int conv1d_fwd_impl(const vqvae_conv1d_desc* d, const float* x, const flo
   g.out[0].bias = b; g.out[0].relu = d->relu;
   g.out[0].amax_out = cam ? cam->out : nullptr;
   g.skip_flag = skip_flag;
-  {
-    const size_t pkb = align_up((size_t)d->K * rp * ldw * sizeof(float), 256);
-    const size_t need = ksplit_partial_floats(d->Cout, d->Tout, d->B, d->K * cdiv(d->Cin, BK)) * sizeof(float);
-    if (need > 0 && pkb + need <= ws_bytes) g.partial = (float*)((char*)ws + pkb);
-  }
+  if (c.partial_bytes[0] > 0 && c.partial[0] + c.partial_bytes[0] <= ws_bytes) g.partial = (float*)((char*)ws + c.partial[0]);
   return launch_gemm<EPI_LINEAR>(g, VQVAE_PROF_CONV_FWD, st);
 }
 
@@ -469,13 +489,14 @@ static int conv1d_bwd_data_impl(const vqvae_conv1d_desc* d, const float* W, cons
   VQ_REQUIRE(W && gy && gx && ws, "conv1d_bwd_data: null pointer");
   hipStream_t st = (hipStream_t)s;
   const int ldw = pad128(d->Cin), rp = slab_rows(d->Cout);
-  if ((size_t)d->K * rp * ldw * sizeof(float) > ws_bytes) { set_error("conv1d_bwd_data: workspace too small"); return VQVAE_E_WORKSPACE; }
+  const ConvPlan c = conv_plan(d);
+  if (c.slab_bytes[1] > ws_bytes) { set_error("conv1d_bwd_data: workspace too small"); return VQVAE_E_WORKSPACE; }
   const void* pre = cam ? cam->packed : nullptr;      // packed ahead (vqvae_conv1d_pack, backward form)
   float* pk = pre ? (float*)pre : (float*)ws;
-  const bool f16 = conv_f16x2(d) && ws_bytes >= vqvae_conv1d_workspace_bytes(d);
+  const bool f16 = conv_f16x2(d) && ws_bytes >= c.total;
   VQ_REQUIRE(!pre || f16 == conv_f16x2(d), "conv1d_bwd_data: workspace too small for the launch the packed slab was written for");
-  unsigned* am = f16 ? conv_amax_slots(d, ws) : nullptr;
-  unsigned* wam = !f16 ? nullptr : (pre ? reinterpret_cast<unsigned*>((char*)pre + conv_slab_bytes(d, 1)) : am + AMAX_SLOTS);
+  unsigned* am = f16 ? (unsigned*)((char*)ws + c.amax) : nullptr;
+  unsigned* wam = !f16 ? nullptr : (pre ? (unsigned*)((char*)pre + conv_packed_plan(d, 1).amax) : am + AMAX_SLOTS);
   const unsigned* gam = am;
   if (f16 && cam && cam->gy) gam = cam->gy;
   else if (f16) {
@@ -504,11 +525,7 @@ static int conv1d_bwd_data_impl(const vqvae_conv1d_desc* d, const float* W, cons
   g.out[0].accumulate = accumulate;
   g.out[0].amax_out = cam ? cam->out : nullptr;
   if (x_relu) { g.out[0].add = x_relu; g.out[0].add_bstride = (long)d->Cin * d->Tin; g.out[0].add_is_mask = 1; }
-  {
-    const size_t pkb = align_up((size_t)d->K * rp * ldw * sizeof(float), 256);
-    const size_t need = ksplit_partial_floats(d->Cin, d->Tin, d->B, d->K * cdiv(d->Cout, BK)) * sizeof(float);
-    if (need > 0 && pkb + need <= ws_bytes) g.partial = (float*)((char*)ws + pkb);
-  }
+  if (c.partial_bytes[1] > 0 && c.partial[1] + c.partial_bytes[1] <= ws_bytes) g.partial = (float*)((char*)ws + c.partial[1]);
   return launch_gemm<EPI_LINEAR>(g, VQVAE_PROF_CONV_BWD_DATA, st);
 }
 
@@ -537,20 +554,19 @@ static int conv1d_bwd_weight_impl(const vqvae_conv1d_desc* d, const float* x, co
   if (int e = check_conv_desc(d)) return e;
   VQ_REQUIRE(x && gy && gW && ws, "conv1d_bwd_weight: null pointer");
   hipStream_t st = (hipStream_t)s;
-  int cins[MAXSEG];
-  for (int i = 0; i < d->K; ++i) cins[i] = d->Cin;
-  WgradPlan p = plan_wgrad(d->Cout, d->B, d->Tout, cins, d->K);
-  if ((p.slab_floats + p.bslab_floats) * sizeof(float) > ws_bytes) { set_error("conv1d_bwd_weight: workspace too small"); return VQVAE_E_WORKSPACE; }
+  const ConvPlan c = conv_plan(d);
+  const WgradPlan& p = c.wg;
+  if (wgrad_bytes(p) > ws_bytes) { set_error("conv1d_bwd_weight: workspace too small"); return VQVAE_E_WORKSPACE; }
   WgradArgs w; memset(&w, 0, sizeof(w));
   w.gy = gy; w.gy_bstride = (long)d->Cout * d->Tout; w.M = d->Cout; w.Tout = d->Tout; w.B = d->B;
   w.nseg = d->K;
-  const bool phases = phase_split_ok(d) && (p.slab_floats + p.bslab_floats + phase_split_floats(d)) * sizeof(float) <= ws_bytes;
+  const bool phases = c.phase_end && c.phase_end <= ws_bytes;
   float* xe = nullptr;
   float* xo = nullptr;
   const int Tp = phase_pitch(d);
   if (phases) {
-    xe = (float*)ws + ((p.slab_floats + p.bslab_floats + 63) / 64) * 64;
-    xo = xe + (size_t)d->B * d->Cin * Tp;
+    xe = (float*)((char*)ws + c.phase_e);
+    xo = (float*)((char*)ws + c.phase_o);
     const long rows = (long)d->B * d->Cin;
     long nb = (rows * Tp + 255) / 256;
     if (nb > 4096) nb = 4096;
@@ -573,8 +589,8 @@ static int conv1d_bwd_weight_impl(const vqvae_conv1d_desc* d, const float* x, co
   }
   w.seg[0].gb = gb; w.accumulate = accumulate;
   w.skip_flag = skip_flag;
-  if (conv_f16x2(d) && !phases && d->stride == 1 && skip_flag == nullptr && ws_bytes >= vqvae_conv1d_workspace_bytes(d)) {
-    unsigned* am = conv_amax_slots(d, ws);
+  if (conv_f16x2(d) && !phases && d->stride == 1 && skip_flag == nullptr && ws_bytes >= c.total) {
+    unsigned* am = (unsigned*)((char*)ws + c.amax);
     const unsigned* xam = am;
     const unsigned* gam = am + AMAX_SLOTS;
     if (cam && cam->x) xam = cam->x;
@@ -1126,25 +1142,44 @@ __global__ void bias_sum_list_kernel(const PtrList bl, int nb, int n, float* out
   out[i] = v;
 }
 
+// The vqvae_resstack_* entry points share one workspace, each laying out its own pieces from the start; the query is the
+// largest of them.  It has always ended in room for the weights' maxima of a float32x2 skip sum plus 1024 spare bytes,
+// whichever layout was the largest, so every layout's total ends in that tail.
+constexpr size_t RESSTACK_WAMAX_BYTES = MAXSEG * AMAX_SLOTS * sizeof(unsigned), RESSTACK_SPARE_BYTES = 1024;
+// skip sum: the blocks' packed Ws slabs (block l's at l * slab_bytes) | the summed biases | AMAX_SLOTS words of max |Ws| per block
+struct SkipPlan { size_t slab_bytes, bsum, wamax, total; };
+static SkipPlan resstack_skip_plan(const vqvae_resblock_desc* d, int nblocks) {
+  WsPlan w; SkipPlan p;
+  p.slab_bytes = (size_t)slab_rows(d->Cd / 2) * pad128(d->Cs) * sizeof(float);
+  w.take(nblocks * p.slab_bytes);
+  p.bsum = w.take(pad128(d->Cs) * sizeof(float));
+  p.wamax = w.take(RESSTACK_WAMAX_BYTES);
+  p.total = w.total + RESSTACK_SPARE_BYTES;
+  return p;
+}
+// condition gradient: the blocks' packed Wc slabs, backward form (block l's at l * slab_bytes)
+struct GcondPlan { size_t slab_bytes, total; };
+static GcondPlan resstack_gcond_plan(const vqvae_resblock_desc* d, int nblocks) {
+  WsPlan w; GcondPlan p;
+  p.slab_bytes = (size_t)slab_rows(d->Cd) * pad128(d->Cc) * sizeof(float);
+  w.take(nblocks * p.slab_bytes);
+  p.total = w.total + RESSTACK_WAMAX_BYTES + RESSTACK_SPARE_BYTES;
+  return p;
+}
+// skip (M = Cs) / res (M = Cr) weight gradients of n blocks: launch_wgrad's slabs
+static WgradPlan resstack_wgrad_plan(const vqvae_resblock_desc* d, int M, int n) {
+  int cz[MAXSEG];
+  for (int i = 0; i < n; ++i) cz[i] = d->Cd / 2;
+  return plan_wgrad(M, d->B, d->T, cz, n);
+}
 extern "C" size_t vqvae_resstack_workspace_bytes(const vqvae_resblock_desc* d, int nblocks) {
   if (!d || nblocks < 1 || nblocks > MAXSEG) return 0;
-  const int Ch = d->Cd / 2;
-  size_t skip_pk = (size_t)nblocks * slab_rows(Ch) * pad128(d->Cs) + pad128(d->Cs);
-  size_t gc_pk = (size_t)nblocks * slab_rows(d->Cd) * pad128(d->Cc);
-  int cz[MAXSEG];
-  for (int i = 0; i < nblocks; ++i) cz[i] = Ch;
   // the res-conv gradients skip blocks without a residual output (the last one), and the split
   // count -- hence the slab volume -- is not monotonic in the segment count: cover every count
   size_t wg = 0;
-  for (int n = 1; n <= nblocks; ++n) {
-    WgradPlan p = plan_wgrad(d->Cs, d->B, d->T, cz, n);
-    WgradPlan p2 = plan_wgrad(d->Cr, d->B, d->T, cz, n);
-    if (p.slab_floats + p.bslab_floats > wg) wg = p.slab_floats + p.bslab_floats;
-    if (p2.slab_floats + p2.bslab_floats > wg) wg = p2.slab_floats + p2.bslab_floats;
-  }
-  size_t m = skip_pk > gc_pk ? skip_pk : gc_pk;
-  if (wg > m) m = wg;
-  return m * sizeof(float) + 1024 + MAXSEG * AMAX_SLOTS * sizeof(unsigned);     // (+ the weights' maxima of a float32x2 skip sum)
+  for (int n = 1; n <= nblocks; ++n)
+    wg = std::max({wg, wgrad_bytes(resstack_wgrad_plan(d, d->Cs, n)), wgrad_bytes(resstack_wgrad_plan(d, d->Cr, n))});
+  return std::max({wg + RESSTACK_WAMAX_BYTES + RESSTACK_SPARE_BYTES, resstack_skip_plan(d, nblocks).total, resstack_gcond_plan(d, nblocks).total});
 }
 
 // stage: 1 = pack the slabs / sum the biases into ws only (vqvae_resstack_skip_prepare), 2 = the GEMM only, over a ws that was
@@ -1176,21 +1211,21 @@ static int resstack_skip_impl(const vqvae_resblock_desc* d, int nblocks, const f
   if (int e = check_rb(d)) return e;
   VQ_REQUIRE(nblocks >= 1 && nblocks <= MAXSEG, "resstack_skip_fwd: 1..%d blocks", MAXSEG);
   VQ_REQUIRE(ws, "resstack_skip_fwd: null pointer");
-  if (ws_bytes < vqvae_resstack_workspace_bytes(d, nblocks)) { set_error("resstack_skip_fwd: workspace too small"); return VQVAE_E_WORKSPACE; }
+  const SkipPlan sp = resstack_skip_plan(d, nblocks);
+  if (ws_bytes < sp.total) { set_error("resstack_skip_fwd: workspace too small"); return VQVAE_E_WORKSPACE; }
   hipStream_t st = (hipStream_t)s;
   const int Ch = d->Cd / 2, T = d->T;
-  const int ld = pad128(d->Cs), rp = slab_rows(Ch);
-  float* w = (float*)ws;
-  float* bsum = w + (size_t)nblocks * rp * ld;
+  const int ld = pad128(d->Cs);
+  float* bsum = (float*)((char*)ws + sp.bsum);
   // matmul mode 3: float32x2 -- the operand is the gate output, |z| <= 1 by construction, so only the weights' maxima
   // (one per block, behind the bias sums) have to be found
   const bool f16 = g_matmul_dtype == 3;
-  unsigned* wam = reinterpret_cast<unsigned*>(bsum + pad128(d->Cs));
+  unsigned* wam = (unsigned*)((char*)ws + sp.wamax);
   if (stage & 1) {
     PackArgs pa; pa.njob = 0;
     PtrList bl;
     for (int l = 0; l < nblocks; ++l) {
-      pa.job[pa.njob] = pack_fwd_job(w + (size_t)l * rp * ld, Ws[l], d->Cs, Ch, 1, 0, ld, 0, ld);
+      pa.job[pa.njob] = pack_fwd_job((float*)((char*)ws + l * sp.slab_bytes), Ws[l], d->Cs, Ch, 1, 0, ld, 0, ld);
       pa.job[pa.njob++].amax = f16 ? wam + l * AMAX_SLOTS : nullptr;
       bl.p[l] = bs[l];
     }
@@ -1203,7 +1238,7 @@ static int resstack_skip_impl(const vqvae_resblock_desc* d, int nblocks, const f
   g.nseg = nblocks;
   for (int l = 0; l < nblocks; ++l) {
     Seg& sg = g.seg[l];
-    seg_stride1(sg, z[l], Ch, T, 0, w + (size_t)l * rp * ld, ld);
+    seg_stride1(sg, z[l], Ch, T, 0, (float*)((char*)ws + l * sp.slab_bytes), ld);
     if (f16) { sg.amax_static = 1.f; sg.wamax = wam + l * AMAX_SLOTS; }
   }
   g.f16x2 = f16 ? 1 : 0;
@@ -1226,20 +1261,20 @@ extern "C" int vqvae_resstack_gcond_bwd(const vqvae_resblock_desc* d, int nblock
   VQ_REQUIRE(nblocks >= 1 && nblocks <= MAXSEG, "resstack_gcond_bwd: 1..%d blocks", MAXSEG);
   VQ_REQUIRE(Wc && gh && gcond && ws, "resstack_gcond_bwd: null pointer");
   VQ_REQUIRE(!(d->storage & VQVAE_STORE_GH_BF16), "resstack_gcond_bwd: reads fp32 gh (the latent-rate chain pulls a bf16 gh back with vqvae_upsample_linear_bwd_bf16)");
-  if (ws_bytes < vqvae_resstack_workspace_bytes(d, nblocks)) { set_error("resstack_gcond_bwd: workspace too small"); return VQVAE_E_WORKSPACE; }
+  const GcondPlan gp = resstack_gcond_plan(d, nblocks);
+  if (ws_bytes < gp.total) { set_error("resstack_gcond_bwd: workspace too small"); return VQVAE_E_WORKSPACE; }
   hipStream_t st = (hipStream_t)s;
   const int T = d->T;
-  const int ld = pad128(d->Cc), rp = slab_rows(d->Cd);
-  float* w = (float*)ws;
+  const int ld = pad128(d->Cc);
   PackArgs pa; pa.njob = 0;
   for (int l = 0; l < nblocks; ++l)
-    pa.job[pa.njob++] = pack_bwd_job(w + (size_t)l * rp * ld, Wc[l], d->Cd, d->Cc, 1, ld);
+    pa.job[pa.njob++] = pack_bwd_job((float*)((char*)ws + l * gp.slab_bytes), Wc[l], d->Cd, d->Cc, 1, ld);
   if (int e = launch_pack(pa, st)) return e;
   GemmArgs g; memset(&g, 0, sizeof(g));
   g.nseg = nblocks;
   for (int l = 0; l < nblocks; ++l) {
     Seg& sg = g.seg[l];
-    seg_stride1(sg, gh[l], d->Cd, T, 0, w + (size_t)l * rp * ld, ld);
+    seg_stride1(sg, gh[l], d->Cd, T, 0, (float*)((char*)ws + l * gp.slab_bytes), ld);
   }
   g.M = d->Cc; g.Tout = T; g.B = d->B;
   g.out[0].y = gcond; g.out[0].y_bstride = (long)d->Cc * T; g.out[0].rows = d->Cc;
@@ -1254,12 +1289,10 @@ extern "C" int vqvae_resstack_skip_wgrad(const vqvae_resblock_desc* d, int nbloc
   if (int e = check_rb(d)) return e;
   VQ_REQUIRE(nblocks >= 1 && nblocks <= MAXSEG, "resstack_skip_wgrad: 1..%d blocks", MAXSEG);
   VQ_REQUIRE(g_skip && z && gWs && ws, "resstack_skip_wgrad: null pointer");
-  if (ws_bytes < vqvae_resstack_workspace_bytes(d, nblocks)) { set_error("resstack_skip_wgrad: workspace too small"); return VQVAE_E_WORKSPACE; }
+  const WgradPlan p = resstack_wgrad_plan(d, d->Cs, nblocks);
+  if (ws_bytes < wgrad_bytes(p)) { set_error("resstack_skip_wgrad: workspace too small"); return VQVAE_E_WORKSPACE; }
   hipStream_t st = (hipStream_t)s;
   const int Ch = d->Cd / 2, T = d->T;
-  int cz[MAXSEG];
-  for (int i = 0; i < nblocks; ++i) cz[i] = Ch;
-  WgradPlan p = plan_wgrad(d->Cs, d->B, T, cz, nblocks);
   WgradArgs wa; memset(&wa, 0, sizeof(wa));
   wa.gy = g_skip; wa.gy_bstride = (long)d->Cs * T; wa.M = d->Cs; wa.Tout = T; wa.B = d->B;
   wa.nseg = nblocks;
@@ -1289,12 +1322,11 @@ extern "C" int vqvae_resstack_res_wgrad(const vqvae_resblock_desc* d, int nblock
   VQ_REQUIRE(g_res && z && gWr && ws, "resstack_res_wgrad: null pointer");
   hipStream_t st = (hipStream_t)s;
   const int Ch = d->Cd / 2, T = d->T;
-  int cz[MAXSEG];
   int n = 0;
   WgradArgs wa; memset(&wa, 0, sizeof(wa));
   for (int l = 0; l < nblocks; ++l) {
     if (!g_res[l] || !gWr[l]) continue;
-    WSeg& sg = wa.seg[n];
+    WSeg& sg = wa.seg[n++];
     sg.gy = g_res[l];
     wseg_stride1(sg, z[l], Ch, T, 0);
     sg.gw = gWr[l]; sg.gw_co_stride = Ch; sg.gw_ci_stride = 1;
@@ -1302,12 +1334,11 @@ extern "C" int vqvae_resstack_res_wgrad(const vqvae_resblock_desc* d, int nblock
     sg.amax_x_static = 1.f;                                   // |z| <= 1
     sg.amax_gy = g_res_amax ? g_res_amax[l] : nullptr;
     if (!sg.amax_gy) g_res_amax = nullptr;                    // one segment without its maximum: the whole launch keeps mode 2's kernel
-    cz[n++] = Ch;
   }
   if (n == 0) return 0;
   if (g_matmul_dtype == 3 && g_res_amax) wa.f16x2 = 1;
-  WgradPlan p = plan_wgrad(d->Cr, d->B, T, cz, n);
-  if ((p.slab_floats + p.bslab_floats) * sizeof(float) > ws_bytes) { set_error("resstack_res_wgrad: workspace too small"); return VQVAE_E_WORKSPACE; }
+  const WgradPlan p = resstack_wgrad_plan(d, d->Cr, n);
+  if (ws_bytes < wgrad_bytes(p)) { set_error("resstack_res_wgrad: workspace too small"); return VQVAE_E_WORKSPACE; }
   wa.gy = wa.seg[0].gy; wa.gy_bstride = (long)d->Cr * T; wa.M = d->Cr; wa.Tout = T; wa.B = d->B;
   wa.nseg = n;
   wa.accumulate = accumulate;
@@ -1326,7 +1357,7 @@ extern "C" int vqvae_resblock_wgrad(const vqvae_resblock_desc* d, const float* x
   int cins[MAXTAPS];
   for (int j = 0; j < d->K; ++j) cins[j] = d->Cr;
   WgradPlan p = plan_wgrad(d->Cd, d->B, T, cins, d->K);
-  if ((p.slab_floats + p.bslab_floats) * sizeof(float) > ws_bytes) { set_error("resblock_wgrad: workspace too small"); return VQVAE_E_WORKSPACE; }
+  if (ws_bytes < wgrad_bytes(p)) { set_error("resblock_wgrad: workspace too small"); return VQVAE_E_WORKSPACE; }
   WgradArgs wa; memset(&wa, 0, sizeof(wa));
   wa.gy = gh; wa.gy_bstride = (long)d->Cd * T; wa.M = d->Cd; wa.Tout = T; wa.B = d->B;
   wa.nseg = d->K;
@@ -1339,6 +1370,14 @@ extern "C" int vqvae_resblock_wgrad(const vqvae_resblock_desc* d, const float* x
   wa.accumulate = accumulate;
   wa.g16 = (d->storage & VQVAE_STORE_GH_BF16) ? 1 : 0;
   return launch_wgrad(wa, p, (float*)ws, VQVAE_PROF_RESBLOCK_WGRAD, st);
+}
+
+// launch_wgrad's slabs for nseg (block, tap) segments; presplit: both operands are stored pre-split, and the launch takes the
+// wide plan where the shape runs on wgrad3_dma_kernel
+static WgradPlan dil_wgrad_plan(const vqvae_resblock_desc* d, int nseg, bool presplit) {
+  int cins[MAXSEG];
+  for (int i = 0; i < nseg; ++i) cins[i] = d->Cr;
+  return plan_wgrad(d->Cd, d->B, d->T, cins, nseg, presplit && wgrad_dma_shape(d->Cd, d->T, cins, nseg));
 }
 
 // gWd_l (+)= sum_{b,t} gh_l[b,:,t] x_l[b,:,t - (K-1-j) dil_l]^T, gbd_l (+)= rowsum(gh_l) for several
@@ -1355,13 +1394,12 @@ extern "C" int vqvae_resstack_dil_wgrad(const vqvae_resblock_desc* d, int nblock
   VQ_REQUIRE(dils && x && gh && gWd && ws, "resstack_dil_wgrad: null pointer");
   hipStream_t st = (hipStream_t)s;
   const int T = d->T;
-  int cins[MAXSEG];
   WgradArgs wa; memset(&wa, 0, sizeof(wa));
   int n = 0;
   for (int l = 0; l < nblocks; ++l) {
     VQ_REQUIRE(x[l] && gh[l] && dils[l] >= 1, "resstack_dil_wgrad: bad block %d", l);
     for (int j = 0; j < d->K; ++j) {
-      WSeg& sg = wa.seg[n];
+      WSeg& sg = wa.seg[n++];
       sg.gy = gh[l];
       wseg_stride1(sg, x[l], d->Cr, T, -(d->K - 1 - j) * dils[l]);
       sg.gw = gWd[l] ? gWd[l] + j : nullptr; sg.gw_co_stride = (long)d->Cr * d->K; sg.gw_ci_stride = d->K;
@@ -1369,14 +1407,13 @@ extern "C" int vqvae_resstack_dil_wgrad(const vqvae_resblock_desc* d, int nblock
       sg.amax_x = x_amax ? x_amax[l] : nullptr;
       sg.amax_gy = gh_amax ? gh_amax[l] : nullptr;
       if (!sg.amax_x || !sg.amax_gy) x_amax = gh_amax = nullptr;      // (see resstack_res_wgrad)
-      cins[n++] = d->Cr;
     }
   }
   if (g_matmul_dtype == 3 && x_amax && gh_amax) wa.f16x2 = 1;
   const bool both_presplit = (wa.f16x2 && (d->storage & VQVAE_STORE_GH_F16X2) && (d->storage & VQVAE_STORE_X_F16X2)) ||
                              (g_matmul_dtype == 1 && (d->storage & VQVAE_STORE_GH_BF16) && (d->storage & VQVAE_STORE_X_BF16) && T % 64 == 0);   // (mode 1: both stored as bf16)
-  WgradPlan p = plan_wgrad(d->Cd, d->B, T, cins, n, both_presplit && wgrad_dma_shape(d->Cd, T, cins, n));
-  if ((p.slab_floats + p.bslab_floats) * sizeof(float) > ws_bytes) { set_error("resstack_dil_wgrad: workspace too small"); return VQVAE_E_WORKSPACE; }
+  const WgradPlan p = dil_wgrad_plan(d, n, both_presplit);
+  if (ws_bytes < wgrad_bytes(p)) { set_error("resstack_dil_wgrad: workspace too small"); return VQVAE_E_WORKSPACE; }
   wa.gy = wa.seg[0].gy; wa.gy_bstride = (long)d->Cd * T; wa.M = d->Cd; wa.Tout = T; wa.B = d->B;
   wa.nseg = n;
   wa.accumulate = accumulate;
@@ -1389,17 +1426,10 @@ extern "C" int vqvae_resstack_dil_wgrad(const vqvae_resblock_desc* d, int nblock
 
 extern "C" size_t vqvae_resstack_dil_wgrad_workspace_bytes(const vqvae_resblock_desc* d, int nblocks) {
   if (!d || nblocks < 1 || nblocks * d->K > MAXSEG) return 0;
-  int cins[MAXSEG];
-  for (int i = 0; i < nblocks * d->K; ++i) cins[i] = d->Cr;
   size_t need = 0;             // any group of 1..nblocks blocks may be flushed; fewer tiles can mean more splits
-  for (int n = 1; n <= nblocks; ++n) {
-    for (int wide = 0; wide < 2; ++wide) {     // the launch takes the wide plan when both operands are stored pre-split (wgrad3_dma_kernel)
-      if (wide && !wgrad_dma_shape(d->Cd, d->T, cins, n * d->K)) continue;
-      WgradPlan p = plan_wgrad(d->Cd, d->B, d->T, cins, n * d->K, wide != 0);
-      if (p.slab_floats + p.bslab_floats > need) need = p.slab_floats + p.bslab_floats;
-    }
-  }
-  return need * sizeof(float) + 256;
+  for (int n = 1; n <= nblocks; ++n)
+    need = std::max({need, wgrad_bytes(dil_wgrad_plan(d, n * d->K, false)), wgrad_bytes(dil_wgrad_plan(d, n * d->K, true))});
+  return need + 256;
 }
 
 // ---------------------------------------------------------------------------

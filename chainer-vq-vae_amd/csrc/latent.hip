@@ -264,12 +264,10 @@ static int cstack_launch(const CStackArgs& a, bool backward, hipStream_t st) {
   using G = CStackGeom<C>;
   const size_t lds = backward ? G::lds_fwd : G::lds_fwd + (size_t)C * G::WP * sizeof(float);      // (forward: + the layer's weight image)
   if (backward) {
-    static bool attr = false;
-    if (!attr) { VQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cstack_bwd_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
+    if (int e = lds_opt_in<cstack_bwd_kernel<C>>(lds)) return e;
     hipLaunchKernelGGL(cstack_bwd_kernel<C>, dim3(a.B), dim3(G::NW * 64), lds, st, a);
   } else {
-    static bool attr = false;
-    if (!attr) { VQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cstack_fwd_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
+    if (int e = lds_opt_in<cstack_fwd_kernel<C>>(lds)) return e;
     hipLaunchKernelGGL(cstack_fwd_kernel<C>, dim3(a.B), dim3(G::NW * 64), lds, st, a);
   }
   VQ_LAUNCH_CHECK();
@@ -286,9 +284,14 @@ extern "C" int vqvae_convstack_supported(int L, int C, int T, const int* dil) {
   return 1;
 }
 
-extern "C" size_t vqvae_convstack_workspace_bytes(int L, int B, int C) {
-  return (size_t)B * L * ((size_t)C * 3 * C + C) * sizeof(float);
+// workspace: part[B][L][C * 3 C + C], every sample's share of the parameter gradients (cstack_reduce_kernel sums them)
+struct CStackPlan { size_t part, total; };
+static CStackPlan cstack_plan(int L, int B, int C) {
+  WsPlan w;
+  const size_t part = w.take((size_t)B * L * ((size_t)C * 3 * C + C) * sizeof(float), sizeof(float));
+  return {part, w.total};
 }
+extern "C" size_t vqvae_convstack_workspace_bytes(int L, int B, int C) { return cstack_plan(L, B, C).total; }
 
 extern "C" int vqvae_convstack_fwd(int L, int B, int C, int T, const int* dil, const float* x, const float* const* W,
                                    const float* const* b, float* const* h, vqvae_stream_t s) {
@@ -306,9 +309,10 @@ extern "C" int vqvae_convstack_bwd(int L, int B, int C, int T, const int* dil, c
                                    const float* const* h, const float* gy, float* gx, float* const* gW, float* const* gb,
                                    int accumulate, void* ws, size_t ws_bytes, vqvae_stream_t s) {
   VQ_REQUIRE(dil && x && W && h && gy && gW && gb && ws && B > 0 && vqvae_convstack_supported(L, C, T, dil), "convstack_bwd: unsupported stack");
-  if (ws_bytes < vqvae_convstack_workspace_bytes(L, B, C)) { set_error("convstack_bwd: workspace too small"); return VQVAE_E_WORKSPACE; }
+  const CStackPlan p = cstack_plan(L, B, C);
+  if (ws_bytes < p.total) { set_error("convstack_bwd: workspace too small"); return VQVAE_E_WORKSPACE; }
   CStackArgs a; memset(&a, 0, sizeof(a));
-  a.x = x; a.L = L; a.B = B; a.T = T; a.gy = gy; a.gx = gx; a.part = (float*)ws;
+  a.x = x; a.L = L; a.B = B; a.T = T; a.gy = gy; a.gx = gx; a.part = (float*)((char*)ws + p.part);
   CStackGrads gr; memset(&gr, 0, sizeof(gr));
   for (int l = 0; l < L; ++l) {
     VQ_REQUIRE(W[l] && h[l], "convstack_bwd: null layer %d", l);
@@ -317,7 +321,7 @@ extern "C" int vqvae_convstack_bwd(int L, int B, int C, int T, const int* dil, c
   }
   if (int e = (C == 64 ? cstack_launch<64>(a, true, (hipStream_t)s) : cstack_launch<32>(a, true, (hipStream_t)s))) return e;
   const int total = L * (C * 3 * C + C);
-  hipLaunchKernelGGL(cstack_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)s, (const float*)ws, gr, B, L, C, accumulate);
+  hipLaunchKernelGGL(cstack_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)s, (const float*)a.part, gr, B, L, C, accumulate);
   VQ_LAUNCH_CHECK();
   return 0;
 }
@@ -458,24 +462,30 @@ __global__ __launch_bounds__(256) void cstage_reduce_kernel(const float* __restr
 extern "C" int vqvae_conv_s2_bwd_supported(int Cin, int Cout, int K, int stride, int pad, int dil, int Tin, int Tout) {
   return (Cin == 64 && Cout == 64 && K == 4 && stride == 2 && pad == 1 && dil == 1 && Tin >= 2 && Tout == Tin / 2) ? 1 : 0;
 }
-extern "C" size_t vqvae_conv_s2_bwd_workspace_bytes(int B, int C, int Tin) {
-  return (size_t)B * ((Tin + 127) / 128) * ((size_t)C * 4 * C + C) * sizeof(float);
+// workspace: part[B * nslice][C * 4 C + C], the weight-gradient share of every workgroup (128 input columns of one sample)
+struct CStagePlan { int nslice; size_t part, total; };
+static CStagePlan cstage_plan(int B, int C, int Tin) {
+  WsPlan w;
+  const int nslice = (Tin + 127) / 128;
+  const size_t part = w.take((size_t)B * nslice * ((size_t)C * 4 * C + C) * sizeof(float), sizeof(float));
+  return {nslice, part, w.total};
 }
+extern "C" size_t vqvae_conv_s2_bwd_workspace_bytes(int B, int C, int Tin) { return cstage_plan(B, C, Tin).total; }
 extern "C" int vqvae_conv_s2_bwd(int B, int C, int Tin, int Tout, const float* x, const float* W, const float* gy, int mask_by_x,
                                  float* gx, float* gW, float* gb, int accumulate, void* ws, size_t ws_bytes, vqvae_stream_t s) {
   VQ_REQUIRE(x && W && gy && ws && B > 0 && vqvae_conv_s2_bwd_supported(C, C, 4, 2, 1, 1, Tin, Tout), "conv_s2_bwd: unsupported stage (C = 64, 4 taps, stride 2, pad 1, Tout = Tin / 2)");
-  if (ws_bytes < vqvae_conv_s2_bwd_workspace_bytes(B, C, Tin)) { set_error("conv_s2_bwd: workspace too small"); return VQVAE_E_WORKSPACE; }
+  const CStagePlan p = cstage_plan(B, C, Tin);
+  if (ws_bytes < p.total) { set_error("conv_s2_bwd: workspace too small"); return VQVAE_E_WORKSPACE; }
   CStageArgs a; memset(&a, 0, sizeof(a));
-  a.x = x; a.gy = gy; a.W = W; a.gx = gx; a.part = (float*)ws; a.B = B; a.Tin = Tin; a.Tout = Tout;
-  a.nslice = (Tin + 127) / 128; a.mask = mask_by_x;
+  a.x = x; a.gy = gy; a.W = W; a.gx = gx; a.part = (float*)((char*)ws + p.part); a.B = B; a.Tin = Tin; a.Tout = Tout;
+  a.nslice = p.nslice; a.mask = mask_by_x;
   const size_t lds = (size_t)(64 * 67 + 64 * 131) * sizeof(float);
-  static bool attr = false;
-  if (!attr) { VQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cstage_bwd_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
+  if (int e = lds_opt_in<cstage_bwd_kernel<64>>(lds)) return e;
   hipLaunchKernelGGL(cstage_bwd_kernel<64>, dim3(B * a.nslice), dim3(512), lds, (hipStream_t)s, a);
   VQ_LAUNCH_CHECK();
   if (gW || gb) {
     const int per = C * 4 * C + C;
-    hipLaunchKernelGGL(cstage_reduce_kernel, dim3((per + 255) / 256), dim3(256), 0, (hipStream_t)s, (const float*)ws, B * a.nslice, C, gW, gb, accumulate);
+    hipLaunchKernelGGL(cstage_reduce_kernel, dim3((per + 255) / 256), dim3(256), 0, (hipStream_t)s, (const float*)a.part, B * a.nslice, C, gW, gb, accumulate);
     VQ_LAUNCH_CHECK();
   }
   return 0;

@@ -1144,7 +1144,7 @@ int vqvae_upsample_linear_bwd(const float* gy, long gy_bstride, int B, int C, in
     if (nb > 8192) nb = 8192;
     const bool pipe = (Tout % 4 == 0) && (Tout / 4 <= UPB_NT * UPB_KV);
     if (pipe && nb > 512) nb = 512;            // persistent: 2 workgroups per CU, next row prefetched
-    VQ_CHECK_HIP(hipFuncSetAttribute((const void*)upsample_bwd_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int e = lds_opt_in<upsample_bwd_rows_kernel>(lds)) return e;
     hipLaunchKernelGGL(upsample_bwd_rows_kernel, dim3(nb), dim3(UPB_NT), lds, (hipStream_t)s, gy, gy_bstride, B, C, Tin, Tout, w0, w1, lo0, hi0, lo1, hi1, gx, gx_bstride);
   } else {
     hipLaunchKernelGGL(upsample_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, gy, gy_bstride, B, C, Tin, Tout, w0, w1, lo0, hi0, lo1, hi1, gx, gx_bstride);
@@ -1353,21 +1353,26 @@ int vqvae_embed_gather_fwd(const int32_t* idx, long idx_bstride, int B, int T, c
   return 0;
 }
 
-// workspace: [per-row partial histograms | class-sorted positions + class offsets (K == 2 gather form) | dense-conv fallback]
-static size_t embed_ws_sort_off(int B, int Cout, int q, int K) { return align_up((size_t)B * Cout * K * q * sizeof(float), 256); }
-static size_t embed_ws_conv_off(int B, int Cout, int q, int K, int T) {
-  return embed_ws_sort_off(B, Cout, q, K) + align_up((size_t)B * T * sizeof(unsigned short), 256) + align_up((size_t)B * (q + 1) * sizeof(int32_t), 256);
+// workspace: [per-row partial histograms | class-sorted positions | class offsets (K == 2 gather form) | dense-conv fallback]
+struct EmbedPlan { vqvae_conv1d_desc conv_desc; size_t part, perm, off, conv, total; };
+static EmbedPlan embed_plan(int B, int Cout, int q, int K, int T) {
+  WsPlan w;
+  EmbedPlan p = {{B, q, T, Cout, T, K, 1, K - 1, 1, 0}};       // the dense causal conv: pad K-1, cropped to T
+  p.part = w.take((size_t)B * Cout * K * q * sizeof(float));
+  p.perm = w.take((size_t)B * T * sizeof(unsigned short));
+  p.off = w.take((size_t)B * (q + 1) * sizeof(int32_t));
+  p.conv = w.take(vqvae_conv1d_workspace_bytes(&p.conv_desc));
+  p.total = w.total + 256;
+  return p;
 }
-size_t vqvae_embed_onehot_workspace_bytes(int B, int Cout, int q, int K, int T) {
-  vqvae_conv1d_desc d = {B, q, T, Cout, T, K, 1, K - 1, 1, 0};
-  return embed_ws_conv_off(B, Cout, q, K, T) + vqvae_conv1d_workspace_bytes(&d) + 256;
-}
+size_t vqvae_embed_onehot_workspace_bytes(int B, int Cout, int q, int K, int T) { return embed_plan(B, Cout, q, K, T).total; }
 
 int vqvae_embed_onehot_fwd(const float* x, const float* W, const float* b, int B, int Cout, int q,
                            int K, int T, float* y, int32_t* idx, int32_t* flag, void* ws,
                            size_t ws_bytes, vqvae_stream_t s) {
   VQ_REQUIRE(x && W && y && idx && flag && ws && B > 0 && Cout > 0 && q > 0 && K >= 1 && T > 0, "embed_onehot_fwd: bad arguments");
-  if (ws_bytes < vqvae_embed_onehot_workspace_bytes(B, Cout, q, K, T)) { set_error("embed_onehot_fwd: workspace too small"); return VQVAE_E_WORKSPACE; }
+  const EmbedPlan p = embed_plan(B, Cout, q, K, T);
+  if (ws_bytes < p.total) { set_error("embed_onehot_fwd: workspace too small"); return VQVAE_E_WORKSPACE; }
   hipStream_t st = (hipStream_t)s;
   hipLaunchKernelGGL(set_flag_kernel, dim3(1), dim3(1), 0, st, flag, 1);
   const bool vec4 = (T % 4 == 0) && (((uintptr_t)x) % 16 == 0) && (((uintptr_t)y) % 16 == 0);
@@ -1387,10 +1392,8 @@ int vqvae_embed_onehot_fwd(const float* x, const float* W, const float* b, int B
     hipLaunchKernelGGL(embed_gather_kernel, dim3(grid_for((size_t)B * Cout * T, 256, 4096)), dim3(256), 0, st, idx, (long)T, B, T, W, b, Cout, q, K, y, (const int32_t*)flag);
   }
   VQ_LAUNCH_CHECK();
-  // ... anything else: the dense causal conv (pad K-1, cropped to T), skipped on the device when flag != 0
-  vqvae_conv1d_desc d = {B, q, T, Cout, T, K, 1, K - 1, 1, 0};
-  char* cw = (char*)ws + embed_ws_conv_off(B, Cout, q, K, T);
-  return vqvae_conv1d_fwd_cond(&d, x, W, b, y, cw, ws_bytes - (size_t)(cw - (char*)ws), flag, s);
+  // ... anything else: the dense causal conv, skipped on the device when flag != 0
+  return vqvae_conv1d_fwd_cond(&p.conv_desc, x, W, b, y, (char*)ws + p.conv, ws_bytes - p.conv, flag, s);
 }
 
 int vqvae_embed_onehot_wgrad(const float* x, const int32_t* idx, const int32_t* flag, const float* gy,
@@ -1398,9 +1401,10 @@ int vqvae_embed_onehot_wgrad(const float* x, const int32_t* idx, const int32_t* 
                              int accumulate, void* ws, size_t ws_bytes, vqvae_stream_t s) {
   VQ_REQUIRE(idx && gy && gW && ws && B > 0 && Cout > 0 && q > 0 && K >= 1 && T > 0, "embed_onehot_wgrad: bad arguments");
   VQ_REQUIRE(flag == nullptr || x != nullptr, "embed_onehot_wgrad: a flag needs the dense input for its fallback");
-  if (ws_bytes < vqvae_embed_onehot_workspace_bytes(B, Cout, q, K, T)) { set_error("embed_onehot_wgrad: workspace too small"); return VQVAE_E_WORKSPACE; }
+  const EmbedPlan p = embed_plan(B, Cout, q, K, T);
+  if (ws_bytes < p.total) { set_error("embed_onehot_wgrad: workspace too small"); return VQVAE_E_WORKSPACE; }
   hipStream_t st = (hipStream_t)s;
-  float* part = (float*)ws;
+  float* part = (float*)((char*)ws + p.part);
   const size_t lds = (size_t)4 * K * q * sizeof(float);
   VQ_REQUIRE(lds <= 64 * 1024, "embed_onehot_wgrad: K*q too large for the LDS histograms");
   const long rows = (long)B * Cout;
@@ -1413,16 +1417,12 @@ int vqvae_embed_onehot_wgrad(const float* x, const int32_t* idx, const int32_t* 
   const size_t lds_gath = (size_t)2 * (T + 4) * sizeof(float) + (((size_t)T * 2 + 15) & ~(size_t)15) + (size_t)(q + 1) * sizeof(int);
   if (K == 2 && T % 4 == 0 && T <= 65535 && q <= ES_NT && (((uintptr_t)gy) % 16 == 0) &&
       lds_sort <= 64 * 1024 && lds_gath <= 150 * 1024) {
-    unsigned short* perm = reinterpret_cast<unsigned short*>((char*)ws + embed_ws_sort_off(B, Cout, q, K));
-    int32_t* off = reinterpret_cast<int32_t*>((char*)perm + align_up((size_t)B * T * sizeof(unsigned short), 256));
+    unsigned short* perm = (unsigned short*)((char*)ws + p.perm);
+    int32_t* off = (int32_t*)((char*)ws + p.off);
     hipLaunchKernelGGL(embed_sort_kernel, dim3(B), dim3(ES_NT), lds_sort, st, idx, q, T, perm, off, flag);
     VQ_LAUNCH_CHECK();
     const int groups = (Cout + EG_ROWS - 1) / EG_ROWS;
-    static size_t lds_allowed = 64 * 1024;                 // dynamic LDS beyond 64 KB has to be asked for
-    if (lds_gath > lds_allowed) {
-      VQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(embed_gathersum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gath));
-      lds_allowed = lds_gath;
-    }
+    if (int e = lds_opt_in<embed_gathersum_kernel>(lds_gath)) return e;
     hipLaunchKernelGGL(embed_gathersum_kernel, dim3(B * groups), dim3(ES_NT), lds_gath, st, gy, B, Cout, q, T, lpc,
                        (const unsigned short*)perm, (const int32_t*)off, part, flag);
   } else
@@ -1442,9 +1442,7 @@ int vqvae_embed_onehot_wgrad(const float* x, const int32_t* idx, const int32_t* 
     VQ_LAUNCH_CHECK();
   }
   if (flag == nullptr) return 0;                          // index-fed input: there is no dense form to fall back to
-  vqvae_conv1d_desc d = {B, q, T, Cout, T, K, 1, K - 1, 1, 0};
-  char* cw = (char*)ws + embed_ws_conv_off(B, Cout, q, K, T);
-  return vqvae_conv1d_bwd_weight_cond(&d, x, gy, gW, gb, accumulate, cw, ws_bytes - (size_t)(cw - (char*)ws), flag, s);
+  return vqvae_conv1d_bwd_weight_cond(&p.conv_desc, x, gy, gW, gb, accumulate, (char*)ws + p.conv, ws_bytes - p.conv, flag, s);
 }
 
 int vqvae_concat(float* dst, const float* const* srcs, int n, size_t count, vqvae_stream_t s) {

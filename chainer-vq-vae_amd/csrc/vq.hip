@@ -990,17 +990,94 @@ static int vq_cols_per_block(int dpad) {
 
 using namespace vq;
 
-extern "C" size_t vqvae_vq_workspace_bytes(int B, int d, int T, int k) {
+// Forward workspace: wn[k] | 256 bytes of words (wmax_bits[2] at +0, nflag at +64, noverflow at +68) | flagged[N] |
+// split codebook (matmul modes 2 and 3) | candidate re-check: (min, band) and count per flagged row, VQ_CAP candidates
+// each, overflow list
+struct VqFwdPlan { size_t wn, words, flagged, wsplit, fminb, ccount, cand, overflow, total; };
+static VqFwdPlan vq_fwd_plan(int B, int d, int T, int k) {
   const size_t N = (size_t)B * T;
-  size_t fwd = align_up((size_t)k * 4, 256) + 256 /*wmax+nflag*/ + align_up(N * 4, 256) +
-               align_up((size_t)k * d * 6, 256) /*split codebook (matmul mode 2)*/ +
-               // candidate re-check: (min, band) and count per flagged row, VQ_CAP candidates each, overflow list
-               align_up(N * 8, 256) + align_up(N * 4, 256) + align_up(N * 4 * VQ_CAP, 256) + align_up(N * 4, 256);
-  // large-N codebook gradient: part64[k][SPLIT][d] | base[k+1] | cursor[nchunk][k] | sorted[N]
-  const size_t nchunk = (N + VQ_GW_CHUNK - 1) / VQ_GW_CHUNK;
-  size_t bwd = align_up((size_t)k * VQ_GW_SPLIT * d * 8, 256) + align_up(((size_t)k + 1) * 4, 256) +
-               align_up(nchunk * k * 4, 256) + align_up(N * 4, 256);
+  WsPlan w; VqFwdPlan p;
+  p.wn = w.take((size_t)k * 4);
+  p.words = w.take(256);
+  p.flagged = w.take(N * 4);
+  p.wsplit = w.take((size_t)k * d * 6);
+  p.fminb = w.take(N * 8);
+  p.ccount = w.take(N * 4);
+  p.cand = w.take(N * 4 * VQ_CAP);
+  p.overflow = w.take(N * 4);
+  p.total = w.total;
+  return p;
+}
+// large-N codebook gradient: part64[k][SPLIT][d] | base[k+1] | cursor[nchunk][k] | sorted[N]
+struct VqGradPlan { size_t nchunk, part64, base, cursor, sorted, total; };
+static VqGradPlan vq_grad_plan(int B, int d, int T, int k) {
+  const size_t N = (size_t)B * T;
+  WsPlan w; VqGradPlan p;
+  p.nchunk = (N + VQ_GW_CHUNK - 1) / VQ_GW_CHUNK;
+  p.part64 = w.take((size_t)k * VQ_GW_SPLIT * d * 8);
+  p.base = w.take(((size_t)k + 1) * 4);
+  p.cursor = w.take(p.nchunk * k * 4);
+  p.sorted = w.take(N * 4);
+  p.total = w.total;
+  return p;
+}
+
+extern "C" size_t vqvae_vq_workspace_bytes(int B, int d, int T, int k) {
+  const size_t fwd = vq_fwd_plan(B, d, T, k).total, bwd = vq_grad_plan(B, d, T, k).total;
   return (fwd > bwd ? fwd : bwd) + 256;
+}
+
+// One forward call: what every sweep and re-check launch is handed, the workspace's pieces as pointers
+struct VqFwd {
+  const float* z; const float* W; int B, d, T, k; long N; int32_t* idx; hipStream_t st;
+  float* wn; int* wmax_bits; int32_t* nflag; int32_t* noverflow; int32_t* flagged; unsigned* wsplit;
+  float* fminb; int32_t* ccount; int32_t* cand; int32_t* overflow;
+};
+
+// modes 2 and 3, d = 64 / 128: the sweep on the 16-bit matrix pipe, then (cand_path) the candidate sweep over the flagged rows
+template <int D, int NP>
+static int launch_x3(const VqFwd& a, bool cand_path) {
+  const size_t lds = 2 * NP * 64 * (size_t)(D / 8 + 1) * 16;
+  const unsigned grid = (unsigned)((a.N + 255) / 256);
+  // the candidate sweep covers at most N/8 flagged rows per launch geometry; rows beyond are re-checked in full
+  const unsigned cgrid = (unsigned)((a.N / 8 + 255) / 256);
+  if (int e = lds_opt_in<vq_mfma_x3_kernel<D, false, NP>>(lds)) return e;
+  hipLaunchKernelGGL((vq_mfma_x3_kernel<D, false, NP>), dim3(grid), dim3(512), lds, a.st, a.z, (const uint4*)a.wsplit, a.wn, a.wmax_bits, a.B, a.T, a.k, a.idx, a.flagged, a.nflag, a.fminb, a.cand, a.ccount);
+  if (cand_path) {
+    if (int e = lds_opt_in<vq_mfma_x3_kernel<D, true, NP>>(lds)) return e;
+    hipLaunchKernelGGL((vq_mfma_x3_kernel<D, true, NP>), dim3(cgrid), dim3(512), lds, a.st, a.z, (const uint4*)a.wsplit, a.wn, a.wmax_bits, a.B, a.T, a.k, a.idx, a.flagged, a.nflag, a.fminb, a.cand, a.ccount);
+  }
+  return 0;
+}
+// fp32 MFMA, d = 2 DP = 64 / 128: the latents stay in registers
+template <int DP>
+static int launch_reg(const VqFwd& a) {
+  const size_t lds = 2 * 64 * (size_t)(a.d + 1) * 4;
+  const unsigned grid = (unsigned)((a.N + 127) / 128);
+  if (int e = lds_opt_in<vq_mfma_reg_kernel<DP>>(lds)) return e;
+  hipLaunchKernelGGL(vq_mfma_reg_kernel<DP>, dim3(grid), dim3(256), lds, a.st, a.z, a.W, a.wn, a.wmax_bits, a.B, a.T, a.k, a.idx, a.flagged, a.nflag);
+  return 0;
+}
+// fp32 MFMA, any d: NW wavefronts of 32 latent columns staged in LDS (vq_cols_per_block)
+template <int NW>
+static int launch_lds(const VqFwd& a, int dpad) {
+  const int NC = 32 * NW;
+  const size_t lds = ((size_t)dpad * NC + 32 * (size_t)(dpad + 1)) * 4;
+  const unsigned grid = (unsigned)((a.N + NC - 1) / NC);
+  if (int e = lds_opt_in<vq_mfma_kernel<NW>>(lds)) return e;
+  hipLaunchKernelGGL(vq_mfma_kernel<NW>, dim3(grid), dim3(64 * NW), lds, a.st, a.z, a.W, a.wn, a.wmax_bits, a.B, a.d, a.T, a.k, dpad, a.idx, a.flagged, a.nflag);
+  return 0;
+}
+// exact re-check of the queued rows, R rows per workgroup pass
+template <int R>
+static int launch_recheck(const VqFwd& a, const int32_t* list, const int32_t* nlist) {
+  const size_t lds2 = ((size_t)R * a.d + 256 * 33 + 512) * 4;
+  if (int e = lds_opt_in<vq_exact_batched_kernel<R>>(lds2)) return e;
+  const long maxb = (a.N + R - 1) / R;
+  unsigned g2 = (unsigned)(maxb < 2048 ? maxb : 2048);
+  hipLaunchKernelGGL(vq_exact_batched_kernel<R>, dim3(g2), dim3(256), lds2, a.st, a.z, a.W, a.B, a.d, a.T, a.k, list, nlist, a.idx);
+  VQ_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int vqvae_vq_nearest_fwd(const float* z, const float* W, int B, int d, int T, int k,
@@ -1008,116 +1085,71 @@ extern "C" int vqvae_vq_nearest_fwd(const float* z, const float* W, int B, int d
                                     void* ws, size_t ws_bytes, vqvae_stream_t s) {
   VQ_REQUIRE(z && W && idx && ws, "vq_nearest_fwd: null pointer");
   VQ_REQUIRE(B > 0 && d > 0 && T > 0 && k > 0, "vq_nearest_fwd: bad dims");
-  if (ws_bytes < vqvae_vq_workspace_bytes(B, d, T, k)) { set_error("vq_nearest_fwd: workspace too small"); return VQVAE_E_WORKSPACE; }
+  const VqFwdPlan p = vq_fwd_plan(B, d, T, k);
+  if (ws_bytes < p.total) { set_error("vq_nearest_fwd: workspace too small"); return VQVAE_E_WORKSPACE; }
   hipStream_t st = (hipStream_t)s;
   const long N = (long)B * T;
   char* wp = (char*)ws;
-  float* wn = (float*)wp; wp += align_up((size_t)k * 4, 256);
-  int* wmax_bits = (int*)wp;
-  int32_t* nflag = (int32_t*)(wp + 64); wp += 256;
-  int32_t* flagged = (int32_t*)wp; wp += align_up((size_t)N * 4, 256);
-  unsigned* wsplit = (unsigned*)wp; wp += align_up((size_t)k * d * 6, 256);
-  float* fminb = (float*)wp; wp += align_up((size_t)N * 8, 256);
-  int32_t* ccount = (int32_t*)wp; wp += align_up((size_t)N * 4, 256);
-  int32_t* cand = (int32_t*)wp; wp += align_up((size_t)N * 4 * VQ_CAP, 256);
-  int32_t* overflow = (int32_t*)wp;
-  int32_t* noverflow = nflag + 1;
+  VqFwd a = {z, W, B, d, T, k, N, idx, st};
+  a.wn = (float*)(wp + p.wn);
+  a.wmax_bits = (int*)(wp + p.words);
+  a.nflag = (int32_t*)(wp + p.words + 64);
+  a.noverflow = a.nflag + 1;
+  a.flagged = (int32_t*)(wp + p.flagged);
+  a.wsplit = (unsigned*)(wp + p.wsplit);
+  a.fminb = (float*)(wp + p.fminb);
+  a.ccount = (int32_t*)(wp + p.ccount);
+  a.cand = (int32_t*)(wp + p.cand);
+  a.overflow = (int32_t*)(wp + p.overflow);
   bool cand_path = false;
   ProfScope ps(VQVAE_PROF_VQ_NEAREST, st);
   if (mode == 0) {
     const int dpad = (d + 1) / 2 * 2;
     const int nw = vq_cols_per_block(dpad);
     VQ_REQUIRE(nw > 0, "vq_nearest_fwd: d=%d too large for the LDS-staged MFMA path (max ~1000)", d);
-    VQ_CHECK_HIP(hipMemsetAsync(wmax_bits, 0, 256, st));
+    VQ_CHECK_HIP(hipMemsetAsync(a.wmax_bits, 0, 256, st));
     // mode 3: three fp16 products (mode 2: six bf16 products)
     const bool x2 = (d == 64 || d == 128) && vqvae_get_matmul_dtype() == 3;
-    if (x2) hipLaunchKernelGGL(vq_wnorm_elt_lds_kernel, dim3(cdiv(k, 64)), dim3(64), (size_t)64 * (d + 1) * 4, st, W, k, d, wn, wmax_bits);      // (x2: d is 64 or 128)
-    else hipLaunchKernelGGL(vq_wnorm_kernel, dim3(cdiv(k, 256)), dim3(256), 0, st, W, k, d, wn, wmax_bits);
+    if (x2) hipLaunchKernelGGL(vq_wnorm_elt_lds_kernel, dim3(cdiv(k, 64)), dim3(64), (size_t)64 * (d + 1) * 4, st, W, k, d, a.wn, a.wmax_bits);      // (x2: d is 64 or 128)
+    else hipLaunchKernelGGL(vq_wnorm_kernel, dim3(cdiv(k, 256)), dim3(256), 0, st, W, k, d, a.wn, a.wmax_bits);
     VQ_LAUNCH_CHECK();
+    int err = 0;
     if ((d == 64 || d == 128) && vqvae_get_matmul_dtype() >= 2) {      // modes 2 and 3: the sweep on the 16-bit matrix pipe
       int nb = (int)(((long)k * d / 2 + 255) / 256);
       if (nb > 2048) nb = 2048;
-      if (x2) hipLaunchKernelGGL(vq_wsplit2_kernel, dim3(nb), dim3(256), 0, st, W, k, d, wmax_bits, wsplit);
-      else hipLaunchKernelGGL(vq_wsplit_kernel, dim3(nb), dim3(256), 0, st, W, k, d, wsplit);
+      if (x2) hipLaunchKernelGGL(vq_wsplit2_kernel, dim3(nb), dim3(256), 0, st, W, k, d, a.wmax_bits, a.wsplit);
+      else hipLaunchKernelGGL(vq_wsplit_kernel, dim3(nb), dim3(256), 0, st, W, k, d, a.wsplit);
       VQ_LAUNCH_CHECK();
-      const size_t lds = 2 * (x2 ? 2 : 3) * 64 * (size_t)(d / 8 + 1) * 16;
-      const unsigned grid = (unsigned)((N + 255) / 256);
       // the candidate pass pays when re-checking a row against all k codes costs more than sweeping it again
       cand_path = k >= 1024 && N >= 1024;      // (round 5: N = 1920 at k = 8192 1.49 -> 1.32 ms with it; from N = 4096 until then)
-      // the candidate sweep covers at most N/8 flagged rows per launch geometry; rows beyond are re-checked in full
-      const unsigned cgrid = (unsigned)((N / 8 + 255) / 256);
-      if (cand_path) VQ_CHECK_HIP(hipMemsetAsync(ccount, 0, (size_t)N * 4, st));
-#define VQ_X3_LAUNCH(Dv, NPv)                                                                                   \
-      {                                                                                                         \
-        VQ_CHECK_HIP(hipFuncSetAttribute((const void*)vq_mfma_x3_kernel<Dv, false, NPv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((vq_mfma_x3_kernel<Dv, false, NPv>), dim3(grid), dim3(512), lds, st, z, (const uint4*)wsplit, wn, wmax_bits, B, T, k, idx, flagged, nflag, fminb, cand, ccount); \
-        if (cand_path) {                                                                                        \
-          VQ_CHECK_HIP(hipFuncSetAttribute((const void*)vq_mfma_x3_kernel<Dv, true, NPv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-          hipLaunchKernelGGL((vq_mfma_x3_kernel<Dv, true, NPv>), dim3(cgrid), dim3(512), lds, st, z, (const uint4*)wsplit, wn, wmax_bits, B, T, k, idx, flagged, nflag, fminb, cand, ccount); \
-        }                                                                                                       \
-      }
-      if (d == 64) { if (x2) VQ_X3_LAUNCH(64, 2) else VQ_X3_LAUNCH(64, 3) }
-      else { if (x2) VQ_X3_LAUNCH(128, 2) else VQ_X3_LAUNCH(128, 3) }
-#undef VQ_X3_LAUNCH
-      VQ_LAUNCH_CHECK();
+      if (cand_path) VQ_CHECK_HIP(hipMemsetAsync(a.ccount, 0, (size_t)N * 4, st));
+      if (d == 64) err = x2 ? launch_x3<64, 2>(a, cand_path) : launch_x3<64, 3>(a, cand_path);
+      else err = x2 ? launch_x3<128, 2>(a, cand_path) : launch_x3<128, 3>(a, cand_path);
     } else if (d == 64 || d == 128) {
-      const size_t lds = 2 * 64 * (size_t)(d + 1) * 4;
-      const unsigned grid = (unsigned)((N + 127) / 128);
-      if (d == 64) {
-        VQ_CHECK_HIP(hipFuncSetAttribute((const void*)vq_mfma_reg_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(vq_mfma_reg_kernel<32>, dim3(grid), dim3(256), lds, st, z, W, wn, wmax_bits, B, T, k, idx, flagged, nflag);
-      } else {
-        VQ_CHECK_HIP(hipFuncSetAttribute((const void*)vq_mfma_reg_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(vq_mfma_reg_kernel<64>, dim3(grid), dim3(256), lds, st, z, W, wn, wmax_bits, B, T, k, idx, flagged, nflag);
-      }
-      VQ_LAUNCH_CHECK();
+      err = d == 64 ? launch_reg<32>(a) : launch_reg<64>(a);
     } else {
-    const int NC = 32 * nw;
-    const size_t lds = ((size_t)dpad * NC + 32 * (size_t)(dpad + 1)) * 4;
-    const unsigned grid = (unsigned)((N + NC - 1) / NC);
-    if (nw == 4) {
-      VQ_CHECK_HIP(hipFuncSetAttribute((const void*)vq_mfma_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(vq_mfma_kernel<4>, dim3(grid), dim3(256), lds, st, z, W, wn, wmax_bits, B, d, T, k, dpad, idx, flagged, nflag);
-    } else if (nw == 2) {
-      VQ_CHECK_HIP(hipFuncSetAttribute((const void*)vq_mfma_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(vq_mfma_kernel<2>, dim3(grid), dim3(128), lds, st, z, W, wn, wmax_bits, B, d, T, k, dpad, idx, flagged, nflag);
-    } else {
-      VQ_CHECK_HIP(hipFuncSetAttribute((const void*)vq_mfma_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(vq_mfma_kernel<1>, dim3(grid), dim3(64), lds, st, z, W, wn, wmax_bits, B, d, T, k, dpad, idx, flagged, nflag);
+      err = nw == 4 ? launch_lds<4>(a, dpad) : nw == 2 ? launch_lds<2>(a, dpad) : launch_lds<1>(a, dpad);
     }
+    if (err) return err;
     VQ_LAUNCH_CHECK();
-    }
-    const int32_t* list = flagged;
-    const int32_t* nlist = nflag;
+    const int32_t* list = a.flagged;
+    const int32_t* nlist = a.nflag;
     if (cand_path) {
       // flagged rows: the listed candidates only; rows with too many candidates (or beyond the candidate
       // sweep's reach, which left their count at 0) fall through to the all-codes re-check below
-      hipLaunchKernelGGL(vq_exact_cand_kernel, dim3(1024), dim3(256), 0, st, z, W, d, T, flagged, nflag, cand, ccount, idx, overflow, noverflow);
+      hipLaunchKernelGGL(vq_exact_cand_kernel, dim3(1024), dim3(256), 0, st, z, W, d, T, a.flagged, a.nflag, a.cand, a.ccount, idx, a.overflow, a.noverflow);
       VQ_LAUNCH_CHECK();
-      list = overflow; nlist = noverflow;
+      list = a.overflow; nlist = a.noverflow;
     }
     if (N > 8192) {
-      // exact re-check of the queued rows, 8 rows per workgroup pass
-      constexpr int R = 8;
-      const size_t lds2 = ((size_t)R * d + 256 * 33 + 512) * 4;
-      VQ_CHECK_HIP(hipFuncSetAttribute((const void*)vq_exact_batched_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-      const long maxb = (N + R - 1) / R;
-      unsigned g2 = (unsigned)(maxb < 2048 ? maxb : 2048);
-      hipLaunchKernelGGL(vq_exact_batched_kernel<R>, dim3(g2), dim3(256), lds2, st, z, W, B, d, T, k, list, nlist, idx);
-      VQ_LAUNCH_CHECK();
+      if (int e2 = launch_recheck<8>(a, list, nlist)) return e2;
     } else {
       // the training shapes (a few thousand rows, a few dozen of them queued): the launch is one workgroup's chain of 64 d
       // dependent roundings per row set -- two rows per workgroup spread it over four times the workgroups (38 -> ~12 us at
       // configs[1], in front of the condition embed); the per-row arithmetic, hence the index, is the same
-      constexpr int R = 2;
-      const size_t lds2 = ((size_t)R * d + 256 * 33 + 512) * 4;
-      VQ_CHECK_HIP(hipFuncSetAttribute((const void*)vq_exact_batched_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-      const long maxb = (N + R - 1) / R;
-      unsigned g2 = (unsigned)(maxb < 2048 ? maxb : 2048);
-      hipLaunchKernelGGL(vq_exact_batched_kernel<R>, dim3(g2), dim3(256), lds2, st, z, W, B, d, T, k, list, nlist, idx);
-      VQ_LAUNCH_CHECK();
+      if (int e2 = launch_recheck<2>(a, list, nlist)) return e2;
     }
-    if (n_rechecked) VQ_CHECK_HIP(hipMemcpyAsync(n_rechecked, nflag, 4, hipMemcpyDeviceToDevice, st));
+    if (n_rechecked) VQ_CHECK_HIP(hipMemcpyAsync(n_rechecked, a.nflag, 4, hipMemcpyDeviceToDevice, st));
   } else {
     const size_t lds2 = ((size_t)d + 512) * 4;
     unsigned g2 = (unsigned)(N < 65535 ? N : 65535);
@@ -1131,7 +1163,7 @@ extern "C" int vqvae_vq_nearest_fwd(const float* z, const float* W, int B, int d
     int nb = (int)((total + 255) / 256);
     if (nb > 4096) nb = 4096;
     // (the training shape's 1 920 rows: one launch of the plain kernel is all latency; d <= 254: the tile's 64 (d + 1) floats stay
-    //  inside the 64 KB of dynamic LDS a launch gets without hipFuncSetAttribute -- wider codes take the plain kernel)
+    //  inside the 64 KB of dynamic LDS a launch gets without lds_opt_in -- wider codes take the plain kernel)
     if ((long)B * T >= 16384 && d <= 254 && B <= 65535)
       hipLaunchKernelGGL(vq_gather_tile_kernel, dim3((T + 63) / 64, B), dim3(256), (size_t)64 * (d + 1) * 4, st, W, idx, B, d, T, e);
     else
@@ -1153,13 +1185,13 @@ extern "C" int vqvae_vq_grad_w(const int32_t* idx, const float* gy, int B, int d
   }
   const long N = (long)B * T;
   VQ_REQUIRE(N < (1L << 31), "vq_grad_w: B*T too large");
-  if (ws_bytes < vqvae_vq_workspace_bytes(B, d, T, k)) { set_error("vq_grad_w: workspace too small"); return VQVAE_E_WORKSPACE; }
-  const int nchunk = (int)((N + VQ_GW_CHUNK - 1) / VQ_GW_CHUNK);
-  char* wp = (char*)ws;
-  double* part64 = (double*)wp; wp += align_up((size_t)k * VQ_GW_SPLIT * d * 8, 256);
-  int32_t* base = (int32_t*)wp; wp += align_up(((size_t)k + 1) * 4, 256);
-  int32_t* cursor = (int32_t*)wp; wp += align_up((size_t)nchunk * k * 4, 256);
-  int32_t* sorted = (int32_t*)wp;
+  const VqGradPlan p = vq_grad_plan(B, d, T, k);
+  if (ws_bytes < p.total) { set_error("vq_grad_w: workspace too small"); return VQVAE_E_WORKSPACE; }
+  const int nchunk = (int)p.nchunk;
+  double* part64 = (double*)((char*)ws + p.part64);
+  int32_t* base = (int32_t*)((char*)ws + p.base);
+  int32_t* cursor = (int32_t*)((char*)ws + p.cursor);
+  int32_t* sorted = (int32_t*)((char*)ws + p.sorted);
   VQ_CHECK_HIP(hipMemsetAsync(cursor, 0, (size_t)nchunk * k * 4, st));
   hipLaunchKernelGGL(vq_gw_hist_kernel, dim3(nchunk), dim3(256), 0, st, idx, N, k, cursor);
   VQ_LAUNCH_CHECK();
