@@ -242,6 +242,20 @@ VQ_EMA_PIECE = 512                # VQVAE_VQ_EMA_PIECE
 VQ_EMA_SMALL_MAX_N = 4096         # VQVAE_VQ_EMA_SMALL_MAX_N
 VQ_EMA_MAX_N = 1 << 24            # VQVAE_VQ_EMA_MAX_N
 
+# include/vqvae_kmeans.h: k-means initialisation of the codebook, a fourth table and version
+KMEANS_PROTOTYPES = {
+    'vqvae_kmeans_abi_version': (c_int, []),
+    'vqvae_kmeans_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'vqvae_kmeans_collect': (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, P]),
+    'vqvae_kmeans_seed': (c_int, [P, c_int, c_int, c_int, C.c_uint64, P, P, P, P, c_size_t, P]),
+    'vqvae_kmeans_update': (c_int, [P, c_int, c_int, c_int, P, C.c_uint64, c_int, P, P, P]),
+    'vqvae_kmeans_inertia': (c_int, [P, P, P, c_int, c_int, c_int, P, P, c_size_t, P]),
+}
+KMEANS_ABI_VERSION = 1            # vqvae_kmeans_abi_version()
+KMEANS_BLOCK = 256                # VQVAE_KMEANS_BLOCK
+KMEANS_MAX_N = 1 << 24            # VQVAE_KMEANS_MAX_N
+KMEANS_MAX_D = 4096               # VQVAE_KMEANS_MAX_D
+
 # elementwise op codes / profiler tags (mirror the header)
 MAX_STACK_GROUP = 24              # blocks per resstack call (MAXSEG in csrc/gemm_common.h)
 STORE_X_BF16, STORE_RES_BF16 = 2, 4
@@ -284,7 +298,7 @@ def load():
     # Must be in the environment before the HSA runtime initialises (first HIP call).
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     lib = C.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES):
+    for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES, KMEANS_PROTOTYPES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)           # AttributeError if the symbol is missing
             fn.restype = res
@@ -298,6 +312,9 @@ def load():
     if lib.vqvae_vq_ema_abi_version() != VQ_EMA_ABI_VERSION:
         raise ImportError('libvqvae_hip.so at %s has EMA-codebook ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
                           % (LIB_PATH, lib.vqvae_vq_ema_abi_version(), VQ_EMA_ABI_VERSION))
+    if lib.vqvae_kmeans_abi_version() != KMEANS_ABI_VERSION:
+        raise ImportError('libvqvae_hip.so at %s has k-means ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
+                          % (LIB_PATH, lib.vqvae_kmeans_abi_version(), KMEANS_ABI_VERSION))
     _lib = lib
     return lib
 
