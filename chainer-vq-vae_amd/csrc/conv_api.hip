@@ -658,7 +658,7 @@ static RbLayout rb_layout(const vqvae_resblock_desc* d) {
   return L;
 }
 
-// (The same predicate also stores the gate tensors [tanh | sigmoid] as bf16 in that mode -- GemmArgs::g16: there the
+// (The same predicate also stores the gate tensors [tanh | sigmoid] as bf16 in that mode -- RbFmt::gates: there the
 // backward pass differentiates the ROUNDED gates, which the oracle's bf16 mode mirrors: configs[4]'s "bf16" taken one
 // step further than operand rounding, 63 MB less written and 63 MB less read per block.)
 // z (B, Cd/2, T) is read only through GEMM staging (res 1x1, skip sum, res / skip weight gradients).  In matmul
@@ -670,18 +670,14 @@ static bool z_bf16(const vqvae_resblock_desc* d) {
          (long)d->B * (d->Cr > d->Cs ? d->Cr : d->Cs) * d->T * 4 < (1L << 31);     // the bf16-reading kernels address with 32-bit offsets
 }
 
-static bool gates_bf16(const vqvae_resblock_desc* d) {
-  return z_bf16(d);
-}
-
 // gh = [ga; gb] (B, Cd, T) stored as bf16 (vqvae_resblock_desc::storage & VQVAE_STORE_GH_BF16): the same blocks, on
 // the caller's request.
 static int bf16_storage_supported(const vqvae_resblock_desc* d) {
   int m = 0;
-  if (gates_bf16(d) && d->K == 2 && d->Cd == 256) m |= VQVAE_STORE_GH_BF16;
+  if (z_bf16(d) && d->K == 2 && d->Cd == 256) m |= VQVAE_STORE_GH_BF16;
   // (the gate GEMM reads a bf16 x in its 256 x 128-tile two-tap form only: not offered when an A/B switch turns that form off)
-  if (lin128_tile() && x3_lean_enabled() && gates_bf16(d) && d->K == 2 && d->Cd == 256 && d->T % 128 == 0) m |= VQVAE_STORE_X_BF16 | VQVAE_STORE_RES_BF16;
-  if (gates_bf16(d) && d->K == 2 && d->Cd == 256 && d->Cs == d->Cr && d->T % 128 == 0) m |= VQVAE_STORE_GX_BF16 | VQVAE_STORE_GRES_BF16;
+  if (lin128_tile() && x3_lean_enabled() && z_bf16(d) && d->K == 2 && d->Cd == 256 && d->T % 128 == 0) m |= VQVAE_STORE_X_BF16 | VQVAE_STORE_RES_BF16;
+  if (z_bf16(d) && d->K == 2 && d->Cd == 256 && d->Cs == d->Cr && d->T % 128 == 0) m |= VQVAE_STORE_GX_BF16 | VQVAE_STORE_GRES_BF16;
   return m;
 }
 
@@ -715,6 +711,38 @@ static int check_rb(const vqvae_resblock_desc* d) {
   VQ_REQUIRE(d->K >= 1 && d->K <= MAXTAPS, "resblock: filter_size %d unsupported", d->K);
   VQ_REQUIRE(d->dil >= 1, "resblock: bad dilation");
   return 0;
+}
+
+// How every tensor of a block is stored (Fmt) -- the one reader of desc.storage behind check_rb, and of z_bf16 behind the
+// *_storage queries; gsig: VQVAE_STORE_GATES_SIG.  `uses`: the RB_* tensors whose bits bind this entry point (the others
+// come out fp32: a backward call carries the forward's bits too); `absent`: those of them the call has no pointer for (fp32
+// as well).  A bf16 bit in `uses` needs the packed chain form, a pre-split one its float32x2 launches (f16) with the scale
+// words of what they store (am; NULL: the entry point neither packs nor publishes, its launch checks the rest).
+constexpr int RB_X = VQVAE_STORE_X_BF16 | VQVAE_STORE_X_F16X2, RB_RES = VQVAE_STORE_RES_BF16 | VQVAE_STORE_RES_F16X2,
+              RB_GH = VQVAE_STORE_GH_BF16 | VQVAE_STORE_GH_F16X2, RB_GRES = VQVAE_STORE_GRES_BF16, RB_GX = VQVAE_STORE_GX_BF16,
+              RB_ALL_BF16 = VQVAE_STORE_X_BF16 | VQVAE_STORE_RES_BF16 | VQVAE_STORE_GH_BF16 | VQVAE_STORE_GRES_BF16 | VQVAE_STORE_GX_BF16,
+              RB_ALL_F16X2 = VQVAE_STORE_X_F16X2 | VQVAE_STORE_RES_F16X2 | VQVAE_STORE_GH_F16X2;
+struct RbFmt { Fmt x, res, z, gates, gh, g_res, gx; int gsig; };
+static int rb_formats(const vqvae_resblock_desc* d, int uses, int absent, bool packed, bool f16, const vqvae_resblock_amax* am, RbFmt& f) {
+  const int bound = d->storage & uses, s = bound & ~absent;
+  VQ_REQUIRE(!(bound & RB_ALL_BF16) || packed, "resblock: bf16-stored tensors (desc.storage) are kept by the packed chain form only");
+  VQ_REQUIRE(!(bound & RB_ALL_F16X2) || f16, "resblock: pre-split tensors (desc.storage) are kept by the packed float32x2 chain only");
+  auto fmt = [s](int bits) { return (s & bits & RB_ALL_BF16) ? FMT_BF16 : ((s & bits & RB_ALL_F16X2) ? FMT_F16X2 : FMT_F32); };
+  f.x = fmt(RB_X); f.res = fmt(RB_RES); f.gh = fmt(RB_GH); f.g_res = fmt(RB_GRES); f.gx = fmt(RB_GX);
+  f.z = f.gates = z_bf16(d) ? FMT_BF16 : FMT_F32;
+  f.gsig = (d->storage & VQVAE_STORE_GATES_SIG) ? 1 : 0;
+  VQ_REQUIRE(f.x == FMT_F32 || !(uses & RB_RES) || (absent & RB_RES) || f.res == f.x, "resblock_fwd: a stored x with an fp32 residual output is not built");
+  if (am) {
+    VQ_REQUIRE(f.res != FMT_F16X2 || (am->x_max && am->res_scale), "resblock_fwd: a pre-split residual output needs amax->x_max and amax->res_scale");
+    VQ_REQUIRE(f.gh != FMT_F16X2 || am->gh_scale, "resblock_bwd: a pre-split gh needs amax->gh_scale");
+  }
+  return 0;
+}
+// ... for the entry points that only READ stored tensors (nothing above can fail: their launches check what they are given)
+static RbFmt rb_formats(const vqvae_resblock_desc* d, int uses) {
+  RbFmt f;
+  rb_formats(d, uses, 0, true, true, nullptr, f);
+  return f;
 }
 }  // namespace
 
@@ -789,16 +817,8 @@ static int resblock_fwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
   const int Mo = (res ? d->Cr : 0) + (skip ? d->Cs : 0);
   const int ldo = pad128(Mo > 0 ? Mo : 1);
   if (packed) VQ_REQUIRE(cproj && !skip, "resblock_fwd_packed: the packed form serves ResidualNet's chain (latent-rate condition, no per-block skip)");
-  const bool xpre = (d->storage & VQVAE_STORE_X_F16X2) != 0, rpre = res && (d->storage & VQVAE_STORE_RES_F16X2);
-  if (d->storage & (VQVAE_STORE_X_F16X2 | VQVAE_STORE_RES_F16X2)) {
-    VQ_REQUIRE(f16, "resblock_fwd: a pre-split residual stream (desc.storage) is kept by the packed float32x2 chain only");
-    VQ_REQUIRE(!xpre || res == nullptr || rpre, "resblock_fwd: a pre-split x with an fp32 residual output is not built");
-    VQ_REQUIRE(!rpre || (am->x_max && am->res_scale), "resblock_fwd: a pre-split residual output needs amax->x_max and amax->res_scale");
-  }
-  if (d->storage & (VQVAE_STORE_X_BF16 | VQVAE_STORE_RES_BF16)) {
-    VQ_REQUIRE(packed, "resblock_fwd: a bf16 residual stream (desc.storage) is kept by the packed chain form only");
-    VQ_REQUIRE(!(d->storage & VQVAE_STORE_X_BF16) || res == nullptr || (d->storage & VQVAE_STORE_RES_BF16), "resblock_fwd: a bf16 x with an fp32 residual output is not built");
-  }
+  RbFmt f;
+  if (int e = rb_formats(d, RB_X | RB_RES, res ? 0 : RB_RES, packed != nullptr, f16, am, f)) return e;
 
   PackArgs pa; pa.njob = 0;
   if (!packed) {
@@ -824,6 +844,7 @@ static int resblock_fwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
     for (int j = 0; j < d->K; ++j) {
       Seg& sg = g.seg[j];
       seg_stride1(sg, x, d->Cr, T, -(d->K - 1 - j) * d->dil, w + L.pk_d + (size_t)j * rp * ldd, ldd);
+      sg.fmt = f.x;                                // (pre-split: amax->x holds its scale words)
       if (f16) { sg.amax = am->x; sg.wamax = hdr_words(w, L, HDR_D); }
     }
     g.f16x2 = f16 ? 1 : 0;
@@ -840,11 +861,8 @@ static int resblock_fwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
     g.out[0].bias2 = cproj ? nullptr : p->bc;
     g.out[0].rows = d->Cd;
     g.out[1].y = z; g.out[1].y_bstride = (long)Ch * T;
-    g.z16 = z_bf16(d) ? 1 : 0;
-    g.g16 = gates_bf16(d) ? 1 : 0;
-    g.gsig = (d->storage & VQVAE_STORE_GATES_SIG) ? 1 : 0;
-    g.x16 = (d->storage & VQVAE_STORE_X_BF16) ? 3 : 0;
-    if (xpre) g.x16 = 3;                         // both taps read the pre-split x_l; amax->x holds its scale words
+    g.out[0].y_fmt = f.gates; g.out[1].y_fmt = f.z;
+    g.gsig = f.gsig;
     if (int e = launch_gemm<EPI_GATE>(g, VQVAE_PROF_RESBLOCK_GATE, st)) return e;
   }
   // K2: [res; skip] = [Wr; Ws] z (+ x) (+= skip)
@@ -853,6 +871,7 @@ static int resblock_fwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
     g.nseg = 1;
     Seg& sg = g.seg[0];
     seg_stride1(sg, z, Ch, T, 0, w + L.pk_o, ldo);
+    sg.fmt = f.z;
     if (f16) { sg.amax_static = 1.f; sg.wamax = hdr_words(w, L, HDR_O); g.f16x2 = 1; }   // |z| = |tanh * sigmoid| <= 1
     g.M = Mo; g.Tout = T; g.B = d->B;
     int o = 0;
@@ -860,17 +879,14 @@ static int resblock_fwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
       g.out[0].y = res; g.out[0].y_bstride = (long)d->Cr * T; g.out[0].rows = d->Cr;
       g.out[0].add = x; g.out[0].add_bstride = (long)d->Cr * T; g.out[0].bias = p->br;
       g.out[0].amax_out = am ? am->res : nullptr;
+      g.out[0].add_fmt = f.x; g.out[0].y_fmt = f.res;
       o = 1;
     }
     if (skip) {
       g.out[o].y = skip; g.out[o].y_bstride = (long)d->Cs * T; g.out[o].rows = d->Cs;
       g.out[o].bias = p->bs; g.out[o].accumulate = skip_accumulate;
     }
-    g.z16 = z_bf16(d) ? 1 : 0;
-    g.add16 = (res && (d->storage & VQVAE_STORE_X_BF16)) ? 1 : 0;
-    g.y16 = (res && (d->storage & VQVAE_STORE_RES_BF16)) ? 1 : 0;
-    if (rpre) {
-      g.add16 = xpre ? 1 : 0; g.y16 = 1;
+    if (f.res == FMT_F16X2) {
       g.add_scale = am->x; g.add_amax = am->x_max; g.scale_out = am->res_scale;
       g.bound_l1 = w + L.hdr + HDR_L1;
       if (cproj && cproj->P_amax) {          // the next block's gate GEMM adds its condition as a K step: leave it room
@@ -878,7 +894,6 @@ static int resblock_fwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
         g.floor_w = hdr_words(w + (L.slabs - L.pk_d), L, HDR_D);      // the next block's slice of the packed slabs
       }
     }
-    if (g.add16 || g.y16) VQ_REQUIRE(!skip, "resblock_fwd: a bf16 residual stream (desc.storage) is served by the chain form only (no per-block skip output)");
     if (int e = launch_gemm<EPI_LINEAR>(g, VQVAE_PROF_RESBLOCK_OUT, st)) return e;
   }
   return 0;
@@ -981,12 +996,8 @@ static int resblock_bwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
   // packed slabs (vqvae_resstack_pack): only the pk_* offsets are read through wpk
   float* wpk = packed ? const_cast<float*>(packed) - L.pk_d : w;
   if (packed) VQ_REQUIRE(!gcond && gh_out, "resblock_bwd_packed: the packed form serves ResidualNet's chain (no per-block condition gradient, gh kept)");
-  const bool h16 = (d->storage & VQVAE_STORE_GH_BF16) != 0;
-  const bool gres16 = g_res && (d->storage & VQVAE_STORE_GRES_BF16), gx16 = gx && (d->storage & VQVAE_STORE_GX_BF16);
-  if (h16 || (d->storage & (VQVAE_STORE_GRES_BF16 | VQVAE_STORE_GX_BF16)))
-    VQ_REQUIRE(packed, "resblock_bwd: bf16-stored gh / gradient stream (desc.storage) are kept by the packed chain form only");
-  const bool hpre = (d->storage & VQVAE_STORE_GH_F16X2) != 0;
-  if (hpre) VQ_REQUIRE(f16 && am->gh_scale, "resblock_bwd: a pre-split gh (desc.storage) is kept by the packed float32x2 chain only and needs amax->gh_scale");
+  RbFmt f;
+  if (int e = rb_formats(d, RB_GH | RB_GRES | RB_GX, (g_res ? 0 : RB_GRES) | (gx ? 0 : RB_GX), packed != nullptr, f16, am, f)) return e;
 
   if (!packed) {
   PackArgs pa; pa.njob = 0;
@@ -1004,6 +1015,7 @@ static int resblock_bwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
     if (g_res) {
       Seg& sg = g.seg[n++];
       seg_stride1(sg, g_res, d->Cr, T, 0, wpk + L.pk_gz_r, ldz);
+      sg.fmt = f.g_res;
       if (f16) { sg.amax = am->g_res; sg.wamax = hdr_words(wpk, L, HDR_GZ_R); }
     }
     Seg& ss = g.seg[n++];
@@ -1015,14 +1027,12 @@ static int resblock_bwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
     g.out[0].y = gh; g.out[0].y_bstride = (long)d->Cd * T; g.out[0].rows = Ch;
     g.out[0].add = gates; g.out[0].add_bstride = (long)d->Cd * T;
     g.out[0].amax_out = am ? am->gh : nullptr;
-    g.g16 = gates_bf16(d) ? 1 : 0;
-    if (d->storage & VQVAE_STORE_GATES_SIG) { g.gsig = 1; g.zsrc = z; }
-    g.h16 = (h16 || hpre) ? 1 : 0;
-    g.x16 = gres16 ? 1 : 0;                       // segment 0 = g_res
+    g.out[0].add_fmt = f.gates; g.out[0].y_fmt = f.gh;
+    if (f.gsig) { g.gsig = 1; g.zsrc = z; }
     if (f16 && am->pb_part) {                     // the latent pull-back of gh in this launch's epilogue
       g.pb_part = am->pb_part; g.lerp.v0 = am->pb_v0; g.lerp.w0 = am->pb_w0; g.lerp.w1 = am->pb_w1; g.lerp.Tl = am->pb_Tl;
     }
-    if (hpre) {                                   // bound: out[1] max|g_res| + out[2] max|g_skip| (wl1_kernel), segment order [g_res,] g_skip
+    if (f.gh == FMT_F16X2) {                      // bound: out[1] max|g_res| + out[2] max|g_skip| (wl1_kernel), segment order [g_res,] g_skip
       g.bound_l1 = wpk + L.hdr + HDR_L1 + (g_res ? 1 : 2);
       g.scale_out = am->gh_scale;
     }
@@ -1036,15 +1046,15 @@ static int resblock_bwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
     for (int j = 0; j < d->K; ++j) {
       Seg& sg = g.seg[j];
       seg_stride1(sg, gh, d->Cd, T, (d->K - 1 - j) * d->dil, wpk + L.pk_bd + (size_t)j * rp * ldr, ldr);
-      if (f16) { sg.amax = hpre ? am->gh_scale : am->gh; sg.wamax = hdr_words(wpk, L, HDR_BD); }
+      sg.fmt = f.gh;
+      if (f16) { sg.amax = f.gh == FMT_F16X2 ? am->gh_scale : am->gh; sg.wamax = hdr_words(wpk, L, HDR_BD); }
     }
     g.f16x2 = f16 ? 1 : 0;
     g.M = d->Cr; g.Tout = T; g.B = d->B;
     g.out[0].y = gx; g.out[0].y_bstride = (long)d->Cr * T; g.out[0].rows = d->Cr;
     g.out[0].add = g_res; g.out[0].add_bstride = (long)d->Cr * T;
     g.out[0].amax_out = am ? am->gx : nullptr;
-    g.x16 = (h16 || hpre) ? 3 : 0;
-    g.add16 = gres16 ? 1 : 0; g.y16 = gx16 ? 1 : 0;
+    g.out[0].add_fmt = f.g_res; g.out[0].y_fmt = f.gx;
     if (int e = launch_gemm<EPI_LINEAR>(g, VQVAE_PROF_RESBLOCK_BWD_GX, st)) return e;
   }
   // K5: gcond (+)= Wc^T gh
@@ -1094,7 +1104,7 @@ static int resblock_bwd_impl(const vqvae_resblock_desc* d, const vqvae_resblock_
     wseg_stride1(sg, z, Ch, T, 0);
     sg.gw = gW; sg.gw_co_stride = Ch; sg.gw_ci_stride = 1;
     wa.seg[0].gb = gb; wa.accumulate = grads_accumulate;
-    wa.x16 = z_bf16(d) ? 1 : 0;
+    wa.x_fmt = f.z;
     if (int e = launch_wgrad(wa, which ? L.p_s : L.p_r, w + L.slabs, VQVAE_PROF_RESBLOCK_WGRAD, st)) return e;
   }
   return 0;
@@ -1234,11 +1244,13 @@ static int resstack_skip_impl(const vqvae_resblock_desc* d, int nblocks, const f
     VQ_LAUNCH_CHECK();
   }
   if (!(stage & 2)) return 0;
+  const RbFmt f = rb_formats(d, 0);
   GemmArgs g; memset(&g, 0, sizeof(g));
   g.nseg = nblocks;
   for (int l = 0; l < nblocks; ++l) {
     Seg& sg = g.seg[l];
     seg_stride1(sg, z[l], Ch, T, 0, (float*)((char*)ws + l * sp.slab_bytes), ld);
+    sg.fmt = f.z;
     if (f16) { sg.amax_static = 1.f; sg.wamax = wam + l * AMAX_SLOTS; }
   }
   g.f16x2 = f16 ? 1 : 0;
@@ -1248,7 +1260,6 @@ static int resstack_skip_impl(const vqvae_resblock_desc* d, int nblocks, const f
   g.out[0].accumulate = accumulate;
   g.out[0].relu = relu ? 1 : 0;                  // the F.relu behind ResidualNet (modules.py:158) in this epilogue: one pass over (B, Cs, T) less
   g.out[0].amax_out = skip_amax_out;
-  g.z16 = z_bf16(d) ? 1 : 0;
   g.x_nt = X3_SKIP_X_NT;
   return launch_gemm<EPI_LINEAR>(g, VQVAE_PROF_RESSTACK_SKIP, st);
 }
@@ -1260,7 +1271,7 @@ extern "C" int vqvae_resstack_gcond_bwd(const vqvae_resblock_desc* d, int nblock
   if (int e = check_rb(d)) return e;
   VQ_REQUIRE(nblocks >= 1 && nblocks <= MAXSEG, "resstack_gcond_bwd: 1..%d blocks", MAXSEG);
   VQ_REQUIRE(Wc && gh && gcond && ws, "resstack_gcond_bwd: null pointer");
-  VQ_REQUIRE(!(d->storage & VQVAE_STORE_GH_BF16), "resstack_gcond_bwd: reads fp32 gh (the latent-rate chain pulls a bf16 gh back with vqvae_upsample_linear_bwd_bf16)");
+  VQ_REQUIRE(rb_formats(d, RB_GH).gh != FMT_BF16, "resstack_gcond_bwd: reads fp32 gh (the latent-rate chain pulls a bf16 gh back with vqvae_upsample_linear_bwd_bf16)");
   const GcondPlan gp = resstack_gcond_plan(d, nblocks);
   if (ws_bytes < gp.total) { set_error("resstack_gcond_bwd: workspace too small"); return VQVAE_E_WORKSPACE; }
   hipStream_t st = (hipStream_t)s;
@@ -1305,7 +1316,7 @@ extern "C" int vqvae_resstack_skip_wgrad(const vqvae_resblock_desc* d, int nbloc
   }
   wa.ngbl = gbs ? nblocks : 0;
   wa.accumulate = accumulate;
-  wa.x16 = z_bf16(d) ? 1 : 0;
+  wa.x_fmt = rb_formats(d, 0).z;
   if (g_matmul_dtype == 3 && g_skip_amax) { wa.f16x2 = 1; wa.amax_gy = g_skip_amax; }
   return launch_wgrad(wa, p, (float*)ws, VQVAE_PROF_WGRAD_RES_SKIP, st);
 }
@@ -1342,8 +1353,8 @@ extern "C" int vqvae_resstack_res_wgrad(const vqvae_resblock_desc* d, int nblock
   wa.gy = wa.seg[0].gy; wa.gy_bstride = (long)d->Cr * T; wa.M = d->Cr; wa.Tout = T; wa.B = d->B;
   wa.nseg = n;
   wa.accumulate = accumulate;
-  wa.x16 = z_bf16(d) ? 1 : 0;
-  wa.g16 = (d->storage & VQVAE_STORE_GRES_BF16) ? 1 : 0;      // every g_res of this launch
+  const RbFmt f = rb_formats(d, RB_GRES);
+  wa.x_fmt = f.z; wa.gy_fmt = f.g_res;                        // every g_res of this launch
   return launch_wgrad(wa, p, (float*)ws, VQVAE_PROF_WGRAD_RES_SKIP, st);
 }
 
@@ -1368,7 +1379,7 @@ extern "C" int vqvae_resblock_wgrad(const vqvae_resblock_desc* d, const float* x
   }
   wa.seg[0].gb = gbd;
   wa.accumulate = accumulate;
-  wa.g16 = (d->storage & VQVAE_STORE_GH_BF16) ? 1 : 0;
+  wa.gy_fmt = rb_formats(d, VQVAE_STORE_GH_BF16).gh;       // (this per-block form reads a bf16 gh; a pre-split one goes through resstack_dil_wgrad)
   return launch_wgrad(wa, p, (float*)ws, VQVAE_PROF_RESBLOCK_WGRAD, st);
 }
 
@@ -1410,17 +1421,14 @@ extern "C" int vqvae_resstack_dil_wgrad(const vqvae_resblock_desc* d, int nblock
     }
   }
   if (g_matmul_dtype == 3 && x_amax && gh_amax) wa.f16x2 = 1;
-  const bool both_presplit = (wa.f16x2 && (d->storage & VQVAE_STORE_GH_F16X2) && (d->storage & VQVAE_STORE_X_F16X2)) ||
-                             (g_matmul_dtype == 1 && (d->storage & VQVAE_STORE_GH_BF16) && (d->storage & VQVAE_STORE_X_BF16) && T % 64 == 0);   // (mode 1: both stored as bf16)
-  const WgradPlan p = dil_wgrad_plan(d, n, both_presplit);
+  const RbFmt f = rb_formats(d, RB_GH | RB_X);      // every block of this launch (the caller groups them accordingly)
+  const bool both_stored = f.x != FMT_F32 && f.gh == f.x && (f.x == FMT_F16X2 ? wa.f16x2 != 0 : T % 64 == 0);
+  const WgradPlan p = dil_wgrad_plan(d, n, both_stored);
   if (ws_bytes < wgrad_bytes(p)) { set_error("resstack_dil_wgrad: workspace too small"); return VQVAE_E_WORKSPACE; }
   wa.gy = wa.seg[0].gy; wa.gy_bstride = (long)d->Cd * T; wa.M = d->Cd; wa.Tout = T; wa.B = d->B;
   wa.nseg = n;
   wa.accumulate = accumulate;
-  wa.g16 = (d->storage & (VQVAE_STORE_GH_BF16 | VQVAE_STORE_GH_F16X2)) ? 1 : 0;
-  wa.x16 = (d->storage & (VQVAE_STORE_X_BF16 | VQVAE_STORE_X_F16X2)) ? 1 : 0;        // every block of this launch (the caller groups them accordingly)
-  if (d->storage & (VQVAE_STORE_GH_F16X2 | VQVAE_STORE_X_F16X2))
-    VQ_REQUIRE(wa.f16x2, "resstack_dil_wgrad: pre-split operands (desc.storage) need the float32x2 launch: every block's scale words");
+  wa.gy_fmt = f.gh; wa.x_fmt = f.x;                 // (pre-split without every block's scale words: launch_wgrad rejects it)
   return launch_wgrad(wa, p, (float*)ws, VQVAE_PROF_WGRAD_DIL, st);
 }
 

@@ -9,9 +9,9 @@
 
 namespace vq {
 
-// X16 (matmul mode 1): activations that are STORED as bf16 (GemmArgs::z16 / x16) are fetched with 2-byte loads and
+// X16 (matmul mode 1): activations that are STORED as bf16 (Seg::fmt, see seg_mask) are fetched with 2-byte loads and
 // staged without a conversion.  Bit 0: segment 0 of a TAP2 launch / every segment of any other launch; bit 1: the
-// second segment of a TAP2 launch (the two may differ: g_res fp32 | g_skip bf16 in the gate-derivative GEMM).
+// second segment of a TAP2 launch (the two may differ: g_res bf16 | g_skip fp32 in the gate-derivative GEMM).
 // (matmul mode 3, NP = 2: the same X16 mask marks PRE-SPLIT segments -- fp16 hi | lo dwords at the fp32 addresses, staged
 // with two v_perm_b32 per element pair instead of split2; OUT = 1: EPI_GATE_BWD stores gh that way.)
 template <int EPI, int WM, int NB, int NP, bool TAP2 = false, int X16 = 0, int OUT = 0>
@@ -810,10 +810,11 @@ static int launch_lin128(const GemmArgs& g, int mode, int tag, hipStream_t st) {
   la.bias = g.out[0].bias;
   la.T = g.Tout;
   la.wamax = s0.wamax; la.z_amax = s0.amax; la.z_amax_static = s0.amax_static; la.amax_out = g.out[0].amax_out;
-  la.add16 = g.add16; la.y16 = g.y16;
+  const bool add16 = g.out[0].add_fmt != FMT_F32, y16 = g.out[0].y_fmt != FMT_F32, z16 = s0.fmt != FMT_F32;      // (mode 1: bf16; mode 3: pre-split)
+  la.add16 = add16; la.y16 = y16;
   la.add_scale = g.add_scale; la.add_amax = g.add_amax; la.l1 = g.bound_l1; la.scale_out = g.scale_out;
   la.floor_w = g.floor_w; la.floor_p = g.floor_p;
-  const int nc = (lin128_tile() == 32 || g.z16) ? 32 : 64;
+  const int nc = (lin128_tile() == 32 || z16) ? 32 : 64;
   la.tiles_per_b = g.Tout / nc; la.ntiles = la.tiles_per_b * g.B;
   static int n_cu = 0;
   if (n_cu == 0) {
@@ -825,10 +826,10 @@ static int launch_lin128(const GemmArgs& g, int mode, int tag, hipStream_t st) {
   void (*k)(Lin128Args);
   if (mode == 2) k = nc == 32 ? (add ? lin128_stream_kernel<3, 32, true> : lin128_stream_kernel<3, 32, false>)
                               : (add ? lin128_stream_kernel<3, 64, true> : lin128_stream_kernel<3, 64, false>);
-  else if (mode == 3 && (g.add16 || g.y16)) k = g.add16 ? lin128_stream_kernel<2, 32, true, false, true, true> : lin128_stream_kernel<2, 32, true, false, false, true>;
+  else if (mode == 3 && (add16 || y16)) k = add16 ? lin128_stream_kernel<2, 32, true, false, true, true> : lin128_stream_kernel<2, 32, true, false, false, true>;
   else if (mode == 3) k = add ? lin128_stream_kernel<2, 32, true> : lin128_stream_kernel<2, 32, false>;
-  else if (g.add16 || g.y16) k = g.add16 ? lin128_stream_kernel<1, 32, true, true, true, true> : lin128_stream_kernel<1, 32, true, true, false, true>;
-  else if (g.z16) k = add ? lin128_stream_kernel<1, 32, true, true> : lin128_stream_kernel<1, 32, false, true>;
+  else if (add16 || y16) k = add16 ? lin128_stream_kernel<1, 32, true, true, true, true> : lin128_stream_kernel<1, 32, true, true, false, true>;
+  else if (z16) k = add ? lin128_stream_kernel<1, 32, true, true> : lin128_stream_kernel<1, 32, false, true>;
   else k = nc == 32 ? (add ? lin128_stream_kernel<1, 32, true> : lin128_stream_kernel<1, 32, false>)
                     : (add ? lin128_stream_kernel<1, 64, true> : lin128_stream_kernel<1, 64, false>);
   launch_tagged(k, dim3(nwg), dim3(512), st, tag, la);
@@ -927,6 +928,15 @@ static TileTraits tile_traits(const GemmArgs& g, int mode) {
   return t;
 }
 
+// conv_gemm_x3_kernel's X16 mask of a launch, from its segments' formats: 0 = all fp32, 3 = all stored, 1 = the first of two
+// (the gate-derivative GEMM's [g_res | g_skip]); -1: a mix no kernel reads
+static int seg_mask(const GemmArgs& g) {
+  bool same = true;
+  for (int i = 1; i < g.nseg; ++i) same = same && g.seg[i].fmt == g.seg[0].fmt;
+  if (same) return g.seg[0].fmt != FMT_F32 ? 3 : 0;
+  return (g.nseg == 2 && g.seg[1].fmt == FMT_F32) ? 1 : -1;
+}
+
 // Everything that writes into g or rejects a malformed g; no later stage mutates it.  (An empty launch returns 0 half way:
 // launch_gemm stops there too.)
 template <int EPI>
@@ -945,6 +955,17 @@ static int prepare_gemm(GemmArgs& g, int mode) {
   const long nblk = (long)g.ntile_m * g.ntile_n * g.B;
   if (nblk <= 0) return 0;
   VQ_REQUIRE(nblk < (1L << 31), "conv_gemm: grid too large");
+  // The storage formats (Fmt) this launch's arithmetic can read and write, and the tensors a kernel keeps in them: any
+  // segment, range 0's y and add; of range 1 only the gate GEMM's z, and that and the gate values never pre-split.
+  {
+    int used = (1 << g.out[0].y_fmt) | (1 << g.out[0].add_fmt) | (1 << g.out[1].y_fmt) | (1 << g.out[1].add_fmt);
+    for (int i = 0; i < g.nseg; ++i) used |= 1 << g.seg[i].fmt;
+    VQ_REQUIRE(!(used & (1 << FMT_BF16)) || mode == 1, "conv_gemm: bf16-stored tensors need matmul mode 1");
+    VQ_REQUIRE(!(used & (1 << FMT_F16X2)) || mode == 3, "conv_gemm: pre-split tensors need a float32x2 launch (every segment with its maxima)");
+    VQ_REQUIRE(seg_mask(g) >= 0, "conv_gemm: segments stored in different formats: only the first of two may differ from the rest");
+    VQ_REQUIRE(g.out[1].add_fmt == FMT_F32 && (EPI == EPI_GATE ? g.out[1].y_fmt != FMT_F16X2 && g.out[0].y_fmt != FMT_F16X2 : g.out[1].y_fmt == FMT_F32) &&
+               (EPI != EPI_GATE_BWD || g.out[0].add_fmt != FMT_F16X2), "conv_gemm: no kernel keeps this output / the gate values in that format");
+  }
   if (mode != 0)          // modes 1 - 3 address a batch item's activations with 32-bit buffer offsets
     for (int i = 0; i < g.nseg; ++i)
       VQ_REQUIRE((long)g.seg[i].cin * g.seg[i].x_cstride * 4 < (1L << 31), "conv_gemm: one batch item of segment %d exceeds 2 GB (Cin * T * 4 bytes)", i);
@@ -963,12 +984,12 @@ static int prepare_gemm(GemmArgs& g, int mode) {
   // first one's upper K steps), which the TAP2 / LEAN loop interleaves like two taps: two workgroups per CU, one tile's
   // epilogue beside the other's loop.  Depends on the contraction only (never on B or T); the K order changes, the products do not.
   // (proj1 / proj2 forward and backward-data 105 -> ~70 us each, the step 14.87 -> 14.73 ms: same box, two interleaved rounds)
-  // (Never a launch the streaming 1x1 forms claim: lin_wide_shape needs y16, lin128_shape this very M and K.)
+  // (Never a launch the streaming 1x1 forms claim: lin_wide_shape needs a pre-split output, lin128_shape this very M and K.)
   if constexpr (EPI == EPI_LINEAR) {
     Seg& s0 = g.seg[0];
     if (big && (mode == 2 || mode == 3) && g.nseg == 1 && g.ksplit == 1 && s0.cin >= 64 && s0.cin % 32 == 0 &&
         !(g.M == 256 && s0.cin == 128) &&      // (the residual 1x1's shape keeps the K order of lin128_stream_kernel, its bitwise twin)
-        s0.tmul == 1 && s0.tdiv == 1 && !g.x16 && !g.z16 && !g.add16 && !g.y16) {
+        s0.tmul == 1 && s0.tdiv == 1 && s0.fmt == FMT_F32 && g.out[0].add_fmt == FMT_F32 && g.out[0].y_fmt == FMT_F32) {
       Seg& s1 = g.seg[1];
       s1 = s0;
       const int half = s0.cin / 2;
@@ -1000,21 +1021,23 @@ static GemmForm tiled_form(int wm, int nb, int np, bool tap2, int x16, int out, 
 }
 
 // Which form serves the prepared g in this mode: the forms in their order of precedence, each with the checks that it can
-// serve the storage flags the caller set.  No side effect but the error text, no HIP call.
+// serve the storage formats the caller set (prepare_gemm has matched them to the mode).  No side effect but the error text, no HIP call.
 template <int EPI>
 static int select_gemm(const GemmArgs& g, int mode, GemmForm& f) {
   f = GemmForm{};
+  // a linear GEMM whose add / output is the stored residual (gradient) stream
+  const bool stream = EPI == EPI_LINEAR && (g.out[0].add_fmt != FMT_F32 || g.out[0].y_fmt != FMT_F32);
   // the K = 128 -> 256-row projection with residual add (the ResidualBlock `res` conv): streaming kernels
   if constexpr (EPI == EPI_LINEAR) {
     if (lin128_tile() != 0) {
       // the 512-channel decoder's pre-split chain (K = 256 -> 512 rows): lin_stream_wide.hip's kernel, two row slices per column tile
       if (mode == 3 && lin_wide_shape(g)) { f.family = GEMM_LIN_WIDE; return 0; }
       if (lin128_shape(g, mode)) {
-        if (mode == 3 && (g.add16 || g.y16))
-          VQ_REQUIRE(g.out[0].add && g.y16 && g.add_amax && g.bound_l1 && g.scale_out && (!g.add16 || g.add_scale),
-                     "conv_gemm: a pre-split residual stream needs the residual add, a pre-split output and its bound's inputs");
-        if (mode == 1 && (g.add16 || g.y16))
-          VQ_REQUIRE(g.z16 && g.out[0].add && g.y16, "conv_gemm: a bf16 residual stream needs matmul mode 1's bf16 z, the residual add and a bf16 output");
+        if (stream)     // (mode 1: bf16; mode 3: pre-split -- prepare_gemm)
+          VQ_REQUIRE(g.out[0].add && g.out[0].y_fmt != FMT_F32 &&
+                     (mode == 3 ? g.add_amax && g.bound_l1 && g.scale_out && (g.out[0].add_fmt == FMT_F32 || g.add_scale) : g.seg[0].fmt == FMT_BF16),
+                     "conv_gemm: a stored residual stream needs the residual add, a stored output and its bound's inputs (pre-split) / a bf16 z (bf16)");
+        VQ_REQUIRE(g.seg[0].fmt != FMT_F16X2, "conv_gemm: the streaming residual 1x1 reads no pre-split z");
         f.family = GEMM_LIN128;
         return 0;
       }
@@ -1022,30 +1045,29 @@ static int select_gemm(const GemmArgs& g, int mode, GemmForm& f) {
   }
   const TileTraits t = tile_traits<EPI>(g, mode);
   const bool big = t.big, tap2 = t.tap2, lean = t.lean, wide = t.wide;
-  VQ_REQUIRE(mode == 3 || g_matmul_dtype != 3 || (!g.x16 && !g.h16 && !g.add16 && !g.y16), "conv_gemm: pre-split tensors need a float32x2 launch (every segment with its maxima)");
-  if (g.add16 || g.y16)
-    VQ_REQUIRE(EPI == EPI_LINEAR && mode == 1 && big && g.Tout % BN == 0 && g.M % 256 == 0 && g.out[1].y == nullptr && !g.out[0].bias &&
+  if (stream)
+    VQ_REQUIRE(mode == 1 && big && g.Tout % BN == 0 && g.M % 256 == 0 && g.out[1].y == nullptr && !g.out[0].bias &&
                !g.out[0].relu && !g.out[0].accumulate && g.ksplit == 1,
                "conv_gemm: a bf16 residual / gradient stream needs matmul mode 1, whole 256-row tiles and a plain (acc + add) epilogue");
   // workgroups: one per tile (prepare_gemm left 256-column tiles in ntile_n where they run) and split
   const long grid = (long)g.ntile_m * g.ntile_n * g.B * g.ksplit;
-  // activations stored as bf16 (matmul mode 1): a linear GEMM over z tensors (z16: every segment), or the caller's mask
-  const int xm = (EPI == EPI_LINEAR && g.z16) ? 3 : g.x16;
-  if (mode == 3 && (xm != 0 || g.h16 || (EPI == EPI_GATE_BWD && g.pb_part))) {       // float32x2 with pre-split tensors (see presplit_pair) / the fused pull-back
+  const int xm = seg_mask(g);                                           // stored activations: the kernels' X16 mask
+  const bool gh_pre = EPI == EPI_GATE_BWD && g.out[0].y_fmt == FMT_F16X2;
+  if (mode == 3 && (xm != 0 || gh_pre || (EPI == EPI_GATE_BWD && g.pb_part))) {       // float32x2 with pre-split tensors (see presplit_pair) / the fused pull-back
     VQ_REQUIRE(g.ksplit == 1, "conv_gemm: pre-split tensors: no split-K");
     if constexpr (EPI == EPI_GATE) {
       VQ_REQUIRE(tap2 && lean && xm == 3 && g.seg[0].amax == g.seg[1].amax && g.seg[0].wamax == g.seg[1].wamax,
                  "conv_gemm: gate GEMM over a pre-split x: both taps of one tensor, 256 x 128 tiles");
       f = tiled_form(4, 1, 2, true, 3, 0, grid);
     } else if constexpr (EPI == EPI_LINEAR) {
-      VQ_REQUIRE(tap2 && lean && xm == 3 && g.seg[0].amax == g.seg[1].amax && g.seg[0].wamax == g.seg[1].wamax && !g.add16 && !g.y16,
+      VQ_REQUIRE(tap2 && lean && xm == 3 && g.seg[0].amax == g.seg[1].amax && g.seg[0].wamax == g.seg[1].wamax,
                  "conv_gemm: backward-data GEMM over a pre-split gh: both taps of one tensor, 256 x 128 tiles");
       f = tiled_form(4, 1, 2, true, 3, 0, grid);
     } else {
-      VQ_REQUIRE(xm == 0 && (!g.h16 || (g.bound_l1 && g.scale_out)), "conv_gemm: gate-derivative GEMM storing a pre-split gh needs its bound's inputs (fp32 operands)");
+      VQ_REQUIRE(xm == 0 && (!gh_pre || (g.bound_l1 && g.scale_out)), "conv_gemm: gate-derivative GEMM storing a pre-split gh needs its bound's inputs (fp32 operands)");
       if (g.pb_part) VQ_REQUIRE(g.M == 128 && g.Tout % BN == 0 && g.lerp.v0 && g.lerp.w0 && g.lerp.w1 && (long)g.Tout >= 64L * g.lerp.Tl,
                                 "conv_gemm: the fused latent pull-back serves 128 gate channels, T %% 128 == 0, T >= 64 Tl");
-      const int out = (g.h16 ? 1 : 0) | (g.pb_part ? 2 : 0);
+      const int out = (gh_pre ? 1 : 0) | (g.pb_part ? 2 : 0);
       // ResidualNet's chain (pre-split gh + pull-back, g_res | g_skip): the column-strip streaming kernel, 16 waves per CU.
       // Same bits; every other launch (the stack's last block has no g_res, OUT = 1 / 2) stays on the tiles below
       if (out == 3 && tap2 && gate_bwd_strip_shape(g)) { f.family = GEMM_GATE_STRIP; return 0; }
@@ -1054,7 +1076,7 @@ static int select_gemm(const GemmArgs& g, int mode, GemmForm& f) {
     return 0;
   }
   if (xm != 0) {
-    VQ_REQUIRE(mode == 1 && g.ksplit == 1, "conv_gemm: bf16-stored activations need matmul mode 1");
+    VQ_REQUIRE(g.ksplit == 1, "conv_gemm: bf16-stored activations: no split-K");
     for (int i = 0; i < g.nseg; ++i) VQ_REQUIRE(g.seg[i].tmul == 1 && g.seg[i].tdiv == 1, "conv_gemm: bf16-stored activations: stride-1 segments only");
     if constexpr (EPI == EPI_LINEAR) {
       VQ_REQUIRE(big && xm == 3, "conv_gemm: bf16-stored activations of a linear GEMM: every segment, 256-row tiles");

@@ -279,8 +279,8 @@ __global__ __launch_bounds__(64 * GS_WAVES) void gate_bwd_strip_kernel(const Gem
 // plain fp32 operands, gh stored pre-split, the pull-back fused (which brings T % 128 == 0 and the resize tables)
 bool gate_bwd_strip_shape(const GemmArgs& g) {
   if (g.nseg != 2 || g.M != 128 || g.Tout % BN != 0 || g.B <= 0) return false;
-  if (!g.h16 || !g.pb_part || !g.bound_l1 || !g.scale_out || !g.lerp.v0 || !g.lerp.w0 || !g.lerp.w1) return false;
-  if (g.x16 || g.g16 || g.skip_flag || g.ksplit != 1 || (g.gsig && !g.zsrc)) return false;
+  if (g.out[0].y_fmt != FMT_F16X2 || !g.pb_part || !g.bound_l1 || !g.scale_out || !g.lerp.v0 || !g.lerp.w0 || !g.lerp.w1) return false;
+  if (g.seg[0].fmt != FMT_F32 || g.seg[1].fmt != FMT_F32 || g.out[0].add_fmt != FMT_F32 || g.skip_flag || g.ksplit != 1 || (g.gsig && !g.zsrc)) return false;
   const Seg& s0 = g.seg[0];
   const Seg& s1 = g.seg[1];
   if (s0.cin != s1.cin || s0.cin % BK != 0 || s0.cin <= 0 || s0.ldw != s1.ldw || s0.ldw < 128) return false;

@@ -54,6 +54,17 @@ __device__ unsigned long long g_phase[3][8];
 constexpr int MAXSEG = 24;   // a whole ResidualNet's blocks can feed one contraction
 constexpr int MAXTAPS = 4;
 
+// How a tensor of the decoder chain lies in HBM.  All three keep fp32's element strides (the caller's buffers are fp32-sized):
+//   FMT_F32    fp32.
+//   FMT_BF16   matmul mode 1 only: 2-byte elements, the buffer simply half used.  The gate values [tanh | sigmoid] are the
+//              exception in shape: the pair of a (channel, t) is ONE dword (bf16 tanh | bf16 sigmoid << 16) in tanh's fp32 position.
+//   FMT_F16X2  float32x2 launches (matmul mode 3) only, PRE-SPLIT storage (see presplit_pair): one dword per element at the
+//              fp32 element's address, fp16 hi | fp16 lo << 16 of v * 2^(14 - e(bound)); the tensor's `amax` words are the
+//              SCALE words its producer wrote.
+// The values are upsample_bwd_seg_kernel's IN16, and FMT_F32 is 0 because every descriptor starts as memset(&g, 0, sizeof(g)):
+// a caller that says nothing (the generic conv, the encoder, the heads) means fp32.
+enum Fmt : int { FMT_F32 = 0, FMT_BF16 = 1, FMT_F16X2 = 2 };
+
 struct Seg {
   const float* x;      // activations, channel 0 of this segment
   long x_bstride;      // elements between batch items
@@ -62,6 +73,7 @@ struct Seg {
   int Tin;             // valid input times [0, Tin)
   int tmul, toff, tdiv;  // t_in = (t_out*tmul + toff) / tdiv  (must divide exactly)
   int vec;             // host says: strides/pointer allow aligned float4 rows
+  Fmt fmt;             // how these activations are stored (host side: conv_gemm_x3_kernel's X16 mask is derived from it)
   const float* w;      // packed A^T slab [cin_pad16][ldw]
   int ldw;
   // float32x2 (NP = 2) only: where the absolute maximum of the activation tensor is (device, float bits; any
@@ -76,11 +88,17 @@ struct OutR {          // one row range of M
   const float* add; long add_bstride;   // residual add / gates input
   const float* bias; const float* bias2;
   int rows; int accumulate; int relu;
+  // how y is stored / how add is (see Fmt).  Range 0: EPI_LINEAR y = the residual (gradient) stream out, add = the stream in
+  // (the streaming 1x1 kernels, the backward-data GEMM's epilogue); EPI_GATE y = the gate values; EPI_GATE_BWD y = gh (bf16,
+  // or pre-split under the bound sum_seg bound_l1[seg] * max|x_seg|, published to scale_out), add = the gate values.
+  // Range 1: EPI_GATE y = z (mode 1: bf16, since its only readers round it while staging)
+  Fmt y_fmt;
   unsigned* amax_out;  // range 0 only, nullable: atomicMax of |y| over everything this launch stores (float bits)
   // add_is_mask != 0: `add` is not added but gates the result -- y = add > 0 ? value : 0: the backward of a ReLU whose OUTPUT
   // is the tensor this GEMM's result is the gradient of (conv1d_bwd_data_relu), applied where the gradient is produced
   // instead of in a pass of its own (three passes over 126 MB per step at the configs)
   int add_is_mask;
+  Fmt add_fmt;
 };
 __device__ __forceinline__ float lin_combine(float acc, float p, int is_mask) { return is_mask ? (p > 0.f ? acc : 0.f) : acc + p; }
 
@@ -117,17 +135,10 @@ struct GemmArgs {
   const int32_t* skip_flag;
   int x_nt;      // the activations of every segment are read once by this launch and by nothing soon after (the skip sum over all blocks' z): non-temporal loads
   int f16x2;     // matmul mode 3: every segment carries its maxima and a format-3 slab -> the float32x2 kernels (NP = 2); otherwise mode 3 runs mode 2's
-  int g16;       // matmul mode 1 only: the gate values (EPI_GATE: out[0]; EPI_GATE_BWD: out[0].add) are stored as bf16, the pair (tanh, sigmoid) of a (channel, t) as one dword in tanh's fp32 position
-  int x16;       // matmul mode 1 only: activations STORED as bf16 (conv_gemm_x3_kernel's X16 mask: bit 0 = segment 0 of a two-tap launch / every segment otherwise, bit 1 = the second segment of a two-tap launch)
-  int add16, y16; // matmul mode 1 only, the streaming residual 1x1 (lin128_stream_kernel): out[0].add is read / out[0].y is stored as bf16 (the residual stream x_l, vqvae_resblock_desc::storage)
-  int h16;       // matmul mode 1 only: EPI_GATE_BWD stores gh (out[0].y) as bf16 (same element strides, 2-byte elements)
-  int z16;       // matmul mode 1 only: EPI_GATE writes z (out[1]) as bf16; a linear GEMM reads the activations of EVERY segment as bf16 (the z tensors)
-  // matmul mode 3 (float32x2 launches), PRE-SPLIT storage (see presplit_pair): x16 = the same segment mask, here "stored
-  // as fp16 hi | lo dwords" (same addresses as fp32; the segment's `amax` words are the scale words its producer wrote);
-  // h16 = EPI_GATE_BWD stores gh that way under the bound sum_seg bound_l1[seg] * max|x_seg|, published to scale_out
+  // a pre-split output's bound (OutR::y_fmt == FMT_F16X2): its inputs and where it is published
   const float* bound_l1; unsigned* scale_out;
-  // ... and the streaming residual 1x1 (lin128_stream_kernel): add16 / y16 = x_l read / x_{l+1} stored pre-split; add_scale =
-  // the scale words of x_l, add_amax = its ACTUAL maximum, bound_l1[0] = max_r (sum_c |Wr[r][c]| + |br[r]|)
+  // ... of the streaming residual 1x1 (lin128_stream_kernel, x_l read / x_{l+1} stored pre-split): add_scale = the scale
+  // words of x_l, add_amax = its ACTUAL maximum, bound_l1[0] = max_r (sum_c |Wr[r][c]| + |br[r]|)
   const unsigned* add_scale; const unsigned* add_amax;
   // ... whose scale also leaves room for the NEXT block's condition step (see "the condition as a K step"): the exponent
   // of x_{l+1}'s scale is at least e(max |P|) - e(max |Wd_{l+1}|) - 1 (floor_p / floor_w: those maxima; NULL = no floor)
@@ -278,7 +289,7 @@ __device__ __forceinline__ void presplit_pair(float x0, float x1, int k, unsigne
 // (rows m0 + wm*64 + mi*32, columns t0 + wn*64 + ni*32) of batch item b.  SPLITK: this instantiation
 // may have been launched with ksplit > 1 (raw partial tiles out, gemm_splitk_reduce_kernel finishes).
 // DEEP: the linear epilogue requests a whole block's operands up front (needs 64 more registers).
-// ST16: the instantiation may be asked for bf16-stored tensors (GemmArgs::g16 / h16 / z16: matmul mode 1's kernels only --
+// ST16: the instantiation may be asked for bf16-stored tensors (OutR::y_fmt / add_fmt: matmul mode 1's kernels only --
 // the other modes' kernels do not carry those paths: they cost the float32x2 gate-derivative kernel 24 spilled registers).
 // OUT = 1 (EPI_GATE_BWD, float32x2): gh is stored PRE-SPLIT under 2^kout (presplit_pair; `am` still collects the actual maximum).
 template <int EPI, int WM, bool SPLITK, bool DEEP = false, bool ST16 = false, int OUT = 0>
@@ -308,11 +319,11 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[2
     // load/store/load/store order exposed one load AND one store latency per sub-tile, which is
     // what bounded the K = 128 projections (315 MB of traffic per launch, 8 GFLOP).
     if constexpr (ST16) {
-      // matmul mode 1, the residual GRADIENT stream kept as bf16 (GemmArgs::add16 / y16: the backward-data GEMM of the
+      // matmul mode 1, the residual GRADIENT stream kept as bf16 (out[0].add_fmt / y_fmt: the backward-data GEMM of the
       // packed chain; whole tiles, one output range, no bias / relu / accumulate -- the host guarantees all of it):
       // y = bf16(acc + add).  2-byte elements at the fp32 element strides; a lane pair (columns t, t + 1) shares the dwords
       // of a row pair and swaps halves by DPP, as in lin128_stream_kernel.  Same one-sub-tile look-ahead as below.
-      if (a.add16 || a.y16) {
+      if (a.out[0].add_fmt || a.out[0].y_fmt) {
         const OutR& od = a.out[0];
         auto run16 = [&](auto add16c, auto y16c) {
           constexpr bool ADD16 = decltype(add16c)::value, Y16 = decltype(y16c)::value;
@@ -364,8 +375,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[2
             }
           }
         };
-        if (a.add16 && a.y16) run16(std::true_type{}, std::true_type{});
-        else if (a.y16) run16(std::false_type{}, std::true_type{});
+        if (od.add_fmt && od.y_fmt) run16(std::true_type{}, std::true_type{});
+        else if (od.y_fmt) run16(std::false_type{}, std::true_type{});
         else run16(std::true_type{}, std::false_type{});
         return;
       }
@@ -605,8 +616,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[2
     // Phase 2 -- gate and the three stores per element
     const rsrc_t rG = make_rsrc(og.y + (long)b * og.y_bstride);
     // z is read only through GEMM staging; in matmul mode 1 that staging rounds it to bf16 anyway, so it is
-    // STORED as bf16 there (a.z16; same element strides, 2-byte elements): identical results, half the bytes
-    const rsrc_t rZ = make_rsrc(reinterpret_cast<const char*>(oz.y) + (long)b * oz.y_bstride * (a.z16 ? 2 : 4));
+    // STORED as bf16 there (oz.y_fmt; same element strides, 2-byte elements): identical results, half the bytes
+    const rsrc_t rZ = make_rsrc(reinterpret_cast<const char*>(oz.y) + (long)b * oz.y_bstride * (oz.y_fmt ? 2 : 4));
     unsigned vT[2];
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) vT[ni] = 4u * (unsigned)(chl * T + tt[ni]);
@@ -626,13 +637,13 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[2
         if constexpr (SIG) {       // sigmoid and z only: the backward takes tanh = z / sigmoid
           buf_st_gate(sb, rG, vT[ni], sT + sGq);
         } else
-        if (ST16 && a.g16) {     // BASELINE configs[4] precision: the saved gate values are bf16 (the backward pass reads exactly these): the pair (tanh, sigmoid) of one (channel, t) as ONE dword in tanh's fp32 position -- one store, and one load in the backward, instead of two
+        if (ST16 && og.y_fmt) {     // BASELINE configs[4] precision: the saved gate values are bf16 (the backward pass reads exactly these): the pair (tanh, sigmoid) of one (channel, t) as ONE dword in tanh's fp32 position -- one store, and one load in the backward, instead of two
           __builtin_amdgcn_raw_buffer_store_b32((int)pack_bf16x2(ta, sb), rG, vT[ni], sT, X3_GATE_ST_AUX);
         } else {
           buf_st_gate(ta, rG, vT[ni], sT);
           buf_st_gate(sb, rG, vT[ni], sT + sGq);
         }
-        if (ST16 && a.z16) __builtin_amdgcn_raw_buffer_store_b16((short)(pack_bf16x2(ta * sb, 0.f) & 0xffffu), rZ, vT[ni] >> 1, sT >> 1, 0);
+        if (ST16 && oz.y_fmt) __builtin_amdgcn_raw_buffer_store_b16((short)(pack_bf16x2(ta * sb, 0.f) & 0xffffu), rZ, vT[ni] >> 1, sT >> 1, 0);
         else buf_st_gate(ta * sb, rZ, vT[ni], sT);
       }
     }
@@ -695,7 +706,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[2
               }
         }
       };
-      if (ST16 && a.g16) load_gates(std::integral_constant<int, 1>{});
+      if (ST16 && od.add_fmt) load_gates(std::integral_constant<int, 1>{});
       else if (a.gsig) load_gates(std::integral_constant<int, 2>{});
       else load_gates(std::integral_constant<int, 0>{});
       // ---- fused latent pull-back (OUT bit 1).  gP[c, v] = sum_t gh[c, t] W(t, v), W(t, v0[t]) = w0[t], W(t, v0[t] + 1) = w1[t]: the
@@ -724,7 +735,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[2
       const bool gsig_ = a.gsig != 0;
       auto store_gh = [&](auto h16c) {         // (ONE wave-uniform branch around the whole store loop, as for the loads)
         constexpr bool H16 = decltype(h16c)::value;
-        // H16 (GemmArgs::h16): gh is read back only as an MFMA operand (backward-data, weight gradient), i.e. rounded
+        // H16 (od.y_fmt, matmul mode 1): gh is read back only as an MFMA operand (backward-data, weight gradient), i.e. rounded
         // to bf16 -- and by the bias sum and the latent pull-back, which then see the rounded values (the oracle's bf16
         // mode mirrors that): stored as bf16, same element strides
         const rsrc_t rGh16 = make_rsrc(reinterpret_cast<const char*>(od.y) + (long)b * od.y_bstride * 2);
@@ -801,7 +812,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[2
             }
           }
       };
-      if (ST16 && a.h16) store_gh(std::true_type{}); else store_gh(std::false_type{});
+      if (ST16 && od.y_fmt) store_gh(std::true_type{}); else store_gh(std::false_type{});
       if constexpr (PB) {
         __syncthreads();
         const int tid_ = (wm * 2 + wn) * 64 + lk * 32 + li;
@@ -1037,8 +1048,7 @@ struct WgradArgs {
   float* gbl[MAXSEG]; int ngbl;   // further copies of segment 0's bias grad (shared gy, many layers)
   int accumulate;
   const int32_t* skip_flag;       // see GemmArgs::skip_flag
-  int x16;                        // matmul mode 1 only: the x operand of every segment (the z tensors) is stored as bf16
-  int g16;                        // matmul mode 1 only: the output-gradient operand (every segment's gy) is stored as bf16
+  Fmt x_fmt, gy_fmt;              // how the x operand of every segment / the output-gradient operand (every segment's gy) is stored (host side: wgrad3_kernel's X16 / G16)
   const unsigned* amax_gy;        // float32x2: absolute maximum of the common gy
   int f16x2;                      // host: run the float32x2 kernel (every segment carries its maxima)
 };

@@ -194,9 +194,9 @@ __global__ __launch_bounds__(512, 1) void lin256_stream_kernel(const LinWideArgs
 bool lin_wide_shape(const GemmArgs& g) {
   const Seg& s0 = g.seg[0];
   if (g.nseg != 1 || g.M != 2 * LW_ROWS || s0.cin != LW_K || g.out[1].y != nullptr || g.B <= 0) return false;
-  if (!g.f16x2 || !g.y16 || !g.out[0].add || !g.add_amax || !g.bound_l1 || !g.scale_out || (g.add16 && !g.add_scale)) return false;
+  if (!g.f16x2 || g.out[0].y_fmt != FMT_F16X2 || !g.out[0].add || !g.add_amax || !g.bound_l1 || !g.scale_out || (g.out[0].add_fmt != FMT_F32 && !g.add_scale)) return false;
   if (g.out[0].relu || g.out[0].accumulate || g.out[0].add_is_mask || g.lerp.P != nullptr || g.skip_flag != nullptr || g.ksplit != 1) return false;
-  if (g.x16 || g.z16 || g.h16 || !s0.wamax || !(s0.amax || s0.amax_static > 0.f)) return false;
+  if (s0.fmt != FMT_F32 || !s0.wamax || !(s0.amax || s0.amax_static > 0.f)) return false;
   if (s0.tmul != 1 || s0.tdiv != 1 || s0.toff != 0 || s0.Tin != g.Tout || s0.x_cstride != g.Tout || g.Tout % LW_NC != 0 || !s0.vec) return false;
   if (s0.ldw < 2 * LW_ROWS) return false;
   return (long)2 * LW_ROWS * g.Tout * 4 < (1L << 31);      // 32-bit offsets inside a batch item of x_l / x_{l+1}
@@ -224,7 +224,7 @@ int launch_lin_wide(const GemmArgs& g, int tag, hipStream_t st) {
   int pairs = n_cu / 2 < la.ntiles ? n_cu / 2 : la.ntiles;
   pairs = (pairs + 7) / 8 * 8;
   const dim3 grid((unsigned)(2 * pairs)), block(512);
-  launch_tagged(g.add16 ? lin256_stream_kernel<true> : lin256_stream_kernel<false>, grid, block, st, tag, la);
+  launch_tagged(g.out[0].add_fmt != FMT_F32 ? lin256_stream_kernel<true> : lin256_stream_kernel<false>, grid, block, st, tag, la);
   VQ_LAUNCH_CHECK();
   return 0;
 }

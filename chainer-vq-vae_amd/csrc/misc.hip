@@ -1072,6 +1072,25 @@ __global__ void f32x2_contract_kernel(const ContractPairs cp, int n, int log2_li
 
 using namespace vq;
 
+// The one launcher of upsample_bwd_seg_kernel<fmt> (fmt = the kernel's IN16 = how gy is stored: 0 fp32, 1 bf16, 2 pre-split
+// with its `scale` words) behind the four pull-back exports: L equally shaped tensors, gy_lstride / gx_lstride apart.
+// served = false: not a shape the kernel takes (nothing launched, no error set) -- the caller falls back or rejects.
+static int launch_upsample_bwd_seg(int fmt, const void* gy, unsigned gy_align, long gy_lstride, long gy_bstride, int L, int B, int C,
+                                   int Tin, int Tout, const float* w0, const float* w1, const int32_t* lo0, const int32_t* hi0,
+                                   const int32_t* lo1, const int32_t* hi1, float* gx, long gx_lstride, long gx_bstride,
+                                   const uint32_t* scale, vqvae_stream_t s, bool& served) {
+  served = Tin >= 3 && Tout >= 8 * Tin && Tout % 4 == 0 && Tout / 4 <= 2 * UPS_NT && gy_bstride % 4 == 0 && gy_lstride % 4 == 0 &&
+           ((uintptr_t)gy) % gy_align == 0 && ((uintptr_t)w0) % 16 == 0 && ((uintptr_t)w1) % 16 == 0 && (long)L * B * C < (1L << 31);
+  if (!served) return 0;
+  long nb = (long)L * B * C;
+  if (nb > 512) nb = 512;                        // persistent: 2 workgroups per CU
+  auto k = fmt == 2 ? upsample_bwd_seg_kernel<2> : (fmt == 1 ? upsample_bwd_seg_kernel<1> : upsample_bwd_seg_kernel<0>);
+  hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(UPS_NT), 0, (hipStream_t)s, reinterpret_cast<const float*>(gy), gy_bstride, B, C, Tin, Tout,
+                     w0, w1, lo0, hi0, lo1, hi1, gx, gx_bstride, scale, L, gy_lstride, gx_lstride);
+  VQ_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" {
 
 int vqvae_elementwise(int op, size_t n, const float* a, const float* b, float* out, float alpha,
@@ -1129,14 +1148,9 @@ int vqvae_upsample_linear_bwd(const float* gy, long gy_bstride, int B, int C, in
                               long gx_bstride, vqvae_stream_t s) {
   VQ_REQUIRE(gy && w0 && w1 && lo0 && hi0 && lo1 && hi1 && gx, "upsample_bwd: null pointer");
   const size_t n = (size_t)B * C * Tin;
-  if (Tin >= 3 && Tout >= 8 * Tin && Tout % 4 == 0 && Tout / 4 <= 2 * UPS_NT && gy_bstride % 4 == 0 &&
-      ((uintptr_t)gy) % 16 == 0 && ((uintptr_t)w0) % 16 == 0 && ((uintptr_t)w1) % 16 == 0) {
-    int nb = B * C;
-    if (nb > 512) nb = 512;                      // persistent: 2 workgroups per CU
-    hipLaunchKernelGGL(upsample_bwd_seg_kernel<0>, dim3(nb), dim3(UPS_NT), 0, (hipStream_t)s, gy, gy_bstride, B, C, Tin, Tout, w0, w1, lo0, hi0, lo1, hi1, gx, gx_bstride, nullptr, 1, 0L, 0L);
-    VQ_LAUNCH_CHECK();
-    return 0;
-  }
+  bool served = false;
+  if (int e = launch_upsample_bwd_seg(0, gy, 16, 0L, gy_bstride, 1, B, C, Tin, Tout, w0, w1, lo0, hi0, lo1, hi1, gx, 0L, gx_bstride, nullptr, s, served)) return e;
+  if (served) return 0;
   const size_t tpad = (size_t)Tout + Tout / 8 + 8;
   const size_t lds = (2 * tpad + 2) * sizeof(float);
   if (lds <= 78 * 1024) {                      // two workgroups per CU
@@ -1160,13 +1174,9 @@ int vqvae_upsample_linear_bwd_bf16(const void* gy, long gy_bstride, int B, int C
                                    const int32_t* hi0, const int32_t* lo1, const int32_t* hi1, float* gx,
                                    long gx_bstride, vqvae_stream_t s) {
   VQ_REQUIRE(gy && w0 && w1 && lo0 && hi0 && lo1 && hi1 && gx, "upsample_bwd_bf16: null pointer");
-  VQ_REQUIRE(Tin >= 3 && Tout >= 8 * Tin && Tout % 4 == 0 && Tout / 4 <= 2 * UPS_NT && gy_bstride % 4 == 0 &&
-             ((uintptr_t)gy) % 8 == 0 && ((uintptr_t)w0) % 16 == 0 && ((uintptr_t)w1) % 16 == 0,
-             "upsample_bwd_bf16: serves ratios >= 8 with Tout %% 4 == 0, Tout <= %d", 8 * UPS_NT);
-  int nb = B * C;
-  if (nb > 512) nb = 512;
-  hipLaunchKernelGGL(upsample_bwd_seg_kernel<1>, dim3(nb), dim3(UPS_NT), 0, (hipStream_t)s, reinterpret_cast<const float*>(gy), gy_bstride, B, C, Tin, Tout, w0, w1, lo0, hi0, lo1, hi1, gx, gx_bstride, nullptr, 1, 0L, 0L);
-  VQ_LAUNCH_CHECK();
+  bool served = false;
+  if (int e = launch_upsample_bwd_seg(1, gy, 8, 0L, gy_bstride, 1, B, C, Tin, Tout, w0, w1, lo0, hi0, lo1, hi1, gx, 0L, gx_bstride, nullptr, s, served)) return e;
+  VQ_REQUIRE(served, "upsample_bwd_bf16: serves ratios >= 8 with Tout %% 4 == 0, Tout <= %d", 8 * UPS_NT);
   return 0;
 }
 
@@ -1178,16 +1188,9 @@ int vqvae_upsample_linear_bwd_blocks(const void* gy, int bf16, long gy_lstride, 
                                      const int32_t* lo1, const int32_t* hi1, float* gx, long gx_lstride, long gx_bstride,
                                      vqvae_stream_t s) {
   VQ_REQUIRE(gy && w0 && w1 && lo0 && hi0 && lo1 && hi1 && gx && L >= 1, "upsample_bwd_blocks: null pointer");
-  VQ_REQUIRE(Tin >= 3 && Tout >= 8 * Tin && Tout % 4 == 0 && Tout / 4 <= 2 * UPS_NT && gy_bstride % 4 == 0 && gy_lstride % 4 == 0 &&
-             ((uintptr_t)gy) % 16 == 0 && ((uintptr_t)w0) % 16 == 0 && ((uintptr_t)w1) % 16 == 0 && (long)L * B * C < (1L << 31),
-             "upsample_bwd_blocks: serves ratios >= 8 with Tout %% 4 == 0, Tout <= %d", 8 * UPS_NT);
-  long nb = (long)L * B * C;
-  if (nb > 512) nb = 512;
-  if (bf16)
-    hipLaunchKernelGGL(upsample_bwd_seg_kernel<1>, dim3((unsigned)nb), dim3(UPS_NT), 0, (hipStream_t)s, reinterpret_cast<const float*>(gy), gy_bstride, B, C, Tin, Tout, w0, w1, lo0, hi0, lo1, hi1, gx, gx_bstride, nullptr, L, gy_lstride, gx_lstride);
-  else
-    hipLaunchKernelGGL(upsample_bwd_seg_kernel<0>, dim3((unsigned)nb), dim3(UPS_NT), 0, (hipStream_t)s, reinterpret_cast<const float*>(gy), gy_bstride, B, C, Tin, Tout, w0, w1, lo0, hi0, lo1, hi1, gx, gx_bstride, nullptr, L, gy_lstride, gx_lstride);
-  VQ_LAUNCH_CHECK();
+  bool served = false;
+  if (int e = launch_upsample_bwd_seg(bf16 ? 1 : 0, gy, 16, gy_lstride, gy_bstride, L, B, C, Tin, Tout, w0, w1, lo0, hi0, lo1, hi1, gx, gx_lstride, gx_bstride, nullptr, s, served)) return e;
+  VQ_REQUIRE(served, "upsample_bwd_blocks: serves ratios >= 8 with Tout %% 4 == 0, Tout <= %d", 8 * UPS_NT);
   return 0;
 }
 
@@ -1198,13 +1201,9 @@ int vqvae_upsample_linear_bwd_f16x2(const void* gy, long gy_bstride, int B, int 
                                     const int32_t* hi0, const int32_t* lo1, const int32_t* hi1, float* gx,
                                     long gx_bstride, const uint32_t* scale, vqvae_stream_t s) {
   VQ_REQUIRE(gy && w0 && w1 && lo0 && hi0 && lo1 && hi1 && gx && scale, "upsample_bwd_f16x2: null pointer");
-  VQ_REQUIRE(Tin >= 3 && Tout >= 8 * Tin && Tout % 4 == 0 && Tout / 4 <= 2 * UPS_NT && gy_bstride % 4 == 0 &&
-             ((uintptr_t)gy) % 16 == 0 && ((uintptr_t)w0) % 16 == 0 && ((uintptr_t)w1) % 16 == 0,
-             "upsample_bwd_f16x2: serves ratios >= 8 with Tout %% 4 == 0, Tout <= %d", 8 * UPS_NT);
-  int nb = B * C;
-  if (nb > 512) nb = 512;
-  hipLaunchKernelGGL(upsample_bwd_seg_kernel<2>, dim3(nb), dim3(UPS_NT), 0, (hipStream_t)s, reinterpret_cast<const float*>(gy), gy_bstride, B, C, Tin, Tout, w0, w1, lo0, hi0, lo1, hi1, gx, gx_bstride, scale, 1, 0L, 0L);
-  VQ_LAUNCH_CHECK();
+  bool served = false;
+  if (int e = launch_upsample_bwd_seg(2, gy, 16, 0L, gy_bstride, 1, B, C, Tin, Tout, w0, w1, lo0, hi0, lo1, hi1, gx, 0L, gx_bstride, scale, s, served)) return e;
+  VQ_REQUIRE(served, "upsample_bwd_f16x2: serves ratios >= 8 with Tout %% 4 == 0, Tout <= %d", 8 * UPS_NT);
   return 0;
 }
 

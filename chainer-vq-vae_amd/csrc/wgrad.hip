@@ -1318,26 +1318,30 @@ static int select_wgrad(const WgradArgs& w, const WgradPlan& p, bool fast, Wgrad
   // shape runs on wgrad3_kernel; both operands are activations, so falling back to mode 2 needs nothing re-packed
   const int mode = g_matmul_dtype == 3 ? ((w.f16x2 && fast) ? 3 : 2) : g_matmul_dtype;
   const bool big = w.M % 256 == 0;
+  // stored operands (Fmt): bf16 is mode 1's, pre-split a float32x2 launch's (their `amax` words are scale words, see presplit_pair)
+  const bool xs = w.x_fmt != FMT_F32, gs = w.gy_fmt != FMT_F32;
+  VQ_REQUIRE((w.x_fmt != FMT_BF16 && w.gy_fmt != FMT_BF16) || mode == 1, "wgrad: bf16-stored operands need matmul mode 1");
+  VQ_REQUIRE((w.x_fmt != FMT_F16X2 && w.gy_fmt != FMT_F16X2) || mode == 3, "wgrad: pre-split operands need a float32x2 launch");
   bool dma_shape = false;         // both operands stored: does the shape run on wgrad3_dma_kernel? (with any plan; the caller asks for a wide one when it knows)
-  if (w.x16 && w.g16) {
+  if (xs && gs) {
     int cins[MAXSEG];
     for (int i = 0; i < w.nseg; ++i) cins[i] = w.seg[i].cin;
     dma_shape = wgrad_dma_shape(w.M, w.Tout, cins, w.nseg);
   }
   f = WgradForm{WG_W3, big ? 4 : 2, 0, false, false, dim3(), 0};
-  if (g_matmul_dtype == 3 && (w.x16 || w.g16)) {        // pre-split operands (see presplit_pair): their `amax` words are scale words
-    VQ_REQUIRE(fast && mode == 3 && big, "wgrad: pre-split operands need a float32x2 launch on 256-row tiles");
-    f.NP = 2; f.X16 = w.x16 != 0; f.G16 = w.g16 != 0;
+  if (mode == 3 && (xs || gs)) {
+    VQ_REQUIRE(big, "wgrad: pre-split operands need 256-row tiles");
+    f.NP = 2; f.X16 = xs; f.G16 = gs;
     if (dma_shape) f.family = WG_DMA;
   } else if (fast && mode == 3) {
     f.NP = 2;
   } else if (fast && mode == 2) {
     f.NP = 3;
-  } else if (w.x16 || w.g16) {
-    bool ok16 = fast && mode == 1 && big && w.Tout % W2K == 0;
-    if (w.x16) for (int i = 0; i < w.nseg; ++i) ok16 = ok16 && w.seg[i].Tin == w.Tout;
-    VQ_REQUIRE(ok16, "wgrad: bf16-stored operands need matmul mode 1, stride-1 segments, 256-row tiles and T %% 16 == 0");
-    f.NP = 1; f.X16 = w.x16 != 0; f.G16 = w.g16 != 0;
+  } else if (xs || gs) {
+    bool ok16 = fast && big && w.Tout % W2K == 0;
+    if (xs) for (int i = 0; i < w.nseg; ++i) ok16 = ok16 && w.seg[i].Tin == w.Tout;
+    VQ_REQUIRE(ok16, "wgrad: bf16-stored operands need stride-1 segments, 256-row tiles and T %% 16 == 0");
+    f.NP = 1; f.X16 = xs; f.G16 = gs;
     // (wgrad3_dma_kernel<BF> takes two plan steps, 64 positions, at a time)
     if (dma_shape && w.Tout % 64 == 0 && p.steps_per_b % 2 == 0 && p.steps_per_split % 2 == 0) f.family = WG_DMA;
   } else if (fast && mode == 1) {
