@@ -957,7 +957,11 @@ extern "C" int vqvae_resstack_pack(const vqvae_resblock_desc* d, int nblocks,
     add(pack_bwd_job(w + L.pk_bd, p.Wd, d->Cd, d->Cr, d->K, ldr), w, HDR_BD);
   }
   if (int e = flush()) return e;
-  if (f16 && f16x2_storage_supported(d) && Ch <= 256) {       // the weight norms behind the pre-split tensors' bounds
+  // the weight norms behind the pre-split tensors' bounds: for every block of the stack -- d carries ONE block's dilation,
+  // and a first block whose dilation is refused pre-split storage (dil >= T) says nothing about the blocks behind it
+  vqvae_resblock_desc d1 = *d;
+  d1.dil = 1; d1.storage = 0;
+  if (f16 && f16x2_storage_supported(&d1) && Ch <= 256) {
     for (int l0 = 0; l0 < nblocks; l0 += MAXSEG) {
       L1Args la; memset(&la, 0, sizeof(la));
       la.Cr = d->Cr; la.Cs = d->Cs; la.Ch = Ch;

@@ -190,14 +190,32 @@ def _grad_out(var, shape):
     return DeviceArray(shape, np.float32)
 
 
-def _plan_storage(descs, packed, f16):
+def _pullback_forms(d0, Tl, f16):
+    """How the gh_l of a chain over a latent of Tl positions can be pulled back to the latent rate besides the plain
+    per-block launch over an fp32 gh_l: (fused, segmented).  fused: 'float32x2', inside the launch that produces gh_l
+    (vqvae_resblock_amax.pb_part: 128 gate channels, T % 128 == 0, T >= 64 Tl; FUSE_PULLBACK = False: not taken).
+    segmented: the domain of the kernel behind vqvae_upsample_linear_bwd_blocks / _bf16 / _f16x2 -- the only pull-back
+    that reads a STORED gh_l (csrc/misc.hip launch_upsample_bwd_seg)."""
+    fused = bool(f16 and FUSE_PULLBACK and _lib.load().vqvae_get_fused_pullback(C.byref(d0)) and d0.T >= 64 * Tl)
+    segmented = Tl >= 3 and d0.T >= 8 * Tl and d0.T % 4 == 0 and d0.T // 4 <= 2048
+    return fused, segmented
+
+
+def _plan_storage(descs, packed, f16, Tl=None):
     """vqvae_resblock_desc.storage of every block for the forward and the backward sweep, ([fwd], [bwd]), from one round of
     queries (they depend on a descriptor's geometry only).  Forward, packed chain only: the residual stream between the
     blocks kept as bf16 (BASELINE configs[4], mode 'bfloat16'; the buffers stay fp32-sized, half used) or, with ``f16``
     ('float32x2'), PRE-SPLIT (fp16 hi | lo dwords under an a-priori bound: its three readers stage it with two v_perm_b32
-    per element pair instead of splitting it again) -- every block but the last stores its residual output that way, every
-    block but the first reads it; and of tanh, sigmoid, z only the last two are saved (the backward takes tanh = z /
-    sigmoid).  Backward: those, plus gh_l as bf16 / pre-split and the gradient stream g_res_l = gx_{l+1} as bf16."""
+    per element pair instead of splitting it again); and of tanh, sigmoid, z only the last two are saved (the backward
+    takes tanh = z / sigmoid).  Backward: those, plus gh_l as bf16 / pre-split and the gradient stream g_res_l = gx_{l+1}
+    as bf16.
+
+    The rule: a tensor that crosses from block l to block l + 1 (x_{l+1}; g_res_l = gx_{l+1}) is stored in a format only
+    when the library offers that format to BOTH blocks -- the answers differ inside a chain (a dilation beyond the
+    sequence is refused pre-split storage) -- and a tensor one block owns (gh_l, the saved gates) from that block's own
+    answer.  No kernel reads a stored x_l and writes an fp32 x_{l+1} (rb_formats refuses it), so a block that cannot store
+    its output takes the stored stream from every block in front of it: it resumes, from fp32, behind that block.  And
+    gh_l is stored only where a pull-back can read it stored (``Tl``: the latent length; _pullback_forms)."""
     nb = len(descs)
     fwd = [0] * nb
     if not packed:
@@ -205,16 +223,27 @@ def _plan_storage(descs, packed, f16):
     lib = _lib.load()
     sup16 = [lib.vqvae_resblock_bf16_storage(C.byref(d)) if BF16_STORAGE else 0 for d in descs]
     supx2 = [lib.vqvae_resblock_f16x2_storage(C.byref(d)) if f16 else 0 for d in descs]
+    for sup, xbit, rbit in ((sup16, _lib.STORE_X_BF16, _lib.STORE_RES_BF16), (supx2, _lib.STORE_X_F16X2, _lib.STORE_RES_F16X2)):
+        both = [bool(a & xbit and a & rbit) for a in sup]
+        stored = [both[l] and both[l + 1] for l in range(nb - 1)]          # x_{l+1}, between block l and block l + 1
+        for l in range(nb - 3, -1, -1):                                    # block l + 1 reads x_{l+1} and writes x_{l+2}
+            stored[l] = stored[l] and stored[l + 1]
+        for l in range(nb - 1):
+            if stored[l]:
+                fwd[l] |= rbit
+                fwd[l + 1] |= xbit
+    bwd = list(fwd)
+    gh_ok = Tl is not None and any(_pullback_forms(descs[0], Tl, f16))
     for l in range(nb):
-        if sup16[l] & _lib.STORE_RES_BF16 and sup16[l] & _lib.STORE_X_BF16:
-            fwd[l] = (_lib.STORE_RES_BF16 if l < nb - 1 else 0) | (_lib.STORE_X_BF16 if l > 0 else 0)
-        if supx2[l] & _lib.STORE_RES_F16X2 and supx2[l] & _lib.STORE_X_F16X2:
-            fwd[l] = (_lib.STORE_RES_F16X2 if l < nb - 1 else 0) | (_lib.STORE_X_F16X2 if l > 0 else 0)
         fwd[l] |= supx2[l] & _lib.STORE_GATES_SIG
-    gh = supx2[0] & _lib.STORE_GH_F16X2 if f16 else sup16[0] & _lib.STORE_GH_BF16
-    gs = sup16[0] & _lib.STORE_GX_BF16 and sup16[0] & _lib.STORE_GRES_BF16
-    bwd = [fwd[l] | gh | (_lib.STORE_GX_BF16 if gs and l >= 1 else 0) | (_lib.STORE_GRES_BF16 if gs and l <= nb - 2 else 0)
-           for l in range(nb)]
+        bwd[l] |= supx2[l] & _lib.STORE_GATES_SIG
+        if gh_ok:
+            bwd[l] |= (supx2[l] & _lib.STORE_GH_F16X2) if f16 else (sup16[l] & _lib.STORE_GH_BF16)
+    gs = [bool(a & _lib.STORE_GX_BF16 and a & _lib.STORE_GRES_BF16) for a in sup16]
+    for l in range(nb - 1):                                                # g_res_l = gx_{l+1}
+        if gs[l] and gs[l + 1]:
+            bwd[l] |= _lib.STORE_GRES_BF16
+            bwd[l + 1] |= _lib.STORE_GX_BF16
     return fwd, bwd
 
 
@@ -255,7 +284,7 @@ class _Sweep(object):
     """What the phases of one ResidualStackFunction.backward share.  Everything the side stream reads or writes is referenced
     from here or from the node until the join is enqueued or backend.defer_to_side has it (the invariant in backend.py)."""
     __slots__ = ('indexes', 'cond', 'blocks', 'pvars',       # what was asked for; the inputs as arrays / Variables per block
-                 'g_skip', 'gh_store', 'hpre',               # the incoming gradient; gh_l's storage bit; gh_l is pre-split
+                 'g_skip', 'gh_store', 'hpre',               # the incoming gradient; per block: gh_l's storage bit; gh_l is pre-split
                  'overlap', 'side', 'defer',                 # two-stream sweep and its stream; deferred weight gradients
                  'tb', 'Tl', 'gP', 'pb_part', 'gh_all',      # latent-rate condition: tables, pulled-back gh, its two batched forms
                  'dil_group', 'ws_side', 'ws_defer',         # dilated wgrad blocks per launch; scratch of the two side uses
@@ -309,7 +338,8 @@ class ResidualStackFunction(FunctionNode):
         elif f16:
             _lib.call('vqvae_absmax', x.ptr, x.size, self.words.x(0), _S())
         self.packed, self.packed_stride, self._skipws = self._stack_slabs(inputs[2:], blocks) if pack else (None, 0, None)
-        self.storage = _plan_storage(self.descs, pack, f16)
+        self.pullback = _pullback_forms(self.descs[0], self.lat.shape[2], f16) if self.lat is not None else (False, False)
+        self.storage = _plan_storage(self.descs, pack, f16, self.lat.shape[2] if self.lat is not None else None)
         self.saved = []
         h = x
         for i, b in enumerate(blocks):
@@ -407,12 +437,11 @@ class ResidualStackFunction(FunctionNode):
         return skip
 
     def _check_contract(self, hpre):
-        """'float32x2': every pre-split tensor of this sweep -- x_l (l >= 1) and, with `hpre`, gh_l -- against the bound it was
+        """'float32x2': every pre-split tensor of this sweep -- x_l (l >= 1) and the gh_l with `hpre[l]` -- against the bound it was
         split under (backend.f32x2_contract_violations; one launch, no host round trip unless backend.contract_debug())."""
         w, nb = self.words, len(self.descs)
         pairs = [(w.x_scale(l), w.x(l)) for l in range(1, nb) if self.descs[l].storage & _lib.STORE_X_F16X2]
-        if hpre:
-            pairs += [(w.gh_scale(l), w.gh(l)) for l in range(nb)]
+        pairs += [(w.gh_scale(l), w.gh(l)) for l in range(nb) if hpre[l]]
         if not pairs:
             return
         global LAST_CONTRACT_WORDS
@@ -493,8 +522,8 @@ class ResidualStackFunction(FunctionNode):
                 _lib.call('vqvae_absmax', g_skip.ptr, g_skip.size, w.g_skip(), _S())
         for d, bits in zip(self.descs, self.storage[1]):
             d.storage = bits
-        s.gh_store = self.storage[1][0] & (_lib.STORE_GH_BF16 | _lib.STORE_GH_F16X2)
-        s.hpre = bool(s.gh_store & _lib.STORE_GH_F16X2)
+        s.gh_store = [bits & (_lib.STORE_GH_BF16 | _lib.STORE_GH_F16X2) for bits in self.storage[1]]
+        s.hpre = [bool(g & _lib.STORE_GH_F16X2) for g in s.gh_store]
         s.overlap = backend.overlap_enabled()
         s.side = backend.side_stream() if s.overlap else _S()
         s.ghs, s.g_ress, s.dil_pending = [None] * nb, [None] * nb, []
@@ -512,14 +541,14 @@ class ResidualStackFunction(FunctionNode):
         # costs -- configs[4] 18.8 -> 20.4 ms -- so it keeps its pull-back launches)
         # -- where the library's gate-derivative launch can carry it (128 gate channels; the 512-channel decoder's gh_l are pulled
         # back by a launch per block on the side stream, below)
-        if (w is not None and FUSE_PULLBACK and _lib.load().vqvae_get_fused_pullback(C.byref(d0))
-                and d0.T >= 64 * s.Tl):
+        if self.pullback[0]:
             s.pb_part = DeviceArray((nb, d0.B, d0.T // 128, d0.Cd, 4), np.float32)
         # where the pull-back stays a kernel of its own (bf16 mode, float32x3, fp32 MFMA): ONE launch over all blocks' gh when
         # the chain is done (vqvae_upsample_linear_bwd_blocks) instead of a launch per block -- the gh_l then are the
         # slices of one array.  BATCH_PULLBACK = False: a launch per block, as before (same sums in the same order)
-        if (BATCH_PULLBACK and s.pb_part is None and self.packed is not None and not s.overlap and not s.hpre
-                and s.Tl >= 3 and d0.T >= 8 * s.Tl and d0.T % 4 == 0 and d0.T // 4 <= 2048
+        if (BATCH_PULLBACK and s.pb_part is None and self.packed is not None and not s.overlap and not any(s.hpre)
+                and len(set(s.gh_store)) == 1
+                and self.pullback[1]
                 and all((dd.B, dd.Cd, dd.T) == (d0.B, d0.Cd, d0.T) for dd in self.descs)):
             s.gh_all = DeviceArray((nb, d0.B, d0.Cd, d0.T), np.float32)
         return s
@@ -582,7 +611,7 @@ class ResidualStackFunction(FunctionNode):
                 am = C.byref(_lib.ResblockAmax(
                     None, None, None if g_res is None else w.g_res(i), w.g_skip(),
                     w.gh(i), w.g_res(i - 1) if (gx is not None and i > 0) else None,
-                    None, None, w.gh_scale(i) if s.hpre else None,
+                    None, None, w.gh_scale(i) if s.hpre[i] else None,
                     (s.pb_part.ptr + i * (s.pb_part.nbytes // len(self.descs))) if s.pb_part is not None else None,
                     s.tb['v0'].ptr, s.tb['w0'].ptr, s.tb['w1'].ptr, s.Tl))
             _lib.call('vqvae_resblock_bwd_packed', C.byref(d), C.byref(prm), h.ptr, gates.ptr,
@@ -602,11 +631,11 @@ class ResidualStackFunction(FunctionNode):
         dst, tabs = s.gP.ptr + i * d.Cd * s.Tl * 4, [tb[k].ptr for k in ('w0', 'w1', 'lo0', 'hi0', 'lo1', 'hi1')]
         if s.pb_part is not None or s.gh_all is not None:
             pass                       # done in the gate-derivative launch's epilogue and reduced below / one launch after the chain
-        elif s.hpre:
+        elif s.hpre[i]:
             _lib.call('vqvae_upsample_linear_bwd_f16x2', s.ghs[i].ptr, d.Cd * d.T, d.B, d.Cd, s.Tl, d.T,
                       *(tabs + [dst, nb * d.Cd * s.Tl, self.words.gh_scale(i), s.side]))
         else:
-            _lib.call('vqvae_upsample_linear_bwd_bf16' if s.gh_store & _lib.STORE_GH_BF16 else 'vqvae_upsample_linear_bwd',
+            _lib.call('vqvae_upsample_linear_bwd_bf16' if s.gh_store[i] & _lib.STORE_GH_BF16 else 'vqvae_upsample_linear_bwd',
                       s.ghs[i].ptr, d.Cd * d.T, d.B, d.Cd, s.Tl, d.T, *(tabs + [dst, nb * d.Cd * s.Tl, s.side]))
         # the fused pull-back's partial sums of the blocks the chain has passed, PB_REDUCE_GROUP at a time (round 5: ~15 us
         # between two chip-filling launches instead of one launch over all blocks in the tail -- 52 us alone, 160 us beside
@@ -619,23 +648,27 @@ class ResidualStackFunction(FunctionNode):
     def _dil_wgrad(self, s, stream, ws):
         """Dilated-conv weight gradients of the pending blocks (their gh exist), dil_group blocks at a time."""
         pending, s.dil_pending = s.dil_pending, []
-        w, d0 = self.words, self.descs[0]
+        w = self.words
         for at in range(0, len(pending), s.dil_group):
             blocks = pending[at:at + s.dil_group]
             if s.overlap:
                 backend.wait_event(s.side, backend.Event().record(_S()))    # their gh are complete
-            # one launch per kind of x: the blocks whose input is the bf16 / pre-split residual stream, and the rest (block 0)
-            for x16 in (_lib.STORE_X_BF16, _lib.STORE_X_F16X2, 0):
-                sel = [i for i in blocks if (self.descs[i].storage & (_lib.STORE_X_BF16 | _lib.STORE_X_F16X2)) == x16]
+            # one launch per kind of (x, gh): the blocks whose input is the bf16 / pre-split residual stream, and the rest
+            # (block 0; the blocks around one that is refused pre-split storage), each with the blocks that keep gh alike
+            kinds = [(x16, g16) for x16 in (_lib.STORE_X_BF16, _lib.STORE_X_F16X2, 0)
+                     for g16 in sorted(set(s.gh_store), reverse=True)]
+            for x16, g16 in kinds:
+                sel = [i for i in blocks if (self.descs[i].storage & (_lib.STORE_X_BF16 | _lib.STORE_X_F16X2)) == x16
+                       and s.gh_store[i] == g16]
                 if not sel:
                     continue
-                dg = _lib.ResblockDesc.from_buffer_copy(d0)
-                dg.storage = s.gh_store | x16
+                dg = _lib.ResblockDesc.from_buffer_copy(self.descs[sel[0]])      # (a block the library offers these bits)
+                dg.storage = g16 | x16
                 dils = (C.c_int * len(sel))(*[self.dilations[i] for i in sel])
                 xam = gam = None
                 if w is not None:      # (a pre-split operand is read under the bound it was split under: its scale words)
                     xam = (C.c_void_p * len(sel))(*[w.x_scale(i) if x16 == _lib.STORE_X_F16X2 else w.x(i) for i in sel])
-                    gam = (C.c_void_p * len(sel))(*[w.gh_scale(i) if s.hpre else w.gh(i) for i in sel])
+                    gam = (C.c_void_p * len(sel))(*[w.gh_scale(i) if s.hpre[i] else w.gh(i) for i in sel])
                 _lib.call('vqvae_resstack_dil_wgrad', C.byref(dg), len(sel), dils,
                           _lib.ptr_array([self.saved[i][0] for i in sel]), _lib.ptr_array([s.ghs[i] for i in sel]),
                           _lib.ptr_array([s.g[i]['Wd'] for i in sel]), _lib.ptr_array([s.g[i]['bd'] for i in sel]),
@@ -665,7 +698,7 @@ class ResidualStackFunction(FunctionNode):
         d, nb, lat, tb = self.descs[0], len(self.descs), self.lat, s.tb
         Cc = lat.shape[1]
         if s.gh_all is not None:       # neither the fused nor the per-block pull-back ran: ONE launch over all blocks' gh
-            bf = 1 if s.gh_store & _lib.STORE_GH_BF16 else 0
+            bf = 1 if s.gh_store[0] & _lib.STORE_GH_BF16 else 0
             _lib.call('vqvae_upsample_linear_bwd_blocks', s.gh_all.ptr, bf, d.B * d.Cd * d.T * (2 if bf else 1), d.Cd * d.T,
                       nb, d.B, d.Cd, s.Tl, d.T, tb['w0'].ptr, tb['w1'].ptr, tb['lo0'].ptr, tb['hi0'].ptr, tb['lo1'].ptr,
                       tb['hi1'].ptr, s.gP.ptr, d.Cd * s.Tl, nb * d.Cd * s.Tl, _S())
