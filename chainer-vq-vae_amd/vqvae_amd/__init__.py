@@ -7,6 +7,7 @@ from .core import (Chain, ChainList, FunctionNode, Link, Parameter, Variable,  #
 from .codebook import CodebookMonitor  # noqa: F401
 from .codebook_ema import EMACodebook  # noqa: F401
 from .codebook_init import KMeansCodebookInit, kmeans_init  # noqa: F401
+from .optimizers import GradientClipping, GradientNorms, NonFiniteGuard  # noqa: F401
 from .net import VAE, ConditionEmbed, Encoder  # noqa: F401
 from .updaters import (VQVAE_ParallelUpdater, VQVAE_StandardUpdater,  # noqa: F401
                        concat_examples)

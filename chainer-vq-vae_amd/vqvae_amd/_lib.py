@@ -256,6 +256,22 @@ KMEANS_BLOCK = 256                # VQVAE_KMEANS_BLOCK
 KMEANS_MAX_N = 1 << 24            # VQVAE_KMEANS_MAX_N
 KMEANS_MAX_D = 4096               # VQVAE_KMEANS_MAX_D
 
+# include/vqvae_optim.h: optimizer hooks (gradient norms, clipping, the non-finite guard), a fifth table and version
+OPTIM_PROTOTYPES = {
+    'vqvae_optim_abi_version': (c_int, []),
+    'vqvae_optim_plan_items': (c_int, [C.POINTER(C.c_int64), c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'vqvae_optim_workspace_bytes': (c_size_t, [c_int]),
+    'vqvae_optim_state_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'vqvae_optim_sumsq': (c_int, [P, c_size_t, P, c_int, P, c_int, P, P, c_int, c_int, c_double, c_int, P, P, c_size_t, P]),
+    'vqvae_optim_adam_step_hooked': (c_int, [P, P, P, P, c_size_t, c_double, P, P, c_double, c_double, c_double, P,
+                                             c_int, P]),
+}
+OPTIM_ABI_VERSION = 1             # vqvae_optim_abi_version()
+OPTIM_CHUNK = 4096                # VQVAE_OPTIM_CHUNK
+OPTIM_THREADS = 256               # VQVAE_OPTIM_THREADS
+OPTIM_STATE_HEADER = 64           # VQVAE_OPTIM_STATE_HEADER
+OPTIM_GUARD = 1                   # VQVAE_OPTIM_GUARD
+
 # elementwise op codes / profiler tags (mirror the header)
 MAX_STACK_GROUP = 24              # blocks per resstack call (MAXSEG in csrc/gemm_common.h)
 STORE_X_BF16, STORE_RES_BF16 = 2, 4
@@ -298,7 +314,7 @@ def load():
     # Must be in the environment before the HSA runtime initialises (first HIP call).
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     lib = C.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES, KMEANS_PROTOTYPES):
+    for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES, KMEANS_PROTOTYPES, OPTIM_PROTOTYPES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)           # AttributeError if the symbol is missing
             fn.restype = res
@@ -315,6 +331,9 @@ def load():
     if lib.vqvae_kmeans_abi_version() != KMEANS_ABI_VERSION:
         raise ImportError('libvqvae_hip.so at %s has k-means ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
                           % (LIB_PATH, lib.vqvae_kmeans_abi_version(), KMEANS_ABI_VERSION))
+    if lib.vqvae_optim_abi_version() != OPTIM_ABI_VERSION:
+        raise ImportError('libvqvae_hip.so at %s has optimizer-hook ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
+                          % (LIB_PATH, lib.vqvae_optim_abi_version(), OPTIM_ABI_VERSION))
     _lib = lib
     return lib
 
