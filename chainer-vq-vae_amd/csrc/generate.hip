@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "../../include/vqvae_sampling.h"
 
 namespace vq {
 
@@ -261,13 +262,12 @@ __global__ __launch_bounds__(256) void gen_finish_kernel(GenFinishArgs a) {
   if (tid == 0) *a.step = t + 1;
 }
 
-int gen_step_lockstep(const vqvae_gen_desc* d, hipStream_t st);   // generate_lockstep.hip: the batch in MFMA columns
+int gen_step_lockstep(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st);   // generate_lockstep.hip: the batch in MFMA columns
+int gen_finish_sampled(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st);  // sampling.hip: finish + advance
 
-}  // namespace vq
-
-using namespace vq;
-
-extern "C" int vqvae_wavenet_gen_step(const vqvae_gen_desc* d, vqvae_stream_t s) {
+// One step.  smp == nullptr: vqvae_wavenet_gen_step; else the sampling controls of include/vqvae_sampling.h, which
+// replace the finish launch and nothing else.
+int gen_step_impl(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st) {
   VQ_REQUIRE(d, "gen_step: null descriptor");
   VQ_REQUIRE(d->n >= 1 && d->n <= VQVAE_GEN_MAX_LOCKSTEP, "gen_step: n must be 1..%d sequences (got %d)", VQVAE_GEN_MAX_LOCKSTEP, d->n);
   VQ_REQUIRE(d->n_blocks >= 1 && d->blocks, "gen_step: no residual blocks");
@@ -282,8 +282,7 @@ extern "C" int vqvae_wavenet_gen_step(const vqvae_gen_desc* d, vqvae_stream_t s)
     if (d->sample_mode == VQVAE_GEN_SOFTMAX) VQ_REQUIRE(d->out_dim <= GEN_MAXOUT, "gen_step: at most %d classes", GEN_MAXOUT);
     else VQ_REQUIRE(d->out_dim % 3 == 0 && d->n_uniform >= d->out_dim / 3, "gen_step: mixture sampling needs out_dim = 3*nr_mix and nr_mix uniforms");
   }
-  hipStream_t st = (hipStream_t)s;
-  if (d->n > GEN_NB) return gen_step_lockstep(d, st);   // n <= 4: the kernels above, as before
+  if (d->n > GEN_NB) return gen_step_lockstep(d, smp, st);   // n <= 4: the kernels above, as before
   const int n = d->n, R = d->residual, half = d->dilated / 2;
 
   GenConvArgs e{};   // embed: pad-free 2-tap conv on [previous input, current input] (modules.py:234, 247-248)
@@ -327,6 +326,7 @@ extern "C" int vqvae_wavenet_gen_step(const vqvae_gen_desc* d, vqvae_stream_t s)
   p2.njobs = 1; p2.n = n; p2.step = d->step; p2.max_steps = d->max_steps;
   hipLaunchKernelGGL(gen_dense_kernel, dim3(cdiv(d->out_dim, 4)), dim3(256), 0, st, p2);
   VQ_LAUNCH_CHECK();
+  if (smp) return gen_finish_sampled(d, smp, st);
 
   GenFinishArgs f{};
   f.logits = d->logits; f.uniforms = d->uniforms; f.forced = d->forced_next; f.out = d->out; f.out_bstride = d->out_bstride;
@@ -337,6 +337,12 @@ extern "C" int vqvae_wavenet_gen_step(const vqvae_gen_desc* d, vqvae_stream_t s)
   VQ_LAUNCH_CHECK();
   return 0;
 }
+
+}  // namespace vq
+
+using namespace vq;
+
+extern "C" int vqvae_wavenet_gen_step(const vqvae_gen_desc* d, vqvae_stream_t s) { return gen_step_impl(d, nullptr, (hipStream_t)s); }
 
 // =================================================================================================
 // Persistent generation kernel ("megakernel"): the whole loop of generate.py:105-145 in ONE launch.

@@ -18,6 +18,7 @@
 //   * columns >= n, rows past the matrix and k past K are predicated: never loaded, never stored (operands read as 0).
 // Launch shape for the default decoder at n = 128: gate 32 x 8 = 256 workgroups, res + skip 48 x 8 = 384.
 #include "common.h"
+#include "../../include/vqvae_sampling.h"
 
 namespace vq {
 
@@ -303,8 +304,10 @@ static int ls_launch(const LsGemmArgs& g, hipStream_t st) {
 }
 
 // One step for 5..VQVAE_GEN_MAX_LOCKSTEP sequences; vqvae_wavenet_gen_step (generate.hip) has validated the descriptor's
-// dimensions, head weights, state buffers and sampling fields.
-int gen_step_lockstep(const vqvae_gen_desc* d, hipStream_t st) {
+// dimensions, head weights, state buffers and sampling fields.  smp != nullptr (include/vqvae_sampling.h): the filtered
+// sampler of sampling.hip takes the place of the finish and advance launches.
+int gen_finish_sampled(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st);
+int gen_step_lockstep(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st) {
   VQ_REQUIRE(d->n >= 1 && d->n <= VQVAE_GEN_MAX_LOCKSTEP, "gen_step: n must be 1..%d sequences (got %d)", VQVAE_GEN_MAX_LOCKSTEP, d->n);
   VQ_REQUIRE(d->sample_mode != VQVAE_GEN_SOFTMAX || d->out_dim <= LS_MAXOUT, "gen_step: at most %d classes", LS_MAXOUT);
   const int n = d->n, R = d->residual, half = d->dilated / 2;
@@ -349,6 +352,7 @@ int gen_step_lockstep(const vqvae_gen_desc* d, hipStream_t st) {
   p2.out0 = d->logits;
   if ((rc = ls_launch(p2, st)) != 0) return rc;
 
+  if (smp) return gen_finish_sampled(d, smp, st);
   if (d->sample_mode != VQVAE_GEN_NONE) {
     LsFinishArgs f{};
     f.logits = d->logits; f.uniforms = d->uniforms; f.forced = d->forced_next; f.out = d->out; f.out_bstride = d->out_bstride;

@@ -70,6 +70,11 @@ class GenDesc(C.Structure):
                    ('out_bstride', c_long), ('logits_out', P), ('max_steps', c_int)])
 
 
+class GenSampling(C.Structure):
+    """vqvae_gen_sampling (include/vqvae_sampling.h): device arrays of n entries, NULL = neutral for every sequence."""
+    _fields_ = [(n, P) for n in ('temperature', 'top_k', 'top_p')]
+
+
 # name -> (restype, argtypes); this table IS the list of symbols the header declares
 PROTOTYPES = {
     'vqvae_last_error_string': (c_char_p, []),
@@ -272,6 +277,15 @@ OPTIM_THREADS = 256               # VQVAE_OPTIM_THREADS
 OPTIM_STATE_HEADER = 64           # VQVAE_OPTIM_STATE_HEADER
 OPTIM_GUARD = 1                   # VQVAE_OPTIM_GUARD
 
+# include/vqvae_sampling.h: sampling controls for generation (temperature, top-k, top-p, greedy), a sixth table and version
+SAMPLING_PROTOTYPES = {
+    'vqvae_sampling_abi_version': (c_int, []),
+    'vqvae_wavenet_gen_step_sampled': (c_int, [C.POINTER(GenDesc), C.POINTER(GenSampling), P]),
+    'vqvae_sample_logits': (c_int, [P, c_int, c_int, c_int, c_float, P, c_int, C.POINTER(GenSampling), P, P, P]),
+}
+SAMPLING_ABI_VERSION = 1          # vqvae_sampling_abi_version()
+SAMPLING_MAX_CLASSES = 1024       # VQVAE_SAMPLING_MAX_CLASSES
+
 # elementwise op codes / profiler tags (mirror the header)
 MAX_STACK_GROUP = 24              # blocks per resstack call (MAXSEG in csrc/gemm_common.h)
 STORE_X_BF16, STORE_RES_BF16 = 2, 4
@@ -314,7 +328,8 @@ def load():
     # Must be in the environment before the HSA runtime initialises (first HIP call).
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     lib = C.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES, KMEANS_PROTOTYPES, OPTIM_PROTOTYPES):
+    for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES, KMEANS_PROTOTYPES, OPTIM_PROTOTYPES,
+                  SAMPLING_PROTOTYPES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)           # AttributeError if the symbol is missing
             fn.restype = res
@@ -334,6 +349,9 @@ def load():
     if lib.vqvae_optim_abi_version() != OPTIM_ABI_VERSION:
         raise ImportError('libvqvae_hip.so at %s has optimizer-hook ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
                           % (LIB_PATH, lib.vqvae_optim_abi_version(), OPTIM_ABI_VERSION))
+    if lib.vqvae_sampling_abi_version() != SAMPLING_ABI_VERSION:
+        raise ImportError('libvqvae_hip.so at %s has sampling ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
+                          % (LIB_PATH, lib.vqvae_sampling_abi_version(), SAMPLING_ABI_VERSION))
     _lib = lib
     return lib
 

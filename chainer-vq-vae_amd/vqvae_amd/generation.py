@@ -19,6 +19,77 @@ _S = backend.stream
 _INT_MAX = 2 ** 31 - 1
 
 
+def sampling_controls(n, temperature=None, top_k=None, top_p=None, use_logistic=False, who='generate_sequence'):
+    """The sampling controls of include/vqvae_sampling.h as host arrays, validated: each of ``temperature`` (>= 0 and
+    finite; 0 = greedy), ``top_k`` (integers >= 0; 0 or >= out_dim = off) and ``top_p`` (in (0, 1]; 1 = off) is None, a
+    scalar or a sequence of ``n`` values, one per sequence.  Returns None when all three are None (the caller then takes
+    the path it took before the controls existed), else the tuple (float32 (n,), int32 (n,), float32 (n,)) with None in
+    the place of a control that was not given.  The mixture-of-logistics output takes a temperature > 0 only.
+    Everything else is a ValueError: the device cannot refuse a value, it reads a bad one as neutral."""
+    if temperature is None and top_k is None and top_p is None:
+        return None
+
+    def per_sequence(v, name, dtype):
+        if v is None:
+            return None
+        a = np.asarray(v)
+        if a.dtype.kind not in 'iuf' or (dtype == np.int32 and a.dtype.kind == 'f' and not (a == np.floor(a)).all()):
+            raise ValueError('%s: %s must be %s, got %r' % (who, name, 'integers' if dtype == np.int32 else 'numbers', v))
+        if a.ndim == 0:
+            a = np.full((n,), a)
+        if a.shape != (n,):
+            raise ValueError('%s: %s must be a scalar or one value per sequence (%d), got shape %s' % (who, name, n, a.shape))
+        return a
+
+    t = per_sequence(temperature, 'temperature', np.float32)
+    k = per_sequence(top_k, 'top_k', np.int32)
+    p = per_sequence(top_p, 'top_p', np.float32)
+    if t is not None and not (np.isfinite(t).all() and (t >= 0).all()):
+        raise ValueError('%s: temperature must be finite and >= 0, got %r' % (who, temperature))
+    if k is not None and not ((k >= 0).all() and (k <= _INT_MAX).all()):
+        raise ValueError('%s: top_k must be >= 0 (0 = off), got %r' % (who, top_k))
+    if p is not None and not ((p > 0).all() and (p <= 1).all()):          # a NaN fails both comparisons
+        raise ValueError('%s: top_p must be in (0, 1] (1 = off), got %r' % (who, top_p))
+    if use_logistic:
+        if k is not None or p is not None:
+            raise ValueError('%s: top_k and top_p truncate a categorical output; the mixture of logistics '
+                             '(use_logistic) takes a temperature only' % who)
+        if (t == 0).any():
+            raise ValueError('%s: temperature 0 (greedy) needs the softmax output; the mixture of logistics '
+                             '(use_logistic) takes a temperature > 0' % who)
+    return (None if t is None else t.astype(np.float32), None if k is None else k.astype(np.int32),
+            None if p is None else p.astype(np.float32))
+
+
+def _upload_controls(sampling):
+    """(GenSampling, the device arrays it points to) for the tuple sampling_controls returns."""
+    arrays = [None if a is None else backend.to_device(np.ascontiguousarray(a)) for a in sampling]
+    s = _lib.GenSampling()
+    s.temperature, s.top_k, s.top_p = [None if a is None else a.ptr for a in arrays]
+    return s, arrays
+
+
+def sample_logits(logits, uniforms, mode=_lib.GEN_SOFTMAX, temperature=None, top_k=None, top_p=None, log_scale_min=-40.0,
+                  return_probs=False):
+    """The sampler of a generation step on logits of the caller's own (vqvae_sample_logits): device float32 (n, out_dim),
+    host doubles ``uniforms`` (n,) for the softmax output or (n, nr_mix) for the mixture of logistics, the controls as in
+    sampling_controls.  Returns the device array (n,) of int32 classes or float32 values (and, with ``return_probs``, the
+    filtered probabilities (n, out_dim) the draw used; softmax output only)."""
+    backend.require_device(logits)
+    n, out_dim = logits.shape
+    softmax = mode == _lib.GEN_SOFTMAX
+    sampling = sampling_controls(n, temperature, top_k, top_p, not softmax, 'sample_logits')
+    u = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(n, -1)
+    u_dev = backend.to_device(u.reshape(-1))
+    out = backend.zeros((n,), np.int32 if softmax else np.float32)
+    probs = DeviceArray((n, out_dim), np.float32) if return_probs else None
+    s, keep = (None, None) if sampling is None else _upload_controls(sampling)
+    _lib.call('vqvae_sample_logits', logits.ptr, n, out_dim, mode, float(log_scale_min), u_dev.ptr, u.shape[1],
+              None if s is None else C.byref(s), out.ptr, None if probs is None else probs.ptr, _S())
+    backend.synchronize()                                   # u_dev and the control arrays go out of scope here
+    return (out, probs) if return_probs else out
+
+
 class GenerationState(object):
     """Device state behind WaveNet.initialize(n): zero queues (modules.py:58-67, 232-244) as
     per-block rings of ``dilation`` slots, the 2-sample embed queue, the step counter."""
@@ -101,7 +172,10 @@ class GenerationState(object):
 
     # ---- the whole loop of generate.py:105-145 on the device ----------------------------------
     def run(self, condition, uniforms, mode, n_steps=None, forced=None, return_logits=False,
-            graph_steps=8, persistent=False, chunk=4096):
+            graph_steps=8, persistent=False, chunk=4096, sampling=None):
+        """``sampling``: None or the tuple of sampling_controls(n, ...).  With controls every step ends in the filtered
+        sampler of csrc/sampling.hip (vqvae_wavenet_gen_step_sampled) and ``persistent`` is not honoured: the persistent
+        kernel has no filtered form, the run is a replayed hipGraph of per-step launches."""
         n = self.n
         if condition.ndim == 4:
             condition = condition.reshape(condition.shape[:3])
@@ -135,6 +209,15 @@ class GenerationState(object):
         if int(self.step.get()[0]) != 0:
             raise RuntimeError('generate_sequence starts from fresh queues: call initialize(n) first')
         d.max_steps = steps
+        if sampling is None:
+            def step():
+                _lib.call('vqvae_wavenet_gen_step', C.byref(d), _S())
+        else:
+            smp, self._controls = _upload_controls(sampling)
+            persistent = False
+
+            def step():
+                _lib.call('vqvae_wavenet_gen_step_sampled', C.byref(d), C.byref(smp), _S())
         nbytes = 0
         if steps and persistent:
             # the library picks the width class (<= 256 or <= 512 channels per vector); shapes outside
@@ -156,7 +239,7 @@ class GenerationState(object):
             self.step.set(np.array([steps], np.int32))
         elif steps and not graph_steps:                # eager launches (profilers, debugging)
             for _ in range(steps):
-                _lib.call('vqvae_wavenet_gen_step', C.byref(d), _S())
+                step()
             backend.synchronize()
         elif steps:
             per = max(1, min(int(graph_steps), steps))
@@ -164,7 +247,7 @@ class GenerationState(object):
             _lib.call('vqvae_graph_capture_begin', _S())
             try:
                 for _ in range(per):
-                    _lib.call('vqvae_wavenet_gen_step', C.byref(d), _S())
+                    step()
             finally:
                 _lib.call('vqvae_graph_capture_end', _S(), C.byref(graph))
             try:
@@ -281,7 +364,7 @@ def _device_group_runner(wavenet, condition, mode, graph_steps, return_logits):
     array, a replayed hipGraph of per-step launches on the main stream."""
     N, Cc, T = condition.shape
 
-    def run_group(idx, u, forced, steps):
+    def run_group(idx, u, forced, steps, sampling=None):
         n = len(idx)
         if (np.diff(idx) == 1).all():
             cview = condition.flat_view(int(idx[0]) * Cc * T, n * Cc * T, (n, Cc, T))
@@ -290,7 +373,7 @@ def _device_group_runner(wavenet, condition, mode, graph_steps, return_logits):
             backend.copy_many([(cview.flat_view(j * Cc * T, Cc * T), condition.flat_view(int(i) * Cc * T, Cc * T))
                                for j, i in enumerate(idx)])
         st = LockstepState(wavenet, n)
-        res = st.run(cview, u, mode, steps, forced, return_logits, graph_steps, persistent=False)
+        res = st.run(cview, u, mode, steps, forced, return_logits, graph_steps, persistent=False, sampling=sampling)
         if return_logits:
             return res[0].get(), res[1].get()[:steps]
         return res.get(), None
@@ -298,7 +381,7 @@ def _device_group_runner(wavenet, condition, mode, graph_steps, return_logits):
 
 
 def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None, forced=None, return_logits=False,
-                 graph_steps=8, group=_lib.GEN_MAX_LOCKSTEP, _run_group=None):
+                 graph_steps=8, group=_lib.GEN_MAX_LOCKSTEP, _run_group=None, sampling=None):
     """Many sequences at once (converting a validation set or a corpus): N sequences of any count as groups of
     <= ``group`` (<= 128) lockstep sequences, each group a replayed hipGraph of ``graph_steps`` per-step launches
     (0 = eager launches), the groups one after another on the main stream.  The weights are streamed once per
@@ -309,7 +392,9 @@ def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None,
     that length, and its output columns from lengths[i] - 1 on are 0.
     Returns the host array (N, T) in the caller's order (and, with ``return_logits``, the host array
     (max steps, N, out_dim), rows past a sequence's own steps 0).  Every sequence gets the values it gets in any
-    other batch of 5..128 and in any other position of it, bit for bit."""
+    other batch of 5..128 and in any other position of it, bit for bit.
+    ``sampling``: None or the tuple of sampling_controls(N, ...); every group gets its members' values, gathered with the
+    group's indices like the uniforms (repeats of the last member included), and the promise above holds with them."""
     if condition.ndim == 4:
         condition = condition.reshape(condition.shape[:3])
     N, Cc, T = condition.shape
@@ -335,7 +420,10 @@ def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None,
     for idx, gsteps in groups:
         ug = np.ascontiguousarray(u[:max(gsteps, 1), idx, :n_uniform])
         fg = None if forced is None else np.ascontiguousarray(forced[:gsteps, idx])
-        o, lg = run_group(idx, ug, fg, gsteps)
+        if sampling is None:
+            o, lg = run_group(idx, ug, fg, gsteps)
+        else:
+            o, lg = run_group(idx, ug, fg, gsteps, tuple(None if a is None else a[idx] for a in sampling))
         for j, i in enumerate(idx):
             out[i, :steps[i]] = o[j, :steps[i]]           # a shorter sequence kept running: its tail is discarded
             if return_logits:

@@ -14,7 +14,8 @@ from .utils import MuLaw
 
 
 def synthesize(encoder, vq, decoder, condition_embed, x_enc, global_condition, rng=None,
-               quantize=256, use_logistic=False, n_steps=None, persistent=True, lockstep=False):
+               quantize=256, use_logistic=False, n_steps=None, persistent=True, lockstep=False,
+               temperature=None, top_k=None, top_p=None):
     """generate.py:100-148.
 
     encoder / vq / decoder / condition_embed: device-resident links (decoder = the WaveNet, EMA or
@@ -26,6 +27,8 @@ def synthesize(encoder, vq, decoder, condition_embed, x_enc, global_condition, r
         (softmax output) or nr_mix per step (mixture of logistics), in the reference's order.
     lockstep: any number of waveforms; the decoder advances them together through WaveNet.generate_lockstep
         (groups of <= 128) instead of generate_sequence (n <= 4).
+    temperature / top_k / top_p: sampling controls, handed to generate_sequence / generate_lockstep as they are (None, a
+        scalar or one value per waveform); with any of them generate_sequence leaves the persistent kernel.
     Returns (wave, output): wave float64/float32 host array (n, T) as written by generate.py:146-149
         (mu-law expanded for the softmax output), output = the raw sampled bins / values."""
     rng = np.random.RandomState() if rng is None else rng
@@ -46,9 +49,10 @@ def synthesize(encoder, vq, decoder, condition_embed, x_enc, global_condition, r
     else:
         u = rng.random_sample((max(steps, 1), n))                    # inside numpy.random.choice, generate.py:136
     if lockstep:
-        out = decoder.generate_lockstep(cond, u, n_steps=steps)
+        out = decoder.generate_lockstep(cond, u, n_steps=steps, temperature=temperature, top_k=top_k, top_p=top_p)
     else:
-        out = decoder.generate_sequence(cond, u, n_steps=steps, persistent=persistent).get()
+        out = decoder.generate_sequence(cond, u, n_steps=steps, persistent=persistent, temperature=temperature,
+                                        top_k=top_k, top_p=top_p).get()
     if use_logistic:
         return out, out                                             # generate.py:147
     return MuLaw(quantize).itransform(out), out                     # generate.py:149

@@ -942,7 +942,7 @@ class WaveNet(Chain):
         return Variable(self._gen_state().step_logits(xd, cd))
 
     def generate_sequence(self, condition, uniforms, n_steps=None, forced=None, return_logits=False,
-                          graph_steps=8, persistent=True):
+                          graph_steps=8, persistent=True, temperature=None, top_k=None, top_p=None):
         """The loop of generate.py:101-145 as one device-resident run from fresh queues:
         condition (n, condition_dim, T[, 1]) on the device; ``uniforms`` the host doubles NumPy's
         RNG would hand generate.py:117 / 136 -- (T, n) for the softmax output, (T, n, nr_mix) for
@@ -951,38 +951,57 @@ class WaveNet(Chain):
         (steps, n, out_dim) when ``return_logits``).  ``forced`` (T, n) feeds these values back
         instead of the samples (teacher forcing).  ``persistent`` runs the loop as one persistent
         kernel (csrc/generate.hip, channel counts <= 512, condition <= 640); otherwise as a replayed hipGraph of
-        per-step kernels (``graph_steps`` steps per graph, 0 = eager launches)."""
+        per-step kernels (``graph_steps`` steps per graph, 0 = eager launches).
+
+        ``temperature`` / ``top_k`` / ``top_p``: sampling controls (include/vqvae_sampling.h), each None, a scalar or one
+        value per sequence: temperature >= 0 (0 = greedy: the most likely class, lowest index on ties), top_k >= 0 (0 =
+        off), top_p in (0, 1] (1 = off); the mixture of logistics takes a temperature > 0 only.  All None is the call
+        as it was.  With any control the persistent kernel is not used, whatever ``persistent`` says: it has no filtered
+        form, and the run is the replayed hipGraph of per-step kernels (for one sequence of the default decoder 667 us
+        against 95 us per sample)."""
         from .core import Variable
+        from .generation import sampling_controls
         cd = condition.data if isinstance(condition, Variable) else condition
+        sampling = sampling_controls(cd.shape[0], temperature, top_k, top_p, self.use_logistic, 'generate_sequence')
         backend.require_device(cd)
         self.initialize(cd.shape[0])
         mode = _lib.GEN_MOL if self.use_logistic else _lib.GEN_SOFTMAX
         return self._gen_state().run(cd, uniforms, mode, n_steps, forced, return_logits, graph_steps,
-                                     persistent)
+                                     persistent, sampling=sampling)
 
-    def generate_batch(self, condition, uniforms, n_steps=None, group=4, max_streams=8):
+    def generate_batch(self, condition, uniforms, n_steps=None, group=4, max_streams=8, temperature=None, top_k=None,
+                       top_p=None):
         """Serving form: N sequences generated as concurrent groups of <= ``group`` lockstep sequences,
         one persistent launch per group on its own stream.  condition (N, condition_dim, T[, 1]) on the
         device, uniforms (T, N[, nr_mix]) host doubles; returns the host array (N, T).  Every sequence
-        gets exactly the samples generate_sequence would give it alone with its column of uniforms."""
+        gets exactly the samples generate_sequence would give it alone with its column of uniforms.
+        It exists only as persistent launches, which have no filtered sampler: any of ``temperature`` / ``top_k`` /
+        ``top_p`` is a ValueError; generate_lockstep takes them."""
         from .core import Variable
         from .generation import run_many
+        if temperature is not None or top_k is not None or top_p is not None:
+            raise ValueError('generate_batch runs persistent launches only, which have no sampling controls: '
+                             'use generate_lockstep (any number of sequences) or generate_sequence (n <= 4)')
         cd = condition.data if isinstance(condition, Variable) else condition
         backend.require_device(cd)
         mode = _lib.GEN_MOL if self.use_logistic else _lib.GEN_SOFTMAX
         return run_many(self, cd, uniforms, mode, n_steps, group, max_streams)
 
     def generate_lockstep(self, condition, uniforms, n_steps=None, lengths=None, forced=None, return_logits=False,
-                          graph_steps=8, group=128):
+                          graph_steps=8, group=128, temperature=None, top_k=None, top_p=None):
         """Many sequences (a validation set, a corpus): N sequences of any count as groups of <= ``group`` (<= 128)
         sequences that advance in lockstep on the matrix pipe, one weight stream per step for the whole group
         (csrc/generate_lockstep.hip).  condition (N, condition_dim, T[, 1]) on the device, uniforms (T, N[, nr_mix])
         host doubles; ``lengths`` (N,): sequence i runs lengths[i] - 1 steps and the rest of its row is 0.  Returns the
         host array (N, T) in the caller's order (plus the logits (steps, N, out_dim) when ``return_logits``).  One
-        sequence alone is faster on generate_sequence (persistent kernel); see INTEGRATION.md "Generation"."""
+        sequence alone is faster on generate_sequence (persistent kernel); see INTEGRATION.md "Generation".
+        ``temperature`` / ``top_k`` / ``top_p``: as in generate_sequence, each None, a scalar or one value per sequence
+        (N), so one batch can mix settings; all None is the call as it was."""
         from .core import Variable
-        from .generation import run_lockstep
+        from .generation import run_lockstep, sampling_controls
         cd = condition.data if isinstance(condition, Variable) else condition
+        sampling = sampling_controls(cd.shape[0], temperature, top_k, top_p, self.use_logistic, 'generate_lockstep')
         backend.require_device(cd)
         mode = _lib.GEN_MOL if self.use_logistic else _lib.GEN_SOFTMAX
-        return run_lockstep(self, cd, uniforms, mode, n_steps, lengths, forced, return_logits, graph_steps, group)
+        return run_lockstep(self, cd, uniforms, mode, n_steps, lengths, forced, return_logits, graph_steps, group,
+                            sampling=sampling)

@@ -1,6 +1,8 @@
 """Throughput of the device-resident generation loop (generate.py:105-145) at BASELINE decoder sizes.
 usage: python tools/gen_bench.py [--workload c2|c5|ref] [--n 1] [--steps 16000] [--graph-steps 8]
-       python tools/gen_bench.py --workload ref --lockstep 128 [--group 128] [--steps 4000]"""
+       python tools/gen_bench.py --workload ref --lockstep 128 [--group 128] [--steps 4000]
+       ... [--temperature 0.8] [--top-k 32] [--top-p 0.95]   sampling controls (every sequence the same); with any of them
+       generate_sequence runs the per-step kernels, and --batch refuses"""
 import argparse
 import os
 import sys
@@ -26,7 +28,12 @@ def main():
     ap.add_argument('--lockstep', type=int, default=0, help='N sequences through generate_lockstep (groups of <= --group, default 128, '
                     'advancing together on the MFMA kernels); --graph-steps 0 = eager launches')
     ap.add_argument('--per-step-kernels', action='store_true', help='hipGraph of per-step kernels instead of the persistent kernel')
+    ap.add_argument('--temperature', type=float, default=None, help='sampling temperature (0 = greedy); default: none')
+    ap.add_argument('--top-k', type=int, default=None, help='keep the k most likely classes; default: none')
+    ap.add_argument('--top-p', type=float, default=None, help='nucleus mass in (0, 1]; default: none')
     a = ap.parse_args()
+    ctl = dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
+    ctl_txt = ''.join(' %s=%g' % (k, v) for k, v in ctl.items() if v is not None) or ' no controls'
     from vqvae_amd import backend
     from vqvae_amd.wavenet import WaveNet
     backend.init(0)
@@ -51,25 +58,25 @@ def main():
         rs = np.random.RandomState(0)
         cond = backend.to_device(rs.standard_normal((a.lockstep, Cc, T)).astype(np.float32))
         u = rs.uniform(0.01, 0.99, (T, a.lockstep, 10 if mol else 1))
-        dec.generate_lockstep(cond, u, n_steps=64, group=group, graph_steps=a.graph_steps)      # warm-up
+        dec.generate_lockstep(cond, u, n_steps=64, group=group, graph_steps=a.graph_steps, **ctl)      # warm-up
         t0 = time.time()
-        o = dec.generate_lockstep(cond, u, group=group, graph_steps=a.graph_steps)
+        o = dec.generate_lockstep(cond, u, group=group, graph_steps=a.graph_steps, **ctl)
         dt = time.time() - t0
         if a.dump:
             np.save(a.dump, o)
         ngroups = (a.lockstep + group - 1) // group
-        print('lockstep workload %s N=%d group %d graph-steps %d: %d steps in %.3f s = %.1f us/step/group, %.0f steps/s, '
+        print('lockstep workload %s N=%d group %d graph-steps %d,%s: %d steps in %.3f s = %.1f us/step/group, %.0f steps/s, '
               '%.0f samples/s aggregate (%.1f sequences in real time at 16 kHz), distinct outputs %d'
-              % (a.workload, a.lockstep, group, a.graph_steps, a.steps, dt, 1e6 * dt / a.steps / ngroups, a.steps * ngroups / dt,
+              % (a.workload, a.lockstep, group, a.graph_steps, ctl_txt, a.steps, dt, 1e6 * dt / a.steps / ngroups, a.steps * ngroups / dt,
                  a.lockstep * a.steps / dt, a.lockstep * a.steps / dt / 16000, len(np.unique(o))))
         return
     if a.batch:
         rs = np.random.RandomState(0)
         cond = backend.to_device(rs.standard_normal((a.batch, Cc, T)).astype(np.float32))
         u = rs.uniform(0.01, 0.99, (T, a.batch, 10 if mol else 1))
-        dec.generate_batch(cond, u, n_steps=64, group=a.group, max_streams=a.streams)
+        dec.generate_batch(cond, u, n_steps=64, group=a.group, max_streams=a.streams, **ctl)
         t0 = time.time()
-        o = dec.generate_batch(cond, u, group=a.group, max_streams=a.streams)
+        o = dec.generate_batch(cond, u, group=a.group, max_streams=a.streams, **ctl)
         dt = time.time() - t0
         if a.dump:
             np.save(a.dump, o)
@@ -79,16 +86,16 @@ def main():
     rs = np.random.RandomState(0)
     cond = backend.to_device(rs.standard_normal((a.n, Cc, T)).astype(np.float32))
     u = rs.uniform(0.01, 0.99, (T, a.n, 10 if mol else 1))
-    pers = not a.per_step_kernels
-    dec.generate_sequence(cond, u, n_steps=64, graph_steps=a.graph_steps, persistent=pers)      # warm-up
+    pers = not a.per_step_kernels and all(v is None for v in ctl.values())     # controls leave the persistent kernel
+    dec.generate_sequence(cond, u, n_steps=64, graph_steps=a.graph_steps, persistent=pers, **ctl)      # warm-up
     t0 = time.time()
-    out = dec.generate_sequence(cond, u, graph_steps=a.graph_steps, persistent=pers)
+    out = dec.generate_sequence(cond, u, graph_steps=a.graph_steps, persistent=pers, **ctl)
     dt = time.time() - t0
     o = out.get()
     if a.dump:
         np.save(a.dump, o)
-    print('%s workload %s n=%d: %d steps in %.3f s = %.1f us/step, %.0f samples/s per sequence (%.2fx real time at 16 kHz), '
-          'distinct outputs %d' % ('persistent' if pers else 'per-step kernels', a.workload, a.n, a.steps, dt, 1e6 * dt / a.steps, a.steps / dt,
+    print('%s workload %s n=%d,%s: %d steps in %.3f s = %.1f us/step, %.0f samples/s per sequence (%.2fx real time at 16 kHz), '
+          'distinct outputs %d' % ('persistent' if pers else 'per-step kernels', a.workload, a.n, ctl_txt, a.steps, dt, 1e6 * dt / a.steps, a.steps / dt,
                                    a.steps / dt / 16000, len(np.unique(o))))
 
 
