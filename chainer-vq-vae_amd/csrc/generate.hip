@@ -265,9 +265,8 @@ __global__ __launch_bounds__(256) void gen_finish_kernel(GenFinishArgs a) {
 int gen_step_lockstep(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st);   // generate_lockstep.hip: the batch in MFMA columns
 int gen_finish_sampled(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st);  // sampling.hip: finish + advance
 
-// One step.  smp == nullptr: vqvae_wavenet_gen_step; else the sampling controls of include/vqvae_sampling.h, which
-// replace the finish launch and nothing else.
-int gen_step_impl(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st) {
+// What every step entry point rejects before it launches anything (generate_slots.hip asks the same of its descriptor).
+int gen_validate_desc(const vqvae_gen_desc* d) {
   VQ_REQUIRE(d, "gen_step: null descriptor");
   VQ_REQUIRE(d->n >= 1 && d->n <= VQVAE_GEN_MAX_LOCKSTEP, "gen_step: n must be 1..%d sequences (got %d)", VQVAE_GEN_MAX_LOCKSTEP, d->n);
   VQ_REQUIRE(d->n_blocks >= 1 && d->blocks, "gen_step: no residual blocks");
@@ -282,6 +281,14 @@ int gen_step_impl(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStr
     if (d->sample_mode == VQVAE_GEN_SOFTMAX) VQ_REQUIRE(d->out_dim <= GEN_MAXOUT, "gen_step: at most %d classes", GEN_MAXOUT);
     else VQ_REQUIRE(d->out_dim % 3 == 0 && d->n_uniform >= d->out_dim / 3, "gen_step: mixture sampling needs out_dim = 3*nr_mix and nr_mix uniforms");
   }
+  return 0;
+}
+
+// One step.  smp == nullptr: vqvae_wavenet_gen_step; else the sampling controls of include/vqvae_sampling.h, which
+// replace the finish launch and nothing else.
+int gen_step_impl(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st) {
+  const int bad = gen_validate_desc(d);
+  if (bad != 0) return bad;
   if (d->n > GEN_NB) return gen_step_lockstep(d, smp, st);   // n <= 4: the kernels above, as before
   const int n = d->n, R = d->residual, half = d->dilated / 2;
 

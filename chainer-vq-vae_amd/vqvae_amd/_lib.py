@@ -75,6 +75,12 @@ class GenSampling(C.Structure):
     _fields_ = [(n, P) for n in ('temperature', 'top_k', 'top_p')]
 
 
+class GenSlots(C.Structure):
+    """vqvae_gen_slots (include/vqvae_gen_slots.h): the slot table of lockstep generation with refill."""
+    _fields_ = [('n_seq', c_int), ('steps', P), ('queue', P), ('n_queue', c_int), ('next', P), ('slot_seq', P),
+                ('slot_t', P), ('live', P), ('started', P)]
+
+
 # name -> (restype, argtypes); this table IS the list of symbols the header declares
 PROTOTYPES = {
     'vqvae_last_error_string': (c_char_p, []),
@@ -286,6 +292,14 @@ SAMPLING_PROTOTYPES = {
 SAMPLING_ABI_VERSION = 1          # vqvae_sampling_abi_version()
 SAMPLING_MAX_CLASSES = 1024       # VQVAE_SAMPLING_MAX_CLASSES
 
+# include/vqvae_gen_slots.h: lockstep generation with refill (slots, queue and scheduler on the device), a seventh table and version
+GEN_SLOTS_PROTOTYPES = {
+    'vqvae_gen_slots_abi_version': (c_int, []),
+    'vqvae_gen_slots_init': (c_int, [C.POINTER(GenDesc), C.POINTER(GenSlots), P]),
+    'vqvae_wavenet_gen_step_slots': (c_int, [C.POINTER(GenDesc), C.POINTER(GenSlots), C.POINTER(GenSampling), P]),
+}
+GEN_SLOTS_ABI_VERSION = 1         # vqvae_gen_slots_abi_version()
+
 # elementwise op codes / profiler tags (mirror the header)
 MAX_STACK_GROUP = 24              # blocks per resstack call (MAXSEG in csrc/gemm_common.h)
 STORE_X_BF16, STORE_RES_BF16 = 2, 4
@@ -329,7 +343,7 @@ def load():
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     lib = C.CDLL(LIB_PATH)
     for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES, KMEANS_PROTOTYPES, OPTIM_PROTOTYPES,
-                  SAMPLING_PROTOTYPES):
+                  SAMPLING_PROTOTYPES, GEN_SLOTS_PROTOTYPES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)           # AttributeError if the symbol is missing
             fn.restype = res
@@ -352,6 +366,9 @@ def load():
     if lib.vqvae_sampling_abi_version() != SAMPLING_ABI_VERSION:
         raise ImportError('libvqvae_hip.so at %s has sampling ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
                           % (LIB_PATH, lib.vqvae_sampling_abi_version(), SAMPLING_ABI_VERSION))
+    if lib.vqvae_gen_slots_abi_version() != GEN_SLOTS_ABI_VERSION:
+        raise ImportError('libvqvae_hip.so at %s has slot-generation ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
+                          % (LIB_PATH, lib.vqvae_gen_slots_abi_version(), GEN_SLOTS_ABI_VERSION))
     _lib = lib
     return lib
 

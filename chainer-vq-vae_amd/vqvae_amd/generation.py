@@ -429,3 +429,187 @@ def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None,
             if return_logits:
                 logits[:steps[i], i] = lg[:steps[i], j]
     return (out, logits) if return_logits else out
+
+
+# ---- lockstep generation with refill (include/vqvae_gen_slots.h, csrc/generate_slots.hip) -----------------------------
+def refill_queue(steps):
+    """The serving order of run_lockstep_refill: longest first, ties in the caller's order, sequences with 0 steps left
+    out (their output rows stay 0)."""
+    steps = np.asarray(steps, np.int64).reshape(-1)
+    order = np.argsort(-steps, kind='stable')
+    return order[steps[order] > 0].astype(np.int32)
+
+
+def refill_slots(n_queue, group=_lib.GEN_MAX_LOCKSTEP):
+    """S = clamp(min(sequences to run, group), 5, 128): the slot count of a refilled run."""
+    if not _lib.GEN_MAX_N < group <= _lib.GEN_MAX_LOCKSTEP:
+        raise ValueError('generate_lockstep: group must be %d..%d, got %d' % (_lib.GEN_MAX_N + 1, _lib.GEN_MAX_LOCKSTEP, group))
+    return max(_lib.GEN_MAX_N + 1, min(int(n_queue), int(group)))
+
+
+def plan_refill(steps, slots):
+    """The device scheduler's rule (csrc/generate_slots.hip) replayed on the host.  ``steps`` (N,) steps per sequence,
+    ``slots`` = S.  Slot s starts with queue[s]; at the end of every tick the slots whose sequence has run all its
+    steps are freed and take, in slot order, the next waiting sequences of refill_queue(steps).
+    Returns (ticks, placement): the number of ticks until every slot is idle, and the int64 array (N, 2) of every
+    sequence's (slot, first tick), (-1, -1) for a sequence with 0 steps, which is never queued.  The host issues
+    ``ticks`` steps and never asks the device how far it is."""
+    import heapq
+    steps = np.asarray(steps, np.int64).reshape(-1)
+    if (steps < 0).any() or slots < 1:
+        raise ValueError('plan_refill: steps must be >= 0 and slots >= 1')
+    queue = refill_queue(steps)
+    placement = np.full((len(steps), 2), -1, np.int64)
+    head = queue[:slots]
+    placement[head, 0] = np.arange(len(head))
+    placement[head, 1] = 0
+    ends = [(int(steps[q]), s) for s, q in enumerate(head)]           # (tick at which the slot is free again, slot)
+    heapq.heapify(ends)
+    nxt, ticks = len(head), 0
+    while ends:
+        tick, slot = heapq.heappop(ends)                              # equal ticks come out in slot order
+        ticks = max(ticks, tick)
+        if nxt < len(queue):
+            q = queue[nxt]
+            nxt += 1
+            placement[q] = (slot, tick)
+            heapq.heappush(ends, (tick + int(steps[q]), slot))
+    return ticks, placement
+
+
+class LockstepRefill(object):
+    """One refilled run on the device: the slot table, the queue and every sequence's inputs uploaded once, one
+    LockstepState of S slots, ``graph_steps`` ticks captured as a hipGraph (0 = eager) and replayed
+    ceil(ticks / graph_steps) times; surplus ticks are device no-ops.
+
+    Device memory besides the decoder state of S slots: the condition (N, condition_dim, T) floats as the caller holds
+    it, the dense uniforms max_steps x N x n_uniform doubles and forced values max_steps x N, ``out`` N x T, with
+    ``return_logits`` max_steps x N x out_dim floats (a test and inspection facility: 25 MB per 100 steps of 256
+    sequences and classes), and 3 N + 2 S + 2 integers of table.  For a corpus of N = 300 utterances of up to 10 s at
+    16 kHz the uniforms are 384 MB; the rows are dense because ragged storage would make a sequence's addresses
+    depend on its neighbours' lengths."""
+
+    def __init__(self, wavenet, condition, steps, u, forced, mode, group, return_logits=False, sampling=None):
+        N, Cc, T = condition.shape
+        steps = np.ascontiguousarray(steps, dtype=np.int32)
+        queue = refill_queue(steps)
+        self.n_slots = S = refill_slots(len(queue), group)
+        self.ticks, self.placement = plan_refill(steps, S)
+        max_steps = int(steps.max())
+        softmax = mode == _lib.GEN_SOFTMAX
+        st = self.state = LockstepState(wavenet, S)
+        n_uniform = u.shape[2]
+        self._keep = [condition,
+                      backend.to_device(steps), backend.to_device(queue),
+                      backend.to_device(np.ascontiguousarray(u[:max_steps]).reshape(-1))]
+        self.out = backend.zeros((N, T), np.int32 if softmax else np.float32)
+        self.logits_out = backend.zeros((max_steps, N, st.out_dim), np.float32) if return_logits else None
+        self.slot_seq = backend.zeros((S,), np.int32)
+        self.slot_t = backend.zeros((S,), np.int32)
+        self.next = backend.zeros((1,), np.int32)
+        self.live = backend.zeros((1,), np.int32)
+        self.started = backend.to_device(np.full((N, 2), -1, np.int32))
+        d = self.desc = st.desc
+        d.sample_mode = mode
+        d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = condition.ptr, Cc * T, T, 1
+        d.uniforms, d.n_uniform = self._keep[3].ptr, n_uniform
+        d.forced_next = None
+        if forced is not None:
+            self._keep.append(backend.to_device(np.ascontiguousarray(
+                forced[:max_steps], dtype=np.int32 if softmax else np.float32).reshape(-1)))
+            d.forced_next = self._keep[-1].ptr
+        d.out, d.out_bstride = self.out.ptr, T
+        d.logits_out = None if self.logits_out is None else self.logits_out.ptr
+        d.max_steps = self.ticks
+        t = self.table = _lib.GenSlots()
+        t.n_seq, t.steps, t.queue, t.n_queue = N, self._keep[1].ptr, self._keep[2].ptr, len(queue)
+        t.next, t.slot_seq, t.slot_t, t.live = self.next.ptr, self.slot_seq.ptr, self.slot_t.ptr, self.live.ptr
+        t.started = self.started.ptr
+        self._smp = None
+        if sampling is not None:
+            self._smp, controls = _upload_controls(sampling)
+            self._keep.append(controls)
+        self._graph = None
+        _lib.call('vqvae_gen_slots_init', C.byref(d), C.byref(t), _S())
+
+    def tick(self):
+        _lib.call('vqvae_wavenet_gen_step_slots', C.byref(self.desc), C.byref(self.table),
+                  None if self._smp is None else C.byref(self._smp), _S())
+
+    def replay(self):
+        """One more launch of the captured graph (``graph_steps`` ticks); past the end a device no-op."""
+        _lib.call('vqvae_graph_launch', self._graph, _S())
+
+    def run(self, graph_steps=8):
+        if not graph_steps:
+            for _ in range(self.ticks):
+                self.tick()
+        elif self.ticks:
+            per = max(1, min(int(graph_steps), self.ticks))
+            self._graph = C.c_void_p()
+            _lib.call('vqvae_graph_capture_begin', _S())
+            try:
+                for _ in range(per):
+                    self.tick()
+            finally:
+                _lib.call('vqvae_graph_capture_end', _S(), C.byref(self._graph))
+            for _ in range((self.ticks + per - 1) // per):
+                self.replay()
+        backend.synchronize()
+        return self
+
+    def close(self):
+        if self._graph is not None:
+            backend.synchronize()
+            _lib.call('vqvae_graph_destroy', self._graph)
+            self._graph = None
+
+
+def _device_refill_runner(wavenet, condition, mode, graph_steps, group, return_logits):
+    def run(steps, u, forced, sampling):
+        r = LockstepRefill(wavenet, condition, steps, u, forced, mode, group, return_logits, sampling)
+        try:
+            r.run(graph_steps)
+            return r.out.get(), None if r.logits_out is None else r.logits_out.get()
+        finally:
+            r.close()
+    return run
+
+
+def run_lockstep_refill(wavenet, condition, uniforms, mode, n_steps=None, lengths=None, forced=None, return_logits=False,
+                        graph_steps=8, group=_lib.GEN_MAX_LOCKSTEP, _run=None, sampling=None):
+    """run_lockstep with the columns refilled on the device: ``group`` is the number of slots, a slot whose sequence
+    has finished takes the next waiting one (longest first) at the next step, and the whole call is one replayed
+    hipGraph with no host read-back until the end (csrc/generate_slots.hip; memory: see LockstepRefill).  Arguments
+    and return value as run_lockstep; every sequence gets the values run_lockstep gives it, bit for bit.
+    ``_run(steps, u, forced, sampling)`` -> (out (N, T), logits (max steps, N, out_dim) or None), both in the caller's
+    order, stands in for the device in host tests."""
+    if condition.ndim == 4:
+        condition = condition.reshape(condition.shape[:3])
+    N, Cc, T = condition.shape
+    steps, _ = plan_lockstep(N, T, lengths, n_steps, group)              # the same step counts and argument errors
+    softmax = mode == _lib.GEN_SOFTMAX
+    out_dim = wavenet.proj2.W.shape[0]
+    n_uniform = 1 if softmax else out_dim // 3
+    u = np.asarray(uniforms, np.float64)
+    max_steps = int(steps.max()) if N else 0
+    if u.ndim < 2 or u.shape[1] != N:
+        raise ValueError('generate_lockstep: uniforms must be (T, N[, %d]) = (%d, %d, ...), got %s'
+                         % (n_uniform, T, N, u.shape))
+    u = u.reshape(u.shape[0], N, -1)
+    if u.shape[0] < max_steps or u.shape[2] < n_uniform:
+        raise ValueError('generate_lockstep: need (%d, %d, %d) uniform doubles, got %s' % (max_steps, N, n_uniform, u.shape))
+    if forced is not None:
+        forced = np.asarray(forced).reshape(-1, N)
+        if forced.shape[0] < max_steps:
+            raise ValueError('generate_lockstep: forced must be (steps, N) = (%d, %d), got %s' % (max_steps, N, forced.shape))
+    out = np.zeros((N, T), np.int32 if softmax else np.float32)                  # generate.py:103
+    logits = np.zeros((max_steps, N, out_dim), np.float32) if return_logits else None
+    if max_steps:
+        run = _run or _device_refill_runner(wavenet, condition, mode, graph_steps, group, return_logits)
+        o, lg = run(steps, u[:max_steps, :, :n_uniform], forced, sampling)
+        for i in range(N):                        # the device wrote nothing past a sequence's own steps; a stub may have
+            out[i, :steps[i]] = o[i, :steps[i]]
+            if return_logits:
+                logits[:steps[i], i] = lg[:steps[i], i]
+    return (out, logits) if return_logits else out

@@ -56,3 +56,51 @@ def synthesize(encoder, vq, decoder, condition_embed, x_enc, global_condition, r
     if use_logistic:
         return out, out                                             # generate.py:147
     return MuLaw(quantize).itransform(out), out                     # generate.py:149
+
+
+def synthesize_many(encoder, vq, decoder, condition_embed, waves, global_condition, rng=None,
+                    quantize=256, use_logistic=False, n_steps=None, group=128, refill=True,
+                    temperature=None, top_k=None, top_p=None, return_output=False):
+    """``synthesize`` for a list of waveforms of different lengths (a validation set, a corpus).
+
+    waves: list of N normalised waveforms, each a host or device float32 array of T_i + 1 samples (any shape that
+        holds them).  global_condition: int32 (N,) speaker ids.
+    Each waveform is encoded, quantised and condition-embedded on its own, with n = 1: in a padded batch the encoder's
+    and ConditionEmbed's edge samples and the align-corners up-sampling would see the padding.  The condition rows are
+    packed into one zero-padded (N, condition_dim, Tmax) device array and the decoder runs them with their lengths
+    through WaveNet.generate_lockstep; ``refill`` (default True) keeps its ``group`` columns busy by handing a finished
+    column the next waiting utterance.
+    rng: as in synthesize; the uniforms are drawn as it draws them for shape (Tmax - 1, N[, nr_mix]), so utterance i
+        uses column i.
+    Returns the list of N host waves, utterance i of its own length T_i, as synthesize returns them (mu-law expanded
+    for the softmax output); with ``return_output`` the list of (wave, output) pairs."""
+    rng = np.random.RandomState() if rng is None else rng
+    N = len(waves)
+    speakers = np.asarray(global_condition.get() if backend.is_device(global_condition) else global_condition,
+                          np.int32).reshape(-1)
+    if speakers.shape != (N,):
+        raise ValueError('synthesize_many: one speaker id per waveform (%d), got %s' % (N, speakers.shape))
+    conds = []
+    with core.using_config('train', False), core.no_backprop_mode():
+        for w, spk in zip(waves, speakers):
+            xd = w if backend.is_device(w) else backend.to_device(np.asarray(w, np.float32))
+            xd = xd.reshape(1, 1, xd.size, 1)
+            e = vq(encoder(Variable(xd)))                                                  # generate.py:95-96
+            c = condition_embed(e, Variable(backend.to_device(np.array([spk], np.int32)))).data   # generate.py:97-98
+            conds.append(c.reshape(c.shape[1], c.shape[2]))
+    lengths = np.array([c.shape[1] for c in conds], np.int64)
+    Cc, Tmax = conds[0].shape[0], int(lengths.max())
+    cond = backend.zeros((N, Cc, Tmax), np.float32)
+    backend.copy_many([(cond.flat_view((i * Cc + ch) * Tmax, int(L)), c.flat_view(ch * int(L), int(L)))
+                       for i, (c, L) in enumerate(zip(conds, lengths)) for ch in range(Cc)])
+    steps = Tmax - 1 if n_steps is None else n_steps
+    nr_mix = decoder.proj2.W.shape[0] // 3
+    if use_logistic:
+        u = rng.uniform(0, 1, (max(steps, 1), N, nr_mix))            # generate.py:117
+    else:
+        u = rng.random_sample((max(steps, 1), N))                    # inside numpy.random.choice, generate.py:136
+    out = decoder.generate_lockstep(cond, u, n_steps=n_steps, lengths=lengths, group=group, refill=refill,
+                                    temperature=temperature, top_k=top_k, top_p=top_p)
+    wave = out if use_logistic else MuLaw(quantize).itransform(out)
+    res = [(wave[i, :L], out[i, :L]) for i, L in enumerate(lengths)]
+    return res if return_output else [w for w, _ in res]

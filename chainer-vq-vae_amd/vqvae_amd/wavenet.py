@@ -988,7 +988,7 @@ class WaveNet(Chain):
         return run_many(self, cd, uniforms, mode, n_steps, group, max_streams)
 
     def generate_lockstep(self, condition, uniforms, n_steps=None, lengths=None, forced=None, return_logits=False,
-                          graph_steps=8, group=128, temperature=None, top_k=None, top_p=None):
+                          graph_steps=8, group=128, temperature=None, top_k=None, top_p=None, refill=False):
         """Many sequences (a validation set, a corpus): N sequences of any count as groups of <= ``group`` (<= 128)
         sequences that advance in lockstep on the matrix pipe, one weight stream per step for the whole group
         (csrc/generate_lockstep.hip).  condition (N, condition_dim, T[, 1]) on the device, uniforms (T, N[, nr_mix])
@@ -996,12 +996,21 @@ class WaveNet(Chain):
         host array (N, T) in the caller's order (plus the logits (steps, N, out_dim) when ``return_logits``).  One
         sequence alone is faster on generate_sequence (persistent kernel); see INTEGRATION.md "Generation".
         ``temperature`` / ``top_k`` / ``top_p``: as in generate_sequence, each None, a scalar or one value per sequence
-        (N), so one batch can mix settings; all None is the call as it was."""
+        (N), so one batch can mix settings; all None is the call as it was.
+        ``refill``: with sequences of different lengths a group runs to its longest member and the columns of the
+        shorter ones do dead work.  True keeps the columns busy instead: ``group`` (5..128) is the number of slots, and a
+        slot whose sequence has finished takes the next waiting one, longest first, on the device
+        (csrc/generate_slots.hip; generation.run_lockstep_refill documents the memory it needs).  Every other argument
+        means what it means without, the return value is the same, bit for bit.  False (the default) is the call as
+        it was."""
         from .core import Variable
-        from .generation import run_lockstep, sampling_controls
+        from .generation import run_lockstep, run_lockstep_refill, sampling_controls
         cd = condition.data if isinstance(condition, Variable) else condition
         sampling = sampling_controls(cd.shape[0], temperature, top_k, top_p, self.use_logistic, 'generate_lockstep')
         backend.require_device(cd)
         mode = _lib.GEN_MOL if self.use_logistic else _lib.GEN_SOFTMAX
+        if refill:
+            return run_lockstep_refill(self, cd, uniforms, mode, n_steps, lengths, forced, return_logits, graph_steps,
+                                       group, sampling=sampling)
         return run_lockstep(self, cd, uniforms, mode, n_steps, lengths, forced, return_logits, graph_steps, group,
                             sampling=sampling)

@@ -1,6 +1,11 @@
 """Throughput of the device-resident generation loop (generate.py:105-145) at BASELINE decoder sizes.
 usage: python tools/gen_bench.py [--workload c2|c5|ref] [--n 1] [--steps 16000] [--graph-steps 8]
        python tools/gen_bench.py --workload ref --lockstep 128 [--group 128] [--steps 4000]
+       python tools/gen_bench.py --workload ref --lengths-n 300 --lengths-seed 0 [--lengths-rate 16000] [--group 128]
+           N utterances of gamma-distributed lengths (mean 3.6 s, clipped to 0.5-10 s at --lengths-rate samples per second;
+           a lower rate keeps the list's shape and shrinks the run) through generate_lockstep twice: as sorted groups
+           (refill=False) and with the columns refilled on the device (refill=True)
+       python tools/gen_bench.py --workload ref --lockstep 128 --refill    equal lengths through the refilled kernels (tick cost)
        ... [--temperature 0.8] [--top-k 32] [--top-p 0.95]   sampling controls (every sequence the same); with any of them
        generate_sequence runs the per-step kernels, and --batch refuses"""
 import argparse
@@ -12,6 +17,12 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'chainer-vq-vae_amd'))
+
+
+def gamma_lengths(n, seed, rate=16000.0):
+    """Utterance lengths in samples: gamma(shape 2, mean 3.6 s) clipped to 0.5-10 s, at ``rate`` samples per second."""
+    rs = np.random.RandomState(seed)
+    return np.maximum((np.clip(rs.gamma(2.0, 1.8, n), 0.5, 10.0) * rate).astype(np.int64), 2)
 
 
 def main():
@@ -27,6 +38,10 @@ def main():
     ap.add_argument('--batch', type=int, default=0, help='N sequences through generate_batch (concurrent groups of 4)')
     ap.add_argument('--lockstep', type=int, default=0, help='N sequences through generate_lockstep (groups of <= --group, default 128, '
                     'advancing together on the MFMA kernels); --graph-steps 0 = eager launches')
+    ap.add_argument('--refill', action='store_true', help='--lockstep through generate_lockstep(refill=True)')
+    ap.add_argument('--lengths-n', type=int, default=0, help='N utterances of seeded gamma lengths, sorted groups against refill')
+    ap.add_argument('--lengths-seed', type=int, default=0)
+    ap.add_argument('--lengths-rate', type=float, default=16000.0, help='samples per second of the length list (default 16 kHz)')
     ap.add_argument('--per-step-kernels', action='store_true', help='hipGraph of per-step kernels instead of the persistent kernel')
     ap.add_argument('--temperature', type=float, default=None, help='sampling temperature (0 = greedy); default: none')
     ap.add_argument('--top-k', type=int, default=None, help='keep the k most likely classes; default: none')
@@ -53,11 +68,45 @@ def main():
     dec.to_gpu()
     dec(Variable(x), Variable(c))
     T = a.steps + 1
+    if a.lengths_n:
+        from vqvae_amd.generation import plan_lockstep, plan_refill, refill_slots
+        group = a.group if a.group > 4 else 128
+        lengths = gamma_lengths(a.lengths_n, a.lengths_seed, a.lengths_rate)
+        N, T = a.lengths_n, int(lengths.max())
+        steps, groups = plan_lockstep(N, T, lengths, group=group)
+        ticks = dict(sorted=sum(g for _, g in groups), refill=plan_refill(steps, refill_slots((steps > 0).sum(), group))[0])
+        rs = np.random.RandomState(0)
+        cond = backend.zeros((N, Cc, T), np.float32)
+        for i in range(N):                                   # row by row: the whole array may not fit the host twice
+            cond.flat_view(i * Cc * T, Cc * T).set(rs.standard_normal(Cc * T).astype(np.float32))
+        u = rs.uniform(0.01, 0.99, (T, N, 10 if mol else 1))
+        short = np.minimum(lengths, 65)
+        for refill in (False, True):                         # warm-up of both roads
+            dec.generate_lockstep(cond, u, lengths=short, group=group, graph_steps=a.graph_steps, refill=refill, **ctl)
+        print('lengths workload %s N=%d seed %d rate %g: %d samples, longest %d, group %d graph-steps %d,%s; lower bound %d ticks'
+              % (a.workload, N, a.lengths_seed, a.lengths_rate, steps.sum(), steps.max(), group, a.graph_steps, ctl_txt,
+                 max(int(steps.max()), -(-int(steps.sum()) // group))))
+        res = {}
+        for name, refill in (('sorted', False), ('refill', True)):
+            t0 = time.time()
+            res[name] = dec.generate_lockstep(cond, u, lengths=lengths, group=group, graph_steps=a.graph_steps, refill=refill, **ctl)
+            dt = time.time() - t0
+            print('  %-6s %8d ticks in %8.3f s = %7.1f us/tick, %9.0f samples/s' % (name, ticks[name], dt, 1e6 * dt / ticks[name],
+                                                                              steps.sum() / dt))
+            res[name + '_dt'] = dt
+        print('  ticks sorted / refill %.3f, wall sorted / refill %.3f, outputs equal: %s'
+              % (ticks['sorted'] / ticks['refill'], res['sorted_dt'] / res['refill_dt'], np.array_equal(res['sorted'], res['refill'])))
+        if a.dump:
+            np.save(a.dump, res['refill'])
+        return
     if a.lockstep:
         group = a.group if a.group > 4 else 128
         rs = np.random.RandomState(0)
         cond = backend.to_device(rs.standard_normal((a.lockstep, Cc, T)).astype(np.float32))
         u = rs.uniform(0.01, 0.99, (T, a.lockstep, 10 if mol else 1))
+        if a.refill:
+            ctl = dict(ctl, refill=True)
+            ctl_txt += ' refill'
         dec.generate_lockstep(cond, u, n_steps=64, group=group, graph_steps=a.graph_steps, **ctl)      # warm-up
         t0 = time.time()
         o = dec.generate_lockstep(cond, u, group=group, graph_steps=a.graph_steps, **ctl)
