@@ -81,6 +81,12 @@ class GenSlots(C.Structure):
                 ('slot_t', P), ('live', P), ('started', P)]
 
 
+class GenLatentCond(C.Structure):
+    """vqvae_gen_latent_cond (include/vqvae_gen_cond.h): the latent-rate condition of lockstep generation."""
+    _fields_ = [('local', P), ('local_off', P), ('tl', P), ('global_vec', P), ('col_seq', P), ('column', P),
+                ('n_seq', c_int), ('Cl', c_int), ('G', c_int), ('upscale', c_int)]
+
+
 # name -> (restype, argtypes); this table IS the list of symbols the header declares
 PROTOTYPES = {
     'vqvae_last_error_string': (c_char_p, []),
@@ -300,6 +306,13 @@ GEN_SLOTS_PROTOTYPES = {
 }
 GEN_SLOTS_ABI_VERSION = 1         # vqvae_gen_slots_abi_version()
 
+# include/vqvae_gen_cond.h: the condition column of a lockstep step from the latent-rate condition, an eighth table and version
+GEN_COND_PROTOTYPES = {
+    'vqvae_gen_cond_abi_version': (c_int, []),
+    'vqvae_gen_cond_column': (c_int, [C.POINTER(GenLatentCond), C.POINTER(GenDesc), C.POINTER(GenSlots), P]),
+}
+GEN_COND_ABI_VERSION = 1          # vqvae_gen_cond_abi_version()
+
 # elementwise op codes / profiler tags (mirror the header)
 MAX_STACK_GROUP = 24              # blocks per resstack call (MAXSEG in csrc/gemm_common.h)
 STORE_X_BF16, STORE_RES_BF16 = 2, 4
@@ -343,7 +356,7 @@ def load():
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     lib = C.CDLL(LIB_PATH)
     for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES, KMEANS_PROTOTYPES, OPTIM_PROTOTYPES,
-                  SAMPLING_PROTOTYPES, GEN_SLOTS_PROTOTYPES):
+                  SAMPLING_PROTOTYPES, GEN_SLOTS_PROTOTYPES, GEN_COND_PROTOTYPES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)           # AttributeError if the symbol is missing
             fn.restype = res
@@ -369,6 +382,9 @@ def load():
     if lib.vqvae_gen_slots_abi_version() != GEN_SLOTS_ABI_VERSION:
         raise ImportError('libvqvae_hip.so at %s has slot-generation ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
                           % (LIB_PATH, lib.vqvae_gen_slots_abi_version(), GEN_SLOTS_ABI_VERSION))
+    if lib.vqvae_gen_cond_abi_version() != GEN_COND_ABI_VERSION:
+        raise ImportError('libvqvae_hip.so at %s has latent-condition ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
+                          % (LIB_PATH, lib.vqvae_gen_cond_abi_version(), GEN_COND_ABI_VERSION))
     _lib = lib
     return lib
 

@@ -531,9 +531,9 @@ class LazyUpsampled(DeviceArray):
     carries the latent-rate tensor ``latent`` (B, Cl+G, Tl) = [local | speaker broadcast]
     and is only expanded to full rate when something reads ``.ptr``.  ResidualNet
     consumes ``latent`` directly (condition projection at the latent rate)."""
-    __slots__ = ('latent', 'upscale', '_full', '_make')
+    __slots__ = ('latent', 'upscale', '_full', '_make', 'local_dim')
 
-    def __init__(self, shape, latent, upscale, make):
+    def __init__(self, shape, latent, upscale, make, local_dim=None):
         self.shape = tuple(shape)
         self.dtype = np.dtype(np.float32)
         self._block = None
@@ -541,6 +541,7 @@ class LazyUpsampled(DeviceArray):
         self.upscale = upscale
         self._full = None
         self._make = make
+        self.local_dim = local_dim       # Cl, where the producer knows it: rows 0..Cl-1 of ``latent`` are the local part
 
     def materialize(self):
         if self._full is None:
@@ -610,7 +611,7 @@ class ConditionAssemble(FunctionNode):
                   tb['w0'].ptr, tb['w1'].ptr, lat.ptr, bs, _S())
         _lib.call('vqvae_embed_broadcast_fwd', E.ptr, ids.ptr, B, G, Tl, lat.ptr + Cl * Tl * 4, bs, _S())
         return LazyUpsampled((B, Cl + G, T, 1), lat, self.upscale,
-                             lambda: self._full(local, E, ids)),
+                             lambda: self._full(local, E, ids), local_dim=Cl),
 
     def backward(self, indexes, gys):
         B, Cl, Tl, G, T, n_id = self._dims

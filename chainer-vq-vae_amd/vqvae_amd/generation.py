@@ -90,6 +90,203 @@ def sample_logits(logits, uniforms, mode=_lib.GEN_SOFTMAX, temperature=None, top
     return (out, probs) if return_probs else out
 
 
+class LatentCondition(object):
+    """The condition of N sequences at the latent rate, for WaveNet.generate_lockstep (include/vqvae_gen_cond.h).
+
+    The full-rate condition (N, Cc, T) of net.py:54-63 is the x``upscale`` align-corners linear up-sampling of a local
+    tensor (Cl, Tl_i) per sequence plus a speaker vector (G,) that is constant in time, Cc = Cl + G.  This object holds
+    those two and nothing at the sample rate: ``local`` one ragged float32 device buffer, sequence i a row-major
+    (Cl, tl[i]) block at ``local_off[i]`` with no padding to the longest, ``global_vec`` (N, G).  Lockstep generation
+    computes the one condition column a step reads from them, at the head of the step
+    (csrc/generate_cond.hip), with the bits the dense tensor would hold.
+      dense   4 Cc N Tmax bytes (``dense_nbytes``; Tmax = upscale max(tl)): 2 560 bytes per sample for the default model
+      latent  4 Cl sum(tl) + 4 G N bytes (``nbytes``): 32 bytes per sample
+    generate_sequence, generate_batch and generate run persistent or host-stepped forms that read the dense tensor:
+    they refuse this object; ``dense()`` gives them (and tests) the tensor."""
+    ndim = 3
+
+    def __init__(self, tl, Cl, G, upscale, local=None, global_vec=None):
+        """The description alone (``local`` and ``global_vec`` None) is enough to plan a run; from_latents and
+        from_condition fill the device buffers in."""
+        tl = np.asarray(tl)
+        if tl.ndim != 1 or tl.size == 0 or tl.dtype.kind not in 'iu' or (tl < 1).any():
+            raise ValueError('LatentCondition: tl must be (N,) latent lengths >= 1 with N >= 1, got %r' % (tl,))
+        if int(Cl) < 0 or int(G) < 0 or int(Cl) + int(G) < 1 or int(upscale) < 1:
+            raise ValueError('LatentCondition: needs Cl >= 0, G >= 0, Cl + G >= 1 and upscale >= 1, got %r, %r, %r' % (Cl, G, upscale))
+        if int(upscale) * int(tl.max()) > _INT_MAX:
+            raise ValueError('LatentCondition: upscale * max(tl) must fit a 32-bit step counter')
+        self.tl = tl.astype(np.int32)
+        self.Cl, self.G, self.upscale = int(Cl), int(G), int(upscale)
+        sizes = self.Cl * self.tl.astype(np.int64)
+        self.local_off = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+        self.local_size = int(sizes.sum())
+        self.local, self.global_vec = local, global_vec
+        self._tables = None
+
+    # ---- what a dense array of the same condition would answer ----
+    @property
+    def shape(self):
+        return (len(self.tl), self.Cl + self.G, self.upscale * int(self.tl.max()))
+
+    @property
+    def lengths(self):
+        """Samples of every sequence, (N,) int64: upscale * tl."""
+        return self.upscale * self.tl.astype(np.int64)
+
+    @property
+    def nbytes(self):
+        return 4 * self.local_size + 4 * self.G * len(self.tl)
+
+    @property
+    def dense_nbytes(self):
+        N, Cc, Tmax = self.shape
+        return 4 * Cc * N * Tmax
+
+    # ---- constructors ----
+    @classmethod
+    def from_latents(cls, latents, global_vec, upscale):
+        """latents: list of N float32 device arrays (Cl, Tl_i[, 1]), Tl_i >= 1; global_vec: float32 device array (N, G), the
+        speaker embedding row of every sequence.  The latents are copied into one ragged buffer (N copies, batched)."""
+        latents = list(latents)
+        if not latents:
+            raise ValueError('LatentCondition.from_latents: no sequences')
+        shapes = [tuple(a.shape[:2]) if len(a.shape) in (2, 3) and tuple(a.shape[2:]) in ((), (1,)) else None for a in latents]
+        if any(sh is None for sh in shapes):
+            raise ValueError('LatentCondition.from_latents: every latent must be (Cl, Tl[, 1]), got %s' % [tuple(a.shape) for a in latents])
+        Cl = shapes[0][0]
+        if any(sh[0] != Cl for sh in shapes):
+            raise ValueError('LatentCondition.from_latents: the latents have different channel counts: %s' % sorted(set(sh[0] for sh in shapes)))
+        if any(sh[1] < 1 for sh in shapes):
+            raise ValueError('LatentCondition.from_latents: a latent of 0 frames (shapes %s)' % shapes)
+        N = len(latents)
+        if len(global_vec.shape) != 2 or global_vec.shape[0] != N:
+            raise ValueError('LatentCondition.from_latents: global_vec must be (N, G) = (%d, G), got %s' % (N, tuple(global_vec.shape)))
+        self = cls([sh[1] for sh in shapes], Cl, global_vec.shape[1], upscale)
+        backend.require_device(global_vec, *latents)
+        self.local = DeviceArray((max(self.local_size, 1),), np.float32)
+        backend.copy_many([(self.local.flat_view(int(o), a.size), a.reshape(-1)) for o, a in zip(self.local_off, latents)])
+        self.global_vec = global_vec
+        return self
+
+    @classmethod
+    def from_condition(cls, cond, local_dim=None, upscale=None):
+        """From what ConditionEmbed returns for B sequences of equal length, without the full-rate tensor being made: a
+        functions.LazyUpsampled, whose ``latent`` (B, Cl + G, Tl) = [local | speaker broadcast] is split into the local
+        blocks and column 0 of the speaker rows (``local_dim`` = Cl defaults to what the tensor's producer recorded); or
+        the dense (B, Cl + G, upscale[, 1]) tensor ConditionEmbed returns for ONE latent frame, whose column 0 is that
+        frame (``local_dim`` and ``upscale`` are needed then).  Any other dense tensor is a TypeError: the latent
+        tensor cannot be recovered from its up-sampling."""
+        from .functions import LazyUpsampled
+        if isinstance(cond, LazyUpsampled):
+            src, up, Tl = cond.latent, cond.upscale, cond.latent.shape[2]
+            local_dim = cond.local_dim if local_dim is None else local_dim
+        else:
+            backend.require_device(cond)
+            if upscale is None or len(cond.shape) < 3 or cond.shape[2] != int(upscale):
+                raise TypeError('LatentCondition.from_condition takes a LazyUpsampled condition (or the dense condition of one '
+                                'latent frame, (B, Cc, upscale), with local_dim and upscale), got %r' % (cond,))
+            src, up, Tl = cond, int(upscale), 1       # only column 0 of its `upscale` columns is taken
+        if local_dim is None:
+            raise ValueError('LatentCondition.from_condition: local_dim (Cl) is not known for this tensor, pass it')
+        B, Cc, Ts = src.shape[:3]
+        Cl = int(local_dim)
+        if not 0 <= Cl <= Cc:
+            raise ValueError('LatentCondition.from_condition: local_dim %d outside 0..%d' % (Cl, Cc))
+        self = cls([Tl] * B, Cl, Cc - Cl, up)
+        self.local = DeviceArray((max(self.local_size, 1),), np.float32)
+        self.global_vec = DeviceArray((B, max(self.G, 1)), np.float32).flat_view(0, B * self.G, (B, self.G))
+        for b in range(B):
+            if Cl:                                        # rows 0..Cl-1 of the sequence, the first Tl of their Ts columns
+                _lib.call('vqvae_memcpy2d_d2d', self.local.ptr + 4 * b * Cl * Tl, 4 * Tl, src.ptr + 4 * b * Cc * Ts, 4 * Ts,
+                          4 * Tl, Cl, _S())
+            if self.G:                                    # column 0 of rows Cl..Cc-1
+                _lib.call('vqvae_memcpy2d_d2d', self.global_vec.ptr + 4 * b * self.G, 4, src.ptr + 4 * (b * Cc + Cl) * Ts,
+                          4 * Ts, 4, self.G, _S())
+        return self
+
+    @classmethod
+    def concatenate(cls, parts):
+        """The sequences of several LatentConditions (same Cl, G and upscale) as one, in order: two batched copies per part."""
+        parts = list(parts)
+        if not parts or any((p.Cl, p.G, p.upscale) != (parts[0].Cl, parts[0].G, parts[0].upscale) for p in parts):
+            raise ValueError('LatentCondition.concatenate: needs parts of one Cl, G and upscale')
+        self = cls(np.concatenate([p.tl for p in parts]), parts[0].Cl, parts[0].G, parts[0].upscale)
+        N, G = len(self.tl), self.G
+        self.local = DeviceArray((max(self.local_size, 1),), np.float32)
+        self.global_vec = DeviceArray((N, max(G, 1)), np.float32).flat_view(0, N * G, (N, G))
+        pairs, off, row = [], 0, 0
+        for p in parts:
+            n = len(p.tl)
+            pairs.append((self.local.flat_view(off, p.local_size), p.local.flat_view(0, p.local_size)))
+            pairs.append((self.global_vec.flat_view(row * G, n * G), p.global_vec.flat_view(0, n * G)))
+            off, row = off + p.local_size, row + n
+        backend.copy_many(pairs)
+        return self
+
+    # ---- the device side ----
+    def tables(self):
+        """(local_off, tl) on the device, uploaded once."""
+        if self._tables is None:
+            self._tables = (backend.to_device(self.local_off), backend.to_device(self.tl))
+        return self._tables
+
+    def struct(self, column, col_seq=None):
+        """The vqvae_gen_latent_cond of this condition writing to ``column``."""
+        if self.local is None or self.global_vec is None:
+            raise RuntimeError('LatentCondition: no device data (built from its description alone)')
+        off, tl = self.tables()
+        c = _lib.GenLatentCond()
+        c.local, c.local_off, c.tl, c.global_vec = self.local.ptr, off.ptr, tl.ptr, self.global_vec.ptr
+        c.col_seq = None if col_seq is None else col_seq.ptr
+        c.column = column.ptr
+        c.n_seq, c.Cl, c.G, c.upscale = len(self.tl), self.Cl, self.G, self.upscale
+        return c
+
+    def dense(self):
+        """The condition as the other paths take it: the float32 device array (N, Cc, Tmax), sequence i expanded to its
+        upscale * tl[i] samples by vqvae_upsample_linear_fwd and vqvae_embed_broadcast_fwd (the kernels ConditionEmbed's
+        full-rate form runs) and zero-padded to the longest."""
+        from .functions import resize_tables
+        if self.local is None or self.global_vec is None:
+            raise RuntimeError('LatentCondition: no device data (built from its description alone)')
+        N, Cc, Tmax = self.shape
+        Cl, G = self.Cl, self.G
+        ids = backend.to_device(np.arange(N, dtype=np.int32))
+
+        def expand(y, q, B, Tl, T):
+            tb = resize_tables(Tl, T)
+            if Cl:
+                _lib.call('vqvae_upsample_linear_fwd', self.local.ptr + 4 * int(self.local_off[q]), B, Cl, Tl, T, tb['v0'].ptr,
+                          tb['v1'].ptr, tb['w0'].ptr, tb['w1'].ptr, y.ptr, Cc * T, _S())
+            if G:
+                _lib.call('vqvae_embed_broadcast_fwd', self.global_vec.ptr, ids.ptr + 4 * q, B, G, T, y.ptr + 4 * Cl * T, Cc * T, _S())
+
+        if (self.tl == self.tl[0]).all():                 # equal lengths: the blocks are one (N, Cl, Tl) tensor
+            out = DeviceArray((N, Cc, Tmax), np.float32)
+            expand(out, 0, N, int(self.tl[0]), Tmax)
+            return out
+        out = backend.zeros((N, Cc, Tmax), np.float32)
+        pairs, keep = [], []
+        for q in range(N):
+            Tl = int(self.tl[q])
+            T = self.upscale * Tl
+            y = DeviceArray((Cc, T), np.float32)
+            expand(y, q, 1, Tl, T)
+            keep.append(y)
+            pairs += [(out.flat_view((q * Cc + ch) * Tmax, T), y.flat_view(ch * T, T)) for ch in range(Cc)]
+        backend.copy_many(pairs)
+        backend.synchronize()                              # the per-sequence buffers go out of scope here
+        return out
+
+
+def refuse_latent(condition, who):
+    """The paths that read the dense condition say so instead of failing on an attribute."""
+    if isinstance(condition, LatentCondition):
+        raise TypeError('%s reads the full-rate condition tensor (a persistent launch runs thousands of steps and cannot '
+                        'take a per-step column): pass condition.dense(), or use generate_lockstep, which takes a '
+                        'LatentCondition as it is' % who)
+
+
 class GenerationState(object):
     """Device state behind WaveNet.initialize(n): zero queues (modules.py:58-67, 232-244) as
     per-block rings of ``dilation`` slots, the 2-sample embed queue, the step counter."""
@@ -172,14 +369,24 @@ class GenerationState(object):
 
     # ---- the whole loop of generate.py:105-145 on the device ----------------------------------
     def run(self, condition, uniforms, mode, n_steps=None, forced=None, return_logits=False,
-            graph_steps=8, persistent=False, chunk=4096, sampling=None):
+            graph_steps=8, persistent=False, chunk=4096, sampling=None, col_seq=None):
         """``sampling``: None or the tuple of sampling_controls(n, ...).  With controls every step ends in the filtered
         sampler of csrc/sampling.hip (vqvae_wavenet_gen_step_sampled) and ``persistent`` is not honoured: the persistent
-        kernel has no filtered form, the run is a replayed hipGraph of per-step launches."""
+        kernel has no filtered form, the run is a replayed hipGraph of per-step launches.
+        ``condition`` may be a LatentCondition (per-step launches only): every step then starts with the launch that
+        computes its condition column (vqvae_gen_cond_column), and ``col_seq`` (n,) int32 on the device, or None for the
+        identity, says which of the object's sequences sits in which column."""
         n = self.n
-        if condition.ndim == 4:
+        latent = isinstance(condition, LatentCondition)
+        if latent:
+            if persistent:
+                refuse_latent(condition, 'the persistent kernel')
+            if condition.shape[1] != self.cond_dim or (col_seq is None and condition.shape[0] != n):
+                raise ValueError('generate_lockstep: the latent condition must be (n, condition_dim, T) = (%d, %d, T), got %s'
+                                 % (n, self.cond_dim, condition.shape))
+        elif condition.ndim == 4:
             condition = condition.reshape(condition.shape[:3])
-        if condition.shape[:2] != (n, self.cond_dim):
+        if not latent and condition.shape[:2] != (n, self.cond_dim):
             raise ValueError('generate_sequence: condition must be (n, condition_dim, T[, 1]) = (%d, %d, T), got %s'
                              % (n, self.cond_dim, condition.shape))
         T = condition.shape[2]
@@ -201,7 +408,13 @@ class GenerationState(object):
         logits_out = DeviceArray((max(steps, 1), n, self.out_dim), np.float32) if return_logits else None
         d = self.desc
         d.sample_mode = mode
-        d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = condition.ptr, self.cond_dim * T, T, 1
+        if latent:
+            # the step reads the compact column its first launch wrote: (n, cond_dim), unit stride, no time axis
+            self._column = backend.zeros((n, self.cond_dim), np.float32)
+            lat = condition.struct(self._column, col_seq)
+            d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = self._column.ptr, self.cond_dim, 1, 0
+        else:
+            d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = condition.ptr, self.cond_dim * T, T, 1
         d.uniforms, d.n_uniform = u_dev.ptr, n_uniform
         d.forced_next = None if forced_dev is None else forced_dev.ptr
         d.out, d.out_bstride = out.ptr, T
@@ -210,14 +423,19 @@ class GenerationState(object):
             raise RuntimeError('generate_sequence starts from fresh queues: call initialize(n) first')
         d.max_steps = steps
         if sampling is None:
-            def step():
+            def network_step():
                 _lib.call('vqvae_wavenet_gen_step', C.byref(d), _S())
         else:
             smp, self._controls = _upload_controls(sampling)
             persistent = False
 
-            def step():
+            def network_step():
                 _lib.call('vqvae_wavenet_gen_step_sampled', C.byref(d), C.byref(smp), _S())
+        step = network_step
+        if latent:
+            def step():
+                _lib.call('vqvae_gen_cond_column', C.byref(lat), C.byref(d), None, _S())
+                network_step()
         nbytes = 0
         if steps and persistent:
             # the library picks the width class (<= 256 or <= 512 channels per vector); shapes outside
@@ -267,6 +485,7 @@ def run_many(wavenet, condition, uniforms, mode, n_steps=None, group=_lib.GEN_MA
     they run concurrently (a launch occupies 128 or 256 two-wave workgroups: a fraction of the GPU).
     condition (N, condition_dim, T) on the device, uniforms (T, N[, nr_mix]) on the host.
     Returns the host array (N, T) of sampled bins / values."""
+    refuse_latent(condition, 'generate_batch')
     if condition.ndim == 4:
         condition = condition.reshape(condition.shape[:3])
     N, Cc, T = condition.shape
@@ -380,6 +599,20 @@ def _device_group_runner(wavenet, condition, mode, graph_steps, return_logits):
     return run_group
 
 
+def _latent_group_runner(wavenet, condition, mode, graph_steps, return_logits):
+    """One group of run_lockstep from a LatentCondition: no condition rows are gathered; the group's indices (repeats of
+    the last member included) go to the device as ``col_seq`` and every step computes its (n, condition_dim) column."""
+    def run_group(idx, u, forced, steps, sampling=None):
+        st = LockstepState(wavenet, len(idx))
+        col_seq = backend.to_device(np.ascontiguousarray(idx, dtype=np.int32))
+        res = st.run(condition, u, mode, steps, forced, return_logits, graph_steps, persistent=False, sampling=sampling,
+                     col_seq=col_seq)
+        if return_logits:
+            return res[0].get(), res[1].get()[:steps]
+        return res.get(), None
+    return run_group
+
+
 def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None, forced=None, return_logits=False,
                  graph_steps=8, group=_lib.GEN_MAX_LOCKSTEP, _run_group=None, sampling=None):
     """Many sequences at once (converting a validation set or a corpus): N sequences of any count as groups of
@@ -394,7 +627,12 @@ def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None,
     (max steps, N, out_dim), rows past a sequence's own steps 0).  Every sequence gets the values it gets in any
     other batch of 5..128 and in any other position of it, bit for bit.
     ``sampling``: None or the tuple of sampling_controls(N, ...); every group gets its members' values, gathered with the
-    group's indices like the uniforms (repeats of the last member included), and the promise above holds with them."""
+    group's indices like the uniforms (repeats of the last member included), and the promise above holds with them.
+    ``condition`` may be a LatentCondition: T is its longest sequence, ``lengths`` defaults to its own, and the values are
+    those of the call with ``condition.dense()``, bit for bit, without that tensor."""
+    latent = isinstance(condition, LatentCondition)
+    if latent and lengths is None:
+        lengths = condition.lengths
     if condition.ndim == 4:
         condition = condition.reshape(condition.shape[:3])
     N, Cc, T = condition.shape
@@ -414,7 +652,8 @@ def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None,
         forced = np.asarray(forced).reshape(-1, N)
         if forced.shape[0] < max_steps:
             raise ValueError('generate_lockstep: forced must be (steps, N) = (%d, %d), got %s' % (max_steps, N, forced.shape))
-    run_group = _run_group or _device_group_runner(wavenet, condition, mode, graph_steps, return_logits)
+    run_group = _run_group or (_latent_group_runner if latent else _device_group_runner)(
+        wavenet, condition, mode, graph_steps, return_logits)
     out = np.zeros((N, T), np.int32 if softmax else np.float32)                  # generate.py:103
     logits = np.zeros((max_steps, N, out_dim), np.float32) if return_logits else None
     for idx, gsteps in groups:
@@ -482,12 +721,14 @@ class LockstepRefill(object):
     LockstepState of S slots, ``graph_steps`` ticks captured as a hipGraph (0 = eager) and replayed
     ceil(ticks / graph_steps) times; surplus ticks are device no-ops.
 
-    Device memory besides the decoder state of S slots: the condition (N, condition_dim, T) floats as the caller holds
-    it, the dense uniforms max_steps x N x n_uniform doubles and forced values max_steps x N, ``out`` N x T, with
+    Device memory besides the decoder state of S slots: the condition as the caller holds it (the (N, condition_dim, T)
+    floats, 2 560 bytes per sample for the default model, or a LatentCondition: 4 Cl sum(tl) + 4 G N bytes, 32 bytes per
+    sample, plus the (N, condition_dim) column that every tick's first launch, vqvae_gen_cond_column, fills for the live
+    slots), the dense uniforms max_steps x N x n_uniform doubles and forced values max_steps x N, ``out`` N x T, with
     ``return_logits`` max_steps x N x out_dim floats (a test and inspection facility: 25 MB per 100 steps of 256
     sequences and classes), and 3 N + 2 S + 2 integers of table.  For a corpus of N = 300 utterances of up to 10 s at
-    16 kHz the uniforms are 384 MB; the rows are dense because ragged storage would make a sequence's addresses
-    depend on its neighbours' lengths."""
+    16 kHz the dense condition would be 123 GB and the latent one is at most 1.5 GB; the uniforms are 384 MB; their rows
+    are dense because ragged storage would make a sequence's addresses depend on its neighbours' lengths."""
 
     def __init__(self, wavenet, condition, steps, u, forced, mode, group, return_logits=False, sampling=None):
         N, Cc, T = condition.shape
@@ -511,7 +752,14 @@ class LockstepRefill(object):
         self.started = backend.to_device(np.full((N, 2), -1, np.int32))
         d = self.desc = st.desc
         d.sample_mode = mode
-        d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = condition.ptr, Cc * T, T, 1
+        self._lat = None
+        if isinstance(condition, LatentCondition):
+            # rows are addressed by the sequence: (N, condition_dim); a tick's first launch writes the live slots' rows
+            self.column = backend.zeros((N, Cc), np.float32)
+            self._lat = condition.struct(self.column)
+            d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = self.column.ptr, Cc, 1, 0
+        else:
+            d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = condition.ptr, Cc * T, T, 1
         d.uniforms, d.n_uniform = self._keep[3].ptr, n_uniform
         d.forced_next = None
         if forced is not None:
@@ -533,6 +781,8 @@ class LockstepRefill(object):
         _lib.call('vqvae_gen_slots_init', C.byref(d), C.byref(t), _S())
 
     def tick(self):
+        if self._lat is not None:         # reads the table vqvae_gen_slots_init or the previous tick's scheduler left behind
+            _lib.call('vqvae_gen_cond_column', C.byref(self._lat), C.byref(self.desc), C.byref(self.table), _S())
         _lib.call('vqvae_wavenet_gen_step_slots', C.byref(self.desc), C.byref(self.table),
                   None if self._smp is None else C.byref(self._smp), _S())
 
@@ -584,6 +834,8 @@ def run_lockstep_refill(wavenet, condition, uniforms, mode, n_steps=None, length
     and return value as run_lockstep; every sequence gets the values run_lockstep gives it, bit for bit.
     ``_run(steps, u, forced, sampling)`` -> (out (N, T), logits (max steps, N, out_dim) or None), both in the caller's
     order, stands in for the device in host tests."""
+    if isinstance(condition, LatentCondition) and lengths is None:
+        lengths = condition.lengths
     if condition.ndim == 4:
         condition = condition.reshape(condition.shape[:3])
     N, Cc, T = condition.shape

@@ -936,8 +936,10 @@ class WaveNet(Chain):
         """modules.py:246-255: one step.  x (n, input_dim, 1, 1), condition (n, condition_dim, 1, 1)
         -> logits Variable (n, out_dim, 1, 1); the queues advance by one sample."""
         from .core import Variable
+        from .generation import refuse_latent
         xd = x.data if isinstance(x, Variable) else x
         cd = condition.data if isinstance(condition, Variable) else condition
+        refuse_latent(cd, 'generate')
         backend.require_device(xd, cd)
         return Variable(self._gen_state().step_logits(xd, cd))
 
@@ -958,10 +960,14 @@ class WaveNet(Chain):
         off), top_p in (0, 1] (1 = off); the mixture of logistics takes a temperature > 0 only.  All None is the call
         as it was.  With any control the persistent kernel is not used, whatever ``persistent`` says: it has no filtered
         form, and the run is the replayed hipGraph of per-step kernels (for one sequence of the default decoder 667 us
-        against 95 us per sample)."""
+        against 95 us per sample).
+
+        The condition is the dense tensor: a generation.LatentCondition is a TypeError here (the persistent launch runs
+        thousands of steps and cannot take a per-step column); generate_lockstep takes one, ``.dense()`` expands it."""
         from .core import Variable
-        from .generation import sampling_controls
+        from .generation import refuse_latent, sampling_controls
         cd = condition.data if isinstance(condition, Variable) else condition
+        refuse_latent(cd, 'generate_sequence')
         sampling = sampling_controls(cd.shape[0], temperature, top_k, top_p, self.use_logistic, 'generate_sequence')
         backend.require_device(cd)
         self.initialize(cd.shape[0])
@@ -976,9 +982,11 @@ class WaveNet(Chain):
         device, uniforms (T, N[, nr_mix]) host doubles; returns the host array (N, T).  Every sequence
         gets exactly the samples generate_sequence would give it alone with its column of uniforms.
         It exists only as persistent launches, which have no filtered sampler: any of ``temperature`` / ``top_k`` /
-        ``top_p`` is a ValueError; generate_lockstep takes them."""
+        ``top_p`` is a ValueError; generate_lockstep takes them.  So is a generation.LatentCondition a TypeError: the
+        persistent launches read the dense tensor (``.dense()``); generate_lockstep takes the latent form."""
         from .core import Variable
-        from .generation import run_many
+        from .generation import refuse_latent, run_many
+        refuse_latent(condition.data if isinstance(condition, Variable) else condition, 'generate_batch')
         if temperature is not None or top_k is not None or top_p is not None:
             raise ValueError('generate_batch runs persistent launches only, which have no sampling controls: '
                              'use generate_lockstep (any number of sequences) or generate_sequence (n <= 4)')
@@ -1002,12 +1010,19 @@ class WaveNet(Chain):
         slot whose sequence has finished takes the next waiting one, longest first, on the device
         (csrc/generate_slots.hip; generation.run_lockstep_refill documents the memory it needs).  Every other argument
         means what it means without, the return value is the same, bit for bit.  False (the default) is the call as
-        it was."""
+        it was.
+        ``condition`` may be a generation.LatentCondition instead of the dense tensor: the local latents and the speaker
+        vectors the tensor is an up-sampling of, 1/80 of its bytes for the default model (32 instead of 2 560 per
+        sample).  Every step, with and without ``refill``, then starts with one small launch that computes the
+        condition column of each live sequence (csrc/generate_cond.hip); T is the longest sequence, ``lengths`` defaults
+        to the object's own, and the return value is that of the call with ``condition.dense()``, bit for bit.  The way to
+        convert a corpus whose dense condition does not fit the device."""
         from .core import Variable
-        from .generation import run_lockstep, run_lockstep_refill, sampling_controls
+        from .generation import LatentCondition, run_lockstep, run_lockstep_refill, sampling_controls
         cd = condition.data if isinstance(condition, Variable) else condition
         sampling = sampling_controls(cd.shape[0], temperature, top_k, top_p, self.use_logistic, 'generate_lockstep')
-        backend.require_device(cd)
+        if not isinstance(cd, LatentCondition):
+            backend.require_device(cd)
         mode = _lib.GEN_MOL if self.use_logistic else _lib.GEN_SOFTMAX
         if refill:
             return run_lockstep_refill(self, cd, uniforms, mode, n_steps, lengths, forced, return_logits, graph_steps,

@@ -6,6 +6,9 @@ usage: python tools/gen_bench.py [--workload c2|c5|ref] [--n 1] [--steps 16000] 
            a lower rate keeps the list's shape and shrinks the run) through generate_lockstep twice: as sorted groups
            (refill=False) and with the columns refilled on the device (refill=True)
        python tools/gen_bench.py --workload ref --lockstep 128 --refill    equal lengths through the refilled kernels (tick cost)
+       ... --lockstep N / --lengths-n N --latent-cond    the condition kept at the latent rate (generation.LatentCondition: random
+           latents of ceil(T / 64) frames instead of the dense (N, Cc, T) array, which is never made); prints the bytes of
+           both forms.  With --lengths-n, --refill runs the refilled road only
        ... [--temperature 0.8] [--top-k 32] [--top-p 0.95]   sampling controls (every sequence the same); with any of them
        generate_sequence runs the per-step kernels, and --batch refuses"""
 import argparse
@@ -25,6 +28,13 @@ def gamma_lengths(n, seed, rate=16000.0):
     return np.maximum((np.clip(rs.gamma(2.0, 1.8, n), 0.5, 10.0) * rate).astype(np.int64), 2)
 
 
+def random_latents(backend, rs, tl, Cl, G, upscale=64):
+    """A LatentCondition of random values, uploaded sequence by sequence."""
+    from vqvae_amd.generation import LatentCondition
+    latents = [backend.to_device(rs.standard_normal((Cl, int(t))).astype(np.float32)) for t in tl]
+    return LatentCondition.from_latents(latents, backend.to_device(rs.standard_normal((len(tl), G)).astype(np.float32)), upscale)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='c2', help='c2 / c5: BASELINE decoders (256 channels); ref: the reference\'s default '
@@ -39,6 +49,8 @@ def main():
     ap.add_argument('--lockstep', type=int, default=0, help='N sequences through generate_lockstep (groups of <= --group, default 128, '
                     'advancing together on the MFMA kernels); --graph-steps 0 = eager launches')
     ap.add_argument('--refill', action='store_true', help='--lockstep through generate_lockstep(refill=True)')
+    ap.add_argument('--latent-cond', action='store_true', help='--lockstep / --lengths-n: the condition as a LatentCondition '
+                    '(local latents 4/5 of the condition channels, x64), not the dense array')
     ap.add_argument('--lengths-n', type=int, default=0, help='N utterances of seeded gamma lengths, sorted groups against refill')
     ap.add_argument('--lengths-seed', type=int, default=0)
     ap.add_argument('--lengths-rate', type=float, default=16000.0, help='samples per second of the length list (default 16 kHz)')
@@ -56,6 +68,7 @@ def main():
     ref = a.workload == 'ref'
     n_loop = 4 if mol else 3 if ref else 2
     Cc = 640 if ref else 192
+    Cl = 512 if ref else 128                                 # --latent-cond: local channels; the rest is the speaker vector
     if ref:
         dec = WaveNet(n_loop, 10, 2, 256, 512, 512, 256, 256, False, 30, -40, Cc, 0)
     else:
@@ -76,33 +89,47 @@ def main():
         steps, groups = plan_lockstep(N, T, lengths, group=group)
         ticks = dict(sorted=sum(g for _, g in groups), refill=plan_refill(steps, refill_slots((steps > 0).sum(), group))[0])
         rs = np.random.RandomState(0)
-        cond = backend.zeros((N, Cc, T), np.float32)
-        for i in range(N):                                   # row by row: the whole array may not fit the host twice
-            cond.flat_view(i * Cc * T, Cc * T).set(rs.standard_normal(Cc * T).astype(np.float32))
+        if a.latent_cond:
+            cond = random_latents(backend, rs, -(-lengths // 64), Cl, Cc - Cl)
+            print('condition: latent %d bytes; dense (N, Cc, T) = (%d, %d, %d) would be %d bytes (%.1f GB), %.1fx'
+                  % (cond.nbytes, N, Cc, T, 4 * N * Cc * T, 4e-9 * N * Cc * T, 4.0 * N * Cc * T / cond.nbytes))
+        else:
+            cond = backend.zeros((N, Cc, T), np.float32)
+            for i in range(N):                               # row by row: the whole array may not fit the host twice
+                cond.flat_view(i * Cc * T, Cc * T).set(rs.standard_normal(Cc * T).astype(np.float32))
         u = rs.uniform(0.01, 0.99, (T, N, 10 if mol else 1))
         short = np.minimum(lengths, 65)
-        for refill in (False, True):                         # warm-up of both roads
+        roads = (('refill', True),) if a.refill else (('sorted', False), ('refill', True))
+        for _, refill in roads:                              # warm-up of the roads
             dec.generate_lockstep(cond, u, lengths=short, group=group, graph_steps=a.graph_steps, refill=refill, **ctl)
         print('lengths workload %s N=%d seed %d rate %g: %d samples, longest %d, group %d graph-steps %d,%s; lower bound %d ticks'
               % (a.workload, N, a.lengths_seed, a.lengths_rate, steps.sum(), steps.max(), group, a.graph_steps, ctl_txt,
                  max(int(steps.max()), -(-int(steps.sum()) // group))))
         res = {}
-        for name, refill in (('sorted', False), ('refill', True)):
+        for name, refill in roads:
             t0 = time.time()
             res[name] = dec.generate_lockstep(cond, u, lengths=lengths, group=group, graph_steps=a.graph_steps, refill=refill, **ctl)
             dt = time.time() - t0
             print('  %-6s %8d ticks in %8.3f s = %7.1f us/tick, %9.0f samples/s' % (name, ticks[name], dt, 1e6 * dt / ticks[name],
                                                                               steps.sum() / dt))
             res[name + '_dt'] = dt
-        print('  ticks sorted / refill %.3f, wall sorted / refill %.3f, outputs equal: %s'
-              % (ticks['sorted'] / ticks['refill'], res['sorted_dt'] / res['refill_dt'], np.array_equal(res['sorted'], res['refill'])))
         if a.dump:
             np.save(a.dump, res['refill'])
+        if a.refill:
+            return
+        print('  ticks sorted / refill %.3f, wall sorted / refill %.3f, outputs equal: %s'
+              % (ticks['sorted'] / ticks['refill'], res['sorted_dt'] / res['refill_dt'], np.array_equal(res['sorted'], res['refill'])))
         return
     if a.lockstep:
         group = a.group if a.group > 4 else 128
         rs = np.random.RandomState(0)
-        cond = backend.to_device(rs.standard_normal((a.lockstep, Cc, T)).astype(np.float32))
+        if a.latent_cond:
+            cond = random_latents(backend, rs, [-(-T // 64)] * a.lockstep, Cl, Cc - Cl)
+            T = cond.shape[2]
+            ctl = dict(ctl, lengths=np.full(a.lockstep, a.steps + 1))         # the dense run's steps, whatever 64 * frames is
+            ctl_txt += ' latent condition (%d bytes, dense %d)' % (cond.nbytes, 4 * a.lockstep * Cc * (a.steps + 1))
+        else:
+            cond = backend.to_device(rs.standard_normal((a.lockstep, Cc, T)).astype(np.float32))
         u = rs.uniform(0.01, 0.99, (T, a.lockstep, 10 if mol else 1))
         if a.refill:
             ctl = dict(ctl, refill=True)
