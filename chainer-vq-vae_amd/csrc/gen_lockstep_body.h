@@ -14,6 +14,7 @@
 #ifndef VQ_GEN_LOCKSTEP_BODY_H_
 #define VQ_GEN_LOCKSTEP_BODY_H_
 #include "common.h"
+#include "gen_rng.h"
 #include "../../include/vqvae_sampling.h"
 
 namespace vq {
@@ -85,6 +86,22 @@ struct LsSlots {
   __device__ __forceinline__ int n_seq(int) const { return nseq; }
   __device__ __forceinline__ bool last(const LsCol& c) const { return c.t + 1 >= steps[c.seq]; }   // live columns only
   __device__ __forceinline__ float* x_prev_row(int c, int input_dim) const { return x_prev + (size_t)c * input_dim; }
+};
+
+// ---- where the uniform for (t, sq, j) comes from: a second template argument of the two finishing bodies ----
+// LsArrayUniforms: the descriptor's (T, n_seq, n_uniform) array; the bodies keep their own load expression for it, so the
+//   kernels of generate_lockstep.hip, sampling.hip and generate_slots.hip compile to what they compiled to without it.
+// LsPhiloxUniforms (gen_rng.hip): computed by the threads that did the load (include/vqvae_gen_rng.h); ids[sq].
+struct LsArrayUniforms { static constexpr bool kArray = true; };
+
+struct LsPhiloxUniforms {
+  static constexpr bool kArray = false;
+  unsigned long long seed; const unsigned long long* ids;
+  int t0;                  // added to t: 0 in a step; the step of vqvae_sample_logits_rng, whose kernel runs at t = 0
+  __device__ __forceinline__ double operator()(int t, int sq, int j) const {
+    const unsigned long long id = ids ? ids[sq] : (unsigned long long)sq;
+    return gen_rng_uniform(seed, id, (uint32_t)(t0 + t), (uint32_t)j);
+  }
 };
 
 // elements k..k+3 of a row (nullptr: a row / column outside the problem), zero past `lim`
@@ -263,8 +280,8 @@ struct LsFinishArgs {
 
 // The feedback of a sequence's last step under LsSlots is the fresh embed queue of the slot's next tenant: zeros in
 // x_cur and in x_prev (this step's x_prev <- x_cur shift has run in block 0's launch).
-template <class P>
-__device__ __forceinline__ void ls_finish_body(const LsFinishArgs& a, const P& pol) {
+template <class P, class U = LsArrayUniforms>
+__device__ __forceinline__ void ls_finish_body(const LsFinishArgs& a, const P& pol, const U& uni = U{}) {
   __shared__ float p_s[LS_MAXOUT];
   __shared__ double cdf_s[LS_MAXOUT];
   __shared__ float red_s[4];
@@ -306,7 +323,9 @@ __device__ __forceinline__ void ls_finish_body(const LsFinishArgs& a, const P& p
     }
     __syncthreads();
     const double total = cdf_s[a.out_dim - 1];
-    const double u = a.uniforms[((size_t)t * ns + sq) * a.n_uniform];
+    double u;
+    if constexpr (U::kArray) u = a.uniforms[((size_t)t * ns + sq) * a.n_uniform];
+    else u = uni(t, sq, 0);
     int cnt = 0;
     for (int i = tid; i < a.out_dim; i += 256) cnt += (cdf_s[i] / total <= u) ? 1 : 0;
 #pragma unroll
@@ -334,7 +353,9 @@ __device__ __forceinline__ void ls_finish_body(const LsFinishArgs& a, const P& p
       for (int j = 0; j < nr; ++j) {
         const float pj = expf(l[j] - m) / s;
         const float sc = expf(fmaxf(l[2 * nr + j], a.log_scale_min));               // generate.py:111-112
-        const double u = a.uniforms[((size_t)t * ns + sq) * a.n_uniform + j];
+        double u;
+        if constexpr (U::kArray) u = a.uniforms[((size_t)t * ns + sq) * a.n_uniform + j];
+        else u = uni(t, sq, j);
         double rv = (double)l[nr + j] + (double)sc * (log(u) - log(1.0 - u));       // generate.py:115-118
         acc += rv * (double)pj;                                                     // generate.py:121-122
       }
@@ -379,8 +400,8 @@ __device__ __forceinline__ unsigned long long smp_key(float v, int i) {
   return ((unsigned long long)(~asc) << 32) | (uint32_t)i;
 }
 
-template <class P>
-__device__ __forceinline__ void smp_finish_body(const SampledArgs& a, const P& pol) {
+template <class P, class U = LsArrayUniforms>
+__device__ __forceinline__ void smp_finish_body(const SampledArgs& a, const P& pol, const U& uni = U{}) {
   __shared__ unsigned long long key_s[SMP_MAXOUT];
   __shared__ double cdf_s[SMP_MAXOUT];
   __shared__ float p_s[SMP_MAXOUT];
@@ -471,7 +492,9 @@ __device__ __forceinline__ void smp_finish_body(const SampledArgs& a, const P& p
     }
     __syncthreads();
     const double total = cdf_s[O - 1];
-    const double u = a.uniforms[((size_t)t * ns + sq) * a.n_uniform];
+    double u;
+    if constexpr (U::kArray) u = a.uniforms[((size_t)t * ns + sq) * a.n_uniform];
+    else u = uni(t, sq, 0);
     int cnt = 0;
     for (int i = tid; i < O; i += SMP_THREADS) cnt += (cdf_s[i] / total <= u) ? 1 : 0;
 #pragma unroll
@@ -505,7 +528,9 @@ __device__ __forceinline__ void smp_finish_body(const SampledArgs& a, const P& p
       for (int j = 0; j < nr; ++j) {
         const float pj = expf(l[j] * inv - m) / s;
         const float sc = expf(fmaxf(l[2 * nr + j], a.log_scale_min)) * T;           // generate.py:111-112, tempered
-        const double u = a.uniforms[((size_t)t * ns + sq) * a.n_uniform + j];
+        double u;
+        if constexpr (U::kArray) u = a.uniforms[((size_t)t * ns + sq) * a.n_uniform + j];
+        else u = uni(t, sq, j);
         double rv = (double)l[nr + j] + (double)sc * (log(u) - log(1.0 - u));       // generate.py:115-118
         acc += rv * (double)pj;                                                     // generate.py:121-122
       }

@@ -266,7 +266,7 @@ int gen_step_lockstep(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hi
 int gen_finish_sampled(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st);  // sampling.hip: finish + advance
 
 // What every step entry point rejects before it launches anything (generate_slots.hip asks the same of its descriptor).
-int gen_validate_desc(const vqvae_gen_desc* d) {
+static int gen_validate_desc_impl(const vqvae_gen_desc* d, bool array_uniforms) {
   VQ_REQUIRE(d, "gen_step: null descriptor");
   VQ_REQUIRE(d->n >= 1 && d->n <= VQVAE_GEN_MAX_LOCKSTEP, "gen_step: n must be 1..%d sequences (got %d)", VQVAE_GEN_MAX_LOCKSTEP, d->n);
   VQ_REQUIRE(d->n_blocks >= 1 && d->blocks, "gen_step: no residual blocks");
@@ -277,12 +277,16 @@ int gen_validate_desc(const vqvae_gen_desc* d) {
   VQ_REQUIRE(d->cond_dim == 0 || d->cond, "gen_step: condition missing");
   VQ_REQUIRE(d->sample_mode == VQVAE_GEN_NONE || d->sample_mode == VQVAE_GEN_SOFTMAX || d->sample_mode == VQVAE_GEN_MOL, "gen_step: bad sample_mode");
   if (d->sample_mode != VQVAE_GEN_NONE) {
-    VQ_REQUIRE(d->uniforms && d->n_uniform >= 1, "gen_step: sampling needs uniforms");
+    VQ_REQUIRE((d->uniforms || !array_uniforms) && d->n_uniform >= 1, "gen_step: sampling needs uniforms");
     if (d->sample_mode == VQVAE_GEN_SOFTMAX) VQ_REQUIRE(d->out_dim <= GEN_MAXOUT, "gen_step: at most %d classes", GEN_MAXOUT);
     else VQ_REQUIRE(d->out_dim % 3 == 0 && d->n_uniform >= d->out_dim / 3, "gen_step: mixture sampling needs out_dim = 3*nr_mix and nr_mix uniforms");
   }
   return 0;
 }
+
+int gen_validate_desc(const vqvae_gen_desc* d) { return gen_validate_desc_impl(d, true); }
+// the same for the entry points of include/vqvae_gen_rng.h, which draw the uniforms themselves: d->uniforms may be null
+int gen_validate_desc_rng(const vqvae_gen_desc* d) { return gen_validate_desc_impl(d, false); }
 
 // One step.  smp == nullptr: vqvae_wavenet_gen_step; else the sampling controls of include/vqvae_sampling.h, which
 // replace the finish launch and nothing else.

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(64) void gen_lockstep_advance_kernel(int* step, int
   if (threadIdx.x == 0 && t < max_steps) *step = t + 1;
 }
 
-static int ls_launch(const LsGemmArgs& g, hipStream_t st) {
+int ls_launch(const LsGemmArgs& g, hipStream_t st) {   // also the products of gen_rng.hip's step
   hipLaunchKernelGGL(gen_lockstep_gemm_kernel, ls_gemm_grid(g), dim3(LS_THREADS), 0, st, g);
   VQ_LAUNCH_CHECK();
   return 0;

@@ -134,25 +134,30 @@ extern "C" int vqvae_gen_slots_init(const vqvae_gen_desc* d, const vqvae_gen_slo
   return 0;
 }
 
-extern "C" int vqvae_wavenet_gen_step_slots(const vqvae_gen_desc* d, const vqvae_gen_slots* slots,
-                                            const vqvae_gen_sampling* s, vqvae_stream_t stream) {
-  int bad = slots_validate(d, slots, "gen_step_slots");
+// One tick.  finish == nullptr: the finishing kernels above read the descriptor's array of uniforms; else `finish`
+// launches the finishing kernel (gen_rng.hip: the uniforms drawn on the device; d->uniforms may then be null).
+namespace vq {
+int gen_validate_desc_rng(const vqvae_gen_desc* d);   // generate.hip
+typedef int (*SlotsFinish)(const vqvae_gen_desc* d, const vqvae_gen_sampling* controls, const LsSlots& p, const void* ctx,
+                           hipStream_t st);
+int gen_step_slots_impl(const vqvae_gen_desc* d, const vqvae_gen_slots* slots, const vqvae_gen_sampling* s, const char* who,
+                        SlotsFinish finish, const void* ctx, hipStream_t st) {
+  int bad = slots_validate(d, slots, who);
   if (bad != 0) return bad;
-  if ((bad = gen_validate_desc(d)) != 0) return bad;
+  if ((bad = finish ? gen_validate_desc_rng(d) : gen_validate_desc(d)) != 0) return bad;
   const bool controls = s && (s->temperature || s->top_k || s->top_p);
-  VQ_REQUIRE(d->sample_mode != VQVAE_GEN_NONE || d->logits_out, "gen_step_slots: sample_mode VQVAE_GEN_NONE needs logits_out");
+  VQ_REQUIRE(d->sample_mode != VQVAE_GEN_NONE || d->logits_out, "%s: sample_mode VQVAE_GEN_NONE needs logits_out", who);
   VQ_REQUIRE(!controls || d->sample_mode != VQVAE_GEN_NONE,
-             "gen_step_slots: sampling controls need sample_mode VQVAE_GEN_SOFTMAX or VQVAE_GEN_MOL");
+             "%s: sampling controls need sample_mode VQVAE_GEN_SOFTMAX or VQVAE_GEN_MOL", who);
   VQ_REQUIRE(!controls || d->sample_mode != VQVAE_GEN_MOL || (!s->top_k && !s->top_p),
-             "gen_step_slots: the mixture of logistics takes a temperature only (top_k and top_p must be NULL)");
-  VQ_REQUIRE(d->sample_mode != VQVAE_GEN_SOFTMAX || d->out_dim <= LS_MAXOUT, "gen_step_slots: at most %d classes", LS_MAXOUT);
+             "%s: the mixture of logistics takes a temperature only (top_k and top_p must be NULL)", who);
+  VQ_REQUIRE(d->sample_mode != VQVAE_GEN_SOFTMAX || d->out_dim <= LS_MAXOUT, "%s: at most %d classes", who, LS_MAXOUT);
   for (int l = 0; l < d->n_blocks; ++l) {
     const vqvae_gen_block& bk = d->blocks[l];
     VQ_REQUIRE(bk.conv_W && bk.conv_b && bk.res_W && bk.res_b && bk.skip_W && bk.skip_b && bk.ring && bk.dilation >= 1,
-               "gen_step_slots: block %d incomplete", l);
-    VQ_REQUIRE(d->cond_dim == 0 || (bk.cond_W && bk.cond_b), "gen_step_slots: block %d has no condition projection", l);
+               "%s: block %d incomplete", who, l);
+    VQ_REQUIRE(d->cond_dim == 0 || (bk.cond_W && bk.cond_b), "%s: block %d has no condition projection", who, l);
   }
-  hipStream_t st = (hipStream_t)stream;
   LsSlots p{};
   p.slot_seq = slots->slot_seq; p.slot_t = slots->slot_t; p.live_count = slots->live; p.steps = slots->steps;
   p.x_prev = d->x_prev; p.nseq = slots->n_seq;
@@ -162,13 +167,23 @@ extern "C" int vqvae_wavenet_gen_step_slots(const vqvae_gen_desc* d, const vqvae
     return 0;
   }, st);
   if (rc != 0) return rc;
-  if (controls) {
-    hipLaunchKernelGGL(gen_slots_sampled_finish_kernel, dim3(d->n), dim3(SMP_THREADS), 0, st, smp_finish_args(d, s), p);
+  if (finish) {
+    if ((bad = finish(d, controls ? s : nullptr, p, ctx, st)) != 0) return bad;
   } else {
-    hipLaunchKernelGGL(gen_slots_finish_kernel, dim3(d->n), dim3(256), 0, st, ls_finish_args(d), p);
+    if (controls) {
+      hipLaunchKernelGGL(gen_slots_sampled_finish_kernel, dim3(d->n), dim3(SMP_THREADS), 0, st, smp_finish_args(d, s), p);
+    } else {
+      hipLaunchKernelGGL(gen_slots_finish_kernel, dim3(d->n), dim3(256), 0, st, ls_finish_args(d), p);
+    }
+    VQ_LAUNCH_CHECK();
   }
-  VQ_LAUNCH_CHECK();
   hipLaunchKernelGGL(gen_slots_schedule_kernel, dim3(1), dim3(64), 0, st, sched_args(d, slots));
   VQ_LAUNCH_CHECK();
   return 0;
+}
+}  // namespace vq
+
+extern "C" int vqvae_wavenet_gen_step_slots(const vqvae_gen_desc* d, const vqvae_gen_slots* slots,
+                                            const vqvae_gen_sampling* s, vqvae_stream_t stream) {
+  return gen_step_slots_impl(d, slots, s, "gen_step_slots", nullptr, nullptr, (hipStream_t)stream);
 }

@@ -87,6 +87,11 @@ class GenLatentCond(C.Structure):
                 ('n_seq', c_int), ('Cl', c_int), ('G', c_int), ('upscale', c_int)]
 
 
+class GenRng(C.Structure):
+    """vqvae_gen_rng (include/vqvae_gen_rng.h): the seed and the device array of stream ids (NULL = the identity)."""
+    _fields_ = [('seed', C.c_uint64), ('ids', P)]
+
+
 # name -> (restype, argtypes); this table IS the list of symbols the header declares
 PROTOTYPES = {
     'vqvae_last_error_string': (c_char_p, []),
@@ -313,6 +318,18 @@ GEN_COND_PROTOTYPES = {
 }
 GEN_COND_ABI_VERSION = 1          # vqvae_gen_cond_abi_version()
 
+# include/vqvae_gen_rng.h: the uniforms of generation drawn on the device (Philox4x32-10), a ninth table and version
+GEN_RNG_PROTOTYPES = {
+    'vqvae_gen_rng_abi_version': (c_int, []),
+    'vqvae_gen_rng_fill': (c_int, [C.POINTER(GenRng), c_int, c_int, c_int, c_int, P, P]),
+    'vqvae_sample_logits_rng': (c_int, [P, c_int, c_int, c_int, c_float, C.POINTER(GenRng), c_int, c_int,
+                                        C.POINTER(GenSampling), P, P, P]),
+    'vqvae_wavenet_gen_step_rng': (c_int, [C.POINTER(GenDesc), C.POINTER(GenSampling), C.POINTER(GenRng), P]),
+    'vqvae_wavenet_gen_step_slots_rng': (c_int, [C.POINTER(GenDesc), C.POINTER(GenSlots), C.POINTER(GenSampling),
+                                                 C.POINTER(GenRng), P]),
+}
+GEN_RNG_ABI_VERSION = 1           # vqvae_gen_rng_abi_version()
+
 # elementwise op codes / profiler tags (mirror the header)
 MAX_STACK_GROUP = 24              # blocks per resstack call (MAXSEG in csrc/gemm_common.h)
 STORE_X_BF16, STORE_RES_BF16 = 2, 4
@@ -356,7 +373,7 @@ def load():
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     lib = C.CDLL(LIB_PATH)
     for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES, KMEANS_PROTOTYPES, OPTIM_PROTOTYPES,
-                  SAMPLING_PROTOTYPES, GEN_SLOTS_PROTOTYPES, GEN_COND_PROTOTYPES):
+                  SAMPLING_PROTOTYPES, GEN_SLOTS_PROTOTYPES, GEN_COND_PROTOTYPES, GEN_RNG_PROTOTYPES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)           # AttributeError if the symbol is missing
             fn.restype = res
@@ -385,6 +402,9 @@ def load():
     if lib.vqvae_gen_cond_abi_version() != GEN_COND_ABI_VERSION:
         raise ImportError('libvqvae_hip.so at %s has latent-condition ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
                           % (LIB_PATH, lib.vqvae_gen_cond_abi_version(), GEN_COND_ABI_VERSION))
+    if lib.vqvae_gen_rng_abi_version() != GEN_RNG_ABI_VERSION:
+        raise ImportError('libvqvae_hip.so at %s has device-uniforms ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
+                          % (LIB_PATH, lib.vqvae_gen_rng_abi_version(), GEN_RNG_ABI_VERSION))
     _lib = lib
     return lib
 

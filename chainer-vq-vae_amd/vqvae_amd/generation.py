@@ -69,16 +69,149 @@ def _upload_controls(sampling):
     return s, arrays
 
 
+# ---- the uniforms drawn on the device (include/vqvae_gen_rng.h, csrc/gen_rng.hip) -------------------------------------
+_U32 = np.uint64(0xFFFFFFFF)
+_SH32 = np.uint64(32)
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 on arrays: ``counter`` (..., 4) and ``key`` (..., 2) 32-bit words (broadcast against each other)
+    -> the block's four words, uint32 (..., 4).  The definition is in include/vqvae_gen_rng.h."""
+    c = np.asarray(counter, np.uint64)
+    k = np.asarray(key, np.uint64)
+    c0, c1, c2, c3 = (c[..., i] & _U32 for i in range(4))
+    k0, k1 = k[..., 0] & _U32, k[..., 1] & _U32
+    m0, m1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+    w0, w1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+    for _ in range(10):
+        p0, p1 = m0 * c0, m1 * c2                      # 32 x 32 bits: the product fits 64
+        c0, c1, c2, c3 = (p1 >> _SH32) ^ c1 ^ k0, p1 & _U32, (p0 >> _SH32) ^ c3 ^ k1, p0 & _U32
+        k0, k1 = (k0 + w0) & _U32, (k1 + w1) & _U32
+    return np.stack(np.broadcast_arrays(c0, c1, c2, c3), axis=-1).astype(np.uint32)
+
+
+def words_to_double(a, b):
+    """Two 32-bit words -> the double in [0, 1) with 53 random bits (RandomState.random_sample's construction)."""
+    a = np.asarray(a, np.uint64) >> np.uint64(5)
+    b = np.asarray(b, np.uint64) >> np.uint64(6)
+    return (a.astype(np.float64) * 67108864.0 + b.astype(np.float64)) / 9007199254740992.0
+
+
+def _u64(values, name, who):
+    """``values`` as uint64, every one an integer in [0, 2**64)."""
+    # a list goes through Python integers: NumPy would make [0, 2**64 - 1] an array of doubles
+    a = values if isinstance(values, np.ndarray) else np.asarray(values, dtype=object)
+    if a.dtype.kind in 'iu':
+        if a.size and int(a.min()) < 0:
+            raise ValueError('%s: %s must be in [0, 2**64), got %r' % (who, name, values))
+        return a.astype(np.uint64)
+    if a.dtype.kind != 'O':
+        raise TypeError('%s: %s must be integers, got %r' % (who, name, values))
+    import operator
+    try:
+        flat = [operator.index(v) for v in a.reshape(-1)]
+    except TypeError:
+        raise TypeError('%s: %s must be integers, got %r' % (who, name, values))
+    if any(not 0 <= v < 2 ** 64 for v in flat):
+        raise ValueError('%s: %s must be in [0, 2**64), got %r' % (who, name, values))
+    return np.array(flat, np.uint64).reshape(a.shape)
+
+
+class DeviceUniforms(object):
+    """The uniforms of generation as a counter-based generator instead of an array (include/vqvae_gen_rng.h): pass it
+    where generate_sequence, generate_lockstep and sample_logits take ``uniforms``.  Uniform (sequence, step, j) is
+    Philox4x32-10 keyed by ``seed`` and counted by (step, j // 2, the sequence's stream id): it is computed by the kernel
+    that consumes it, nothing is drawn, stored or uploaded, and a sequence's draw is the same in any batch, group, slot
+    or list position.
+
+    seed: an integer in [0, 2**64).  stream_ids: (N,) integers in [0, 2**64), one per sequence, or None for
+    arange(N), resolved when the call knows N.  Two sequences with one id share a stream (a padded group's repeated
+    member already does).  ``host`` gives the same numbers as a NumPy array."""
+
+    def __init__(self, seed, stream_ids=None):
+        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)):
+            raise TypeError('DeviceUniforms: seed must be an integer, got %r' % (seed,))
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError('DeviceUniforms: seed must be in [0, 2**64), got %r' % (seed,))
+        self.seed = int(seed)
+        self.stream_ids = None
+        if stream_ids is not None:
+            ids = _u64(stream_ids, 'stream_ids', 'DeviceUniforms')
+            if ids.ndim != 1:
+                raise ValueError('DeviceUniforms: stream_ids must be (N,), one id per sequence, got shape %s' % (ids.shape,))
+            self.stream_ids = ids
+
+    def ids_for(self, n, who):
+        """The (n,) uint64 ids of a call with ``n`` sequences; a ValueError naming ``who`` when the count differs."""
+        if self.stream_ids is None:
+            return np.arange(n, dtype=np.uint64)
+        if len(self.stream_ids) != n:
+            raise ValueError('%s: the DeviceUniforms has %d stream_ids for %d sequences' % (who, len(self.stream_ids), n))
+        return self.stream_ids
+
+    def resolved(self, n, who):
+        """The same generator with its ids spelled out for ``n`` sequences."""
+        return DeviceUniforms(self.seed, self.ids_for(n, who))
+
+    def gather(self, idx):
+        """The generator of the sequences ``idx`` of a resolved one, repeats included (a group of run_lockstep)."""
+        return DeviceUniforms(self.seed, self.stream_ids[np.asarray(idx, np.int64)])
+
+    def host(self, steps, n_uniform=1, ids=None, t0=0):
+        """The numbers the device draws, as the float64 array (steps, N, n_uniform) the array form of the calls takes:
+        steps t0 .. t0 + steps - 1 of the streams ``ids`` (default: this object's stream_ids)."""
+        ids = self.stream_ids if ids is None else _u64(ids, 'ids', 'DeviceUniforms.host')
+        if ids is None:
+            raise ValueError('DeviceUniforms.host: no stream_ids were given, so N is not known: pass ids')
+        if ids.ndim != 1:
+            raise ValueError('DeviceUniforms.host: ids must be (N,), got shape %s' % (ids.shape,))
+        steps, n_uniform, t0 = int(steps), int(n_uniform), int(t0)
+        if steps < 0 or n_uniform < 1 or t0 < 0 or t0 + steps > _INT_MAX:
+            raise ValueError('DeviceUniforms.host: needs steps >= 0, n_uniform >= 1 and steps inside 0..2**31 - 1, got %d, %d, t0 %d'
+                             % (steps, n_uniform, t0))
+        pairs = (n_uniform + 1) // 2
+        t = np.arange(t0, t0 + steps, dtype=np.uint64)[:, None, None]
+        jb = np.arange(pairs, dtype=np.uint64)[None, None, :]
+        lo, hi = (ids & _U32)[None, :, None], (ids >> _SH32)[None, :, None]
+        counter = np.stack(np.broadcast_arrays(t, jb, lo, hi), axis=-1)
+        w = philox4x32_10(counter, np.array([self.seed & 0xFFFFFFFF, self.seed >> 32], np.uint64))
+        u = words_to_double(w[..., 0::2], w[..., 1::2])                  # (steps, N, pairs, 2): uniforms 2 jb, 2 jb + 1
+        return np.ascontiguousarray(u.reshape(steps, len(ids), 2 * pairs)[:, :, :n_uniform])
+
+    def upload(self, n, who):
+        """(GenRng, what it points to) for a call with ``n`` sequences: the ids go to the device as (n,) uint64, or stay
+        NULL (the identity) when none were given."""
+        ids = self.ids_for(n, who)
+        dev = None if self.stream_ids is None else backend.to_device(np.ascontiguousarray(ids, dtype=np.uint64))
+        r = _lib.GenRng()
+        r.seed, r.ids = self.seed, None if dev is None else dev.ptr
+        return r, dev
+
+
 def sample_logits(logits, uniforms, mode=_lib.GEN_SOFTMAX, temperature=None, top_k=None, top_p=None, log_scale_min=-40.0,
-                  return_probs=False):
+                  return_probs=False, step=0):
     """The sampler of a generation step on logits of the caller's own (vqvae_sample_logits): device float32 (n, out_dim),
     host doubles ``uniforms`` (n,) for the softmax output or (n, nr_mix) for the mixture of logistics, the controls as in
     sampling_controls.  Returns the device array (n,) of int32 classes or float32 values (and, with ``return_probs``, the
-    filtered probabilities (n, out_dim) the draw used; softmax output only)."""
+    filtered probabilities (n, out_dim) the draw used; softmax output only).
+    ``uniforms`` may be a DeviceUniforms: sequence q then draws the uniforms of its stream at step ``step``
+    (vqvae_sample_logits_rng); with an array ``step`` is not read."""
     backend.require_device(logits)
     n, out_dim = logits.shape
     softmax = mode == _lib.GEN_SOFTMAX
     sampling = sampling_controls(n, temperature, top_k, top_p, not softmax, 'sample_logits')
+    if isinstance(uniforms, DeviceUniforms):
+        if not 0 <= int(step) <= _INT_MAX:
+            raise ValueError('sample_logits: step must be in [0, 2**31), got %r' % (step,))
+        rng, keep_ids = uniforms.upload(n, 'sample_logits')
+        out = backend.zeros((n,), np.int32 if softmax else np.float32)
+        probs = DeviceArray((n, out_dim), np.float32) if return_probs else None
+        s, keep = (None, None) if sampling is None else _upload_controls(sampling)
+        _lib.call('vqvae_sample_logits_rng', logits.ptr, n, out_dim, mode, float(log_scale_min), C.byref(rng), int(step),
+                  1 if softmax else max(out_dim // 3, 1), None if s is None else C.byref(s), out.ptr,
+                  None if probs is None else probs.ptr, _S())
+        backend.synchronize()                               # the ids and the control arrays go out of scope here
+        return (out, probs) if return_probs else out
     u = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(n, -1)
     u_dev = backend.to_device(u.reshape(-1))
     out = backend.zeros((n,), np.int32 if softmax else np.float32)
@@ -287,6 +420,13 @@ def refuse_latent(condition, who):
                         'LatentCondition as it is' % who)
 
 
+def refuse_device_uniforms(uniforms, who):
+    if isinstance(uniforms, DeviceUniforms):
+        raise TypeError('%s runs persistent launches only, which read an array of uniforms: use generate_lockstep (any number '
+                        'of sequences) or generate_sequence (n <= 4), which take a DeviceUniforms, or pass its .host(...) array'
+                        % who)
+
+
 class GenerationState(object):
     """Device state behind WaveNet.initialize(n): zero queues (modules.py:58-67, 232-244) as
     per-block rings of ``dilation`` slots, the 2-sample embed queue, the step counter."""
@@ -375,7 +515,10 @@ class GenerationState(object):
         kernel has no filtered form, the run is a replayed hipGraph of per-step launches.
         ``condition`` may be a LatentCondition (per-step launches only): every step then starts with the launch that
         computes its condition column (vqvae_gen_cond_column), and ``col_seq`` (n,) int32 on the device, or None for the
-        identity, says which of the object's sequences sits in which column."""
+        identity, says which of the object's sequences sits in which column.
+        ``uniforms`` may be a DeviceUniforms with one stream id per column: n <= 4 fills the array on the device
+        (vqvae_gen_rng_fill) and runs as with an array, more columns draw in the finishing launch
+        (vqvae_wavenet_gen_step_rng)."""
         n = self.n
         latent = isinstance(condition, LatentCondition)
         if latent:
@@ -395,11 +538,22 @@ class GenerationState(object):
             raise ValueError('generate_sequence: n_steps must be in [0, %d]' % T)
         softmax = mode == _lib.GEN_SOFTMAX
         n_uniform = 1 if softmax else self.out_dim // 3
-        u = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(-1)
-        if u.size < steps * n * n_uniform:
-            raise ValueError('generate_sequence: need %d uniform doubles (steps, n, %d), got %d'
-                             % (steps * n * n_uniform, n_uniform, u.size))
-        u_dev = backend.to_device(u[:max(1, steps * n * n_uniform)])
+        rng = None
+        if isinstance(uniforms, DeviceUniforms):
+            # n <= 4 runs the matrix-vector kernels or the persistent kernel, which read an array: it is filled on the
+            # device (at most steps * 4 * n_uniform doubles).  More sequences draw inside the step's finishing launch.
+            rng, self._rng_ids = uniforms.upload(n, 'generate_sequence' if n <= _lib.GEN_MAX_N else 'generate_lockstep')
+            u_dev = None
+            if n <= _lib.GEN_MAX_N:
+                u_dev = DeviceArray((max(1, steps * n * n_uniform),), np.float64)
+                _lib.call('vqvae_gen_rng_fill', C.byref(rng), 0, steps, n, n_uniform, u_dev.ptr, _S())
+                rng = None
+        else:
+            u = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(-1)
+            if u.size < steps * n * n_uniform:
+                raise ValueError('generate_sequence: need %d uniform doubles (steps, n, %d), got %d'
+                                 % (steps * n * n_uniform, n_uniform, u.size))
+            u_dev = backend.to_device(u[:max(1, steps * n * n_uniform)])
         out = backend.zeros((n, T), np.int32 if softmax else np.float32)     # generate.py:103
         forced_dev = None
         if forced is not None:
@@ -415,20 +569,26 @@ class GenerationState(object):
             d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = self._column.ptr, self.cond_dim, 1, 0
         else:
             d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = condition.ptr, self.cond_dim * T, T, 1
-        d.uniforms, d.n_uniform = u_dev.ptr, n_uniform
+        d.uniforms, d.n_uniform = None if u_dev is None else u_dev.ptr, n_uniform
         d.forced_next = None if forced_dev is None else forced_dev.ptr
         d.out, d.out_bstride = out.ptr, T
         d.logits_out = None if logits_out is None else logits_out.ptr
         if int(self.step.get()[0]) != 0:
             raise RuntimeError('generate_sequence starts from fresh queues: call initialize(n) first')
         d.max_steps = steps
-        if sampling is None:
+        smp = None
+        if sampling is not None:
+            smp, self._controls = _upload_controls(sampling)
+            persistent = False
+        if rng is not None:
+            persistent = False
+
+            def network_step():
+                _lib.call('vqvae_wavenet_gen_step_rng', C.byref(d), None if smp is None else C.byref(smp), C.byref(rng), _S())
+        elif smp is None:
             def network_step():
                 _lib.call('vqvae_wavenet_gen_step', C.byref(d), _S())
         else:
-            smp, self._controls = _upload_controls(sampling)
-            persistent = False
-
             def network_step():
                 _lib.call('vqvae_wavenet_gen_step_sampled', C.byref(d), C.byref(smp), _S())
         step = network_step
@@ -486,6 +646,7 @@ def run_many(wavenet, condition, uniforms, mode, n_steps=None, group=_lib.GEN_MA
     condition (N, condition_dim, T) on the device, uniforms (T, N[, nr_mix]) on the host.
     Returns the host array (N, T) of sampled bins / values."""
     refuse_latent(condition, 'generate_batch')
+    refuse_device_uniforms(uniforms, 'generate_batch')
     if condition.ndim == 4:
         condition = condition.reshape(condition.shape[:3])
     N, Cc, T = condition.shape
@@ -613,6 +774,21 @@ def _latent_group_runner(wavenet, condition, mode, graph_steps, return_logits):
     return run_group
 
 
+def _lockstep_uniforms(uniforms, N, T, max_steps, n_uniform):
+    """The uniforms of a lockstep call, checked: the host array as (T', N, n_uniform'), or the DeviceUniforms with its
+    ids spelled out for the N sequences."""
+    if isinstance(uniforms, DeviceUniforms):
+        return uniforms.resolved(N, 'generate_lockstep')
+    u = np.asarray(uniforms, np.float64)
+    if u.ndim < 2 or u.shape[1] != N:
+        raise ValueError('generate_lockstep: uniforms must be (T, N[, %d]) = (%d, %d, ...), got %s'
+                         % (n_uniform, T, N, u.shape))
+    u = u.reshape(u.shape[0], N, -1)
+    if u.shape[0] < max_steps or u.shape[2] < n_uniform:
+        raise ValueError('generate_lockstep: need (%d, %d, %d) uniform doubles, got %s' % (max_steps, N, n_uniform, u.shape))
+    return u
+
+
 def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None, forced=None, return_logits=False,
                  graph_steps=8, group=_lib.GEN_MAX_LOCKSTEP, _run_group=None, sampling=None):
     """Many sequences at once (converting a validation set or a corpus): N sequences of any count as groups of
@@ -629,7 +805,10 @@ def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None,
     ``sampling``: None or the tuple of sampling_controls(N, ...); every group gets its members' values, gathered with the
     group's indices like the uniforms (repeats of the last member included), and the promise above holds with them.
     ``condition`` may be a LatentCondition: T is its longest sequence, ``lengths`` defaults to its own, and the values are
-    those of the call with ``condition.dense()``, bit for bit, without that tensor."""
+    those of the call with ``condition.dense()``, bit for bit, without that tensor.
+    ``uniforms`` may be a DeviceUniforms: a group then gets the generator with its members' stream ids (gathered with the
+    group's indices, repeats included) in place of an array, and the values are those of the call with
+    ``uniforms.host(steps, n_uniform)``."""
     latent = isinstance(condition, LatentCondition)
     if latent and lengths is None:
         lengths = condition.lengths
@@ -640,14 +819,8 @@ def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None,
     softmax = mode == _lib.GEN_SOFTMAX
     out_dim = wavenet.proj2.W.shape[0]
     n_uniform = 1 if softmax else out_dim // 3
-    u = np.asarray(uniforms, np.float64)
     max_steps = int(steps.max()) if N else 0
-    if u.ndim < 2 or u.shape[1] != N:
-        raise ValueError('generate_lockstep: uniforms must be (T, N[, %d]) = (%d, %d, ...), got %s'
-                         % (n_uniform, T, N, u.shape))
-    u = u.reshape(u.shape[0], N, -1)
-    if u.shape[0] < max_steps or u.shape[2] < n_uniform:
-        raise ValueError('generate_lockstep: need (%d, %d, %d) uniform doubles, got %s' % (max_steps, N, n_uniform, u.shape))
+    u = _lockstep_uniforms(uniforms, N, T, max_steps, n_uniform)
     if forced is not None:
         forced = np.asarray(forced).reshape(-1, N)
         if forced.shape[0] < max_steps:
@@ -657,7 +830,8 @@ def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None,
     out = np.zeros((N, T), np.int32 if softmax else np.float32)                  # generate.py:103
     logits = np.zeros((max_steps, N, out_dim), np.float32) if return_logits else None
     for idx, gsteps in groups:
-        ug = np.ascontiguousarray(u[:max(gsteps, 1), idx, :n_uniform])
+        # a DeviceUniforms has no (steps, n) array on either side: the group gets its members' stream ids
+        ug = u.gather(idx) if isinstance(u, DeviceUniforms) else np.ascontiguousarray(u[:max(gsteps, 1), idx, :n_uniform])
         fg = None if forced is None else np.ascontiguousarray(forced[:gsteps, idx])
         if sampling is None:
             o, lg = run_group(idx, ug, fg, gsteps)
@@ -724,11 +898,13 @@ class LockstepRefill(object):
     Device memory besides the decoder state of S slots: the condition as the caller holds it (the (N, condition_dim, T)
     floats, 2 560 bytes per sample for the default model, or a LatentCondition: 4 Cl sum(tl) + 4 G N bytes, 32 bytes per
     sample, plus the (N, condition_dim) column that every tick's first launch, vqvae_gen_cond_column, fills for the live
-    slots), the dense uniforms max_steps x N x n_uniform doubles and forced values max_steps x N, ``out`` N x T, with
+    slots), the uniforms (an array: max_steps x N x n_uniform doubles, dense; a DeviceUniforms: the N stream ids, 8 N bytes,
+    the numbers being computed in the finishing launch), the dense forced values max_steps x N, ``out`` N x T, with
     ``return_logits`` max_steps x N x out_dim floats (a test and inspection facility: 25 MB per 100 steps of 256
     sequences and classes), and 3 N + 2 S + 2 integers of table.  For a corpus of N = 300 utterances of up to 10 s at
-    16 kHz the dense condition would be 123 GB and the latent one is at most 1.5 GB; the uniforms are 384 MB; their rows
-    are dense because ragged storage would make a sequence's addresses depend on its neighbours' lengths."""
+    16 kHz the dense condition would be 123 GB and the latent one is at most 1.5 GB; an array of uniforms is 384 MB (3.8 GB
+    for a mixture of 10 logistics), its rows dense because ragged storage would make a sequence's addresses depend on its
+    neighbours' lengths; a DeviceUniforms is 2 400 bytes.  ``out`` and the forced values stay dense."""
 
     def __init__(self, wavenet, condition, steps, u, forced, mode, group, return_logits=False, sampling=None):
         N, Cc, T = condition.shape
@@ -739,10 +915,14 @@ class LockstepRefill(object):
         max_steps = int(steps.max())
         softmax = mode == _lib.GEN_SOFTMAX
         st = self.state = LockstepState(wavenet, S)
-        n_uniform = u.shape[2]
-        self._keep = [condition,
-                      backend.to_device(steps), backend.to_device(queue),
-                      backend.to_device(np.ascontiguousarray(u[:max_steps]).reshape(-1))]
+        self._rng = None
+        if isinstance(u, DeviceUniforms):                  # the (N,) stream ids, uploaded once; no array of uniforms
+            n_uniform = 1 if softmax else st.out_dim // 3
+            self._rng, u_dev = u.upload(N, 'generate_lockstep')
+        else:
+            n_uniform = u.shape[2]
+            u_dev = backend.to_device(np.ascontiguousarray(u[:max_steps]).reshape(-1))
+        self._keep = [condition, backend.to_device(steps), backend.to_device(queue), u_dev]
         self.out = backend.zeros((N, T), np.int32 if softmax else np.float32)
         self.logits_out = backend.zeros((max_steps, N, st.out_dim), np.float32) if return_logits else None
         self.slot_seq = backend.zeros((S,), np.int32)
@@ -760,7 +940,7 @@ class LockstepRefill(object):
             d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = self.column.ptr, Cc, 1, 0
         else:
             d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = condition.ptr, Cc * T, T, 1
-        d.uniforms, d.n_uniform = self._keep[3].ptr, n_uniform
+        d.uniforms, d.n_uniform = None if self._rng is not None else u_dev.ptr, n_uniform
         d.forced_next = None
         if forced is not None:
             self._keep.append(backend.to_device(np.ascontiguousarray(
@@ -783,8 +963,11 @@ class LockstepRefill(object):
     def tick(self):
         if self._lat is not None:         # reads the table vqvae_gen_slots_init or the previous tick's scheduler left behind
             _lib.call('vqvae_gen_cond_column', C.byref(self._lat), C.byref(self.desc), C.byref(self.table), _S())
-        _lib.call('vqvae_wavenet_gen_step_slots', C.byref(self.desc), C.byref(self.table),
-                  None if self._smp is None else C.byref(self._smp), _S())
+        smp = None if self._smp is None else C.byref(self._smp)
+        if self._rng is not None:
+            _lib.call('vqvae_wavenet_gen_step_slots_rng', C.byref(self.desc), C.byref(self.table), smp, C.byref(self._rng), _S())
+        else:
+            _lib.call('vqvae_wavenet_gen_step_slots', C.byref(self.desc), C.byref(self.table), smp, _S())
 
     def replay(self):
         """One more launch of the captured graph (``graph_steps`` ticks); past the end a device no-op."""
@@ -833,7 +1016,8 @@ def run_lockstep_refill(wavenet, condition, uniforms, mode, n_steps=None, length
     hipGraph with no host read-back until the end (csrc/generate_slots.hip; memory: see LockstepRefill).  Arguments
     and return value as run_lockstep; every sequence gets the values run_lockstep gives it, bit for bit.
     ``_run(steps, u, forced, sampling)`` -> (out (N, T), logits (max steps, N, out_dim) or None), both in the caller's
-    order, stands in for the device in host tests."""
+    order, stands in for the device in host tests; ``u`` is the (max steps, N, n_uniform) array or, when ``uniforms`` is a
+    DeviceUniforms, that object with its (N,) stream ids spelled out."""
     if isinstance(condition, LatentCondition) and lengths is None:
         lengths = condition.lengths
     if condition.ndim == 4:
@@ -843,14 +1027,8 @@ def run_lockstep_refill(wavenet, condition, uniforms, mode, n_steps=None, length
     softmax = mode == _lib.GEN_SOFTMAX
     out_dim = wavenet.proj2.W.shape[0]
     n_uniform = 1 if softmax else out_dim // 3
-    u = np.asarray(uniforms, np.float64)
     max_steps = int(steps.max()) if N else 0
-    if u.ndim < 2 or u.shape[1] != N:
-        raise ValueError('generate_lockstep: uniforms must be (T, N[, %d]) = (%d, %d, ...), got %s'
-                         % (n_uniform, T, N, u.shape))
-    u = u.reshape(u.shape[0], N, -1)
-    if u.shape[0] < max_steps or u.shape[2] < n_uniform:
-        raise ValueError('generate_lockstep: need (%d, %d, %d) uniform doubles, got %s' % (max_steps, N, n_uniform, u.shape))
+    u = _lockstep_uniforms(uniforms, N, T, max_steps, n_uniform)
     if forced is not None:
         forced = np.asarray(forced).reshape(-1, N)
         if forced.shape[0] < max_steps:
@@ -859,7 +1037,7 @@ def run_lockstep_refill(wavenet, condition, uniforms, mode, n_steps=None, length
     logits = np.zeros((max_steps, N, out_dim), np.float32) if return_logits else None
     if max_steps:
         run = _run or _device_refill_runner(wavenet, condition, mode, graph_steps, group, return_logits)
-        o, lg = run(steps, u[:max_steps, :, :n_uniform], forced, sampling)
+        o, lg = run(steps, u if isinstance(u, DeviceUniforms) else u[:max_steps, :, :n_uniform], forced, sampling)
         for i in range(N):                        # the device wrote nothing past a sequence's own steps; a stub may have
             out[i, :steps[i]] = o[i, :steps[i]]
             if return_logits:

@@ -32,6 +32,9 @@ def synthesize(encoder, vq, decoder, condition_embed, x_enc, global_condition, r
     rng: numpy.random.RandomState (default: a fresh RandomState(), the stand-in for NumPy's global
         RNG that generate.py:117 / 136 draws from).  The uniforms are drawn up front, one per step
         (softmax output) or nr_mix per step (mixture of logistics), in the reference's order.
+        A vqvae_amd.DeviceUniforms(seed, stream_ids) is passed through to the decoder instead: nothing is drawn on the
+        host, and waveform i's wave depends only on (seed, stream_ids[i]), its own input and the model, not on n or on
+        its position.
     lockstep: any number of waveforms; the decoder advances them together through WaveNet.generate_lockstep
         (groups of <= 128) instead of generate_sequence (n <= 4).
     temperature / top_k / top_p: sampling controls, handed to generate_sequence / generate_lockstep as they are (None, a
@@ -43,6 +46,7 @@ def synthesize(encoder, vq, decoder, condition_embed, x_enc, global_condition, r
         (mu-law expanded for the softmax output), output = the raw sampled bins / values."""
     if latent_condition and not lockstep:
         raise ValueError('synthesize: latent_condition needs lockstep=True (generate_sequence reads the full-rate condition)')
+    from .generation import DeviceUniforms
     rng = np.random.RandomState() if rng is None else rng
     xd = x_enc if backend.is_device(x_enc) else backend.to_device(np.asarray(x_enc, np.float32))
     gd = global_condition if backend.is_device(global_condition) else \
@@ -56,7 +60,9 @@ def synthesize(encoder, vq, decoder, condition_embed, x_enc, global_condition, r
     T = cond.shape[2]
     steps = T - 1 if n_steps is None else n_steps                   # generate.py:105
     nr_mix = decoder.proj2.W.shape[0] // 3
-    if use_logistic:
+    if isinstance(rng, DeviceUniforms):
+        u = rng                                                      # drawn on the device, where it is consumed
+    elif use_logistic:
         u = rng.uniform(0, 1, (max(steps, 1), n, nr_mix))            # generate.py:117
     else:
         u = rng.random_sample((max(steps, 1), n))                    # inside numpy.random.choice, generate.py:136
@@ -83,7 +89,11 @@ def synthesize_many(encoder, vq, decoder, condition_embed, waves, global_conditi
     through WaveNet.generate_lockstep; ``refill`` (default True) keeps its ``group`` columns busy by handing a finished
     column the next waiting utterance.
     rng: as in synthesize; the uniforms are drawn as it draws them for shape (Tmax - 1, N[, nr_mix]), so utterance i
-        uses column i.
+        uses column i, and its wave depends on how many utterances the list has and on the longest one.
+        A vqvae_amd.DeviceUniforms(seed, stream_ids) is passed through to the decoder instead: nothing is drawn on the
+        host (for 300 utterances of up to 10 s that array is 384 MB, 3.8 GB with a mixture of 10 logistics, and the same
+        again on the device), and utterance i's wave depends only on (seed, stream_ids[i]), its own input and the
+        model, not on the list: the same bits alone, in any list, at any position, with any ``group`` and ``refill``.
     latent_condition: keep the condition at the latent rate (generation.LatentCondition): no utterance's condition is
         expanded to the sample rate, the (N, condition_dim, Tmax) array and its N * condition_dim row copies do not
         exist, and the decoder computes each step's condition column on the device.  Same waves, bit for bit.
@@ -93,6 +103,7 @@ def synthesize_many(encoder, vq, decoder, condition_embed, waves, global_conditi
         contiguous column).  The default is False because the call without it is the call as it was.
     Returns the list of N host waves, utterance i of its own length T_i, as synthesize returns them (mu-law expanded
     for the softmax output); with ``return_output`` the list of (wave, output) pairs."""
+    from .generation import DeviceUniforms
     rng = np.random.RandomState() if rng is None else rng
     N = len(waves)
     speakers = np.asarray(global_condition.get() if backend.is_device(global_condition) else global_condition,
@@ -120,7 +131,9 @@ def synthesize_many(encoder, vq, decoder, condition_embed, waves, global_conditi
                            for i, (c, L) in enumerate(zip(conds, lengths)) for ch in range(Cc)])
     steps = Tmax - 1 if n_steps is None else n_steps
     nr_mix = decoder.proj2.W.shape[0] // 3
-    if use_logistic:
+    if isinstance(rng, DeviceUniforms):
+        u = rng                                                      # no (Tmax - 1, N[, nr_mix]) array on either side
+    elif use_logistic:
         u = rng.uniform(0, 1, (max(steps, 1), N, nr_mix))            # generate.py:117
     else:
         u = rng.random_sample((max(steps, 1), N))                    # inside numpy.random.choice, generate.py:136

@@ -963,7 +963,13 @@ class WaveNet(Chain):
         against 95 us per sample).
 
         The condition is the dense tensor: a generation.LatentCondition is a TypeError here (the persistent launch runs
-        thousands of steps and cannot take a per-step column); generate_lockstep takes one, ``.dense()`` expands it."""
+        thousands of steps and cannot take a per-step column); generate_lockstep takes one, ``.dense()`` expands it.
+
+        ``uniforms`` may be a DeviceUniforms(seed, stream_ids) instead of the array: the numbers are then Philox4x32-10
+        draws made on the device (include/vqvae_gen_rng.h), sequence i the stream stream_ids[i] (default i), and the
+        host draws and uploads nothing.  The kernels of this call (n <= 4) keep reading an array, so it is filled on the
+        device first, (steps, n[, nr_mix]) doubles; every other argument means what it means with an array, and the
+        result is that of the call with ``uniforms.host(steps, n_uniform)``, bit for bit."""
         from .core import Variable
         from .generation import refuse_latent, sampling_controls
         cd = condition.data if isinstance(condition, Variable) else condition
@@ -983,10 +989,12 @@ class WaveNet(Chain):
         gets exactly the samples generate_sequence would give it alone with its column of uniforms.
         It exists only as persistent launches, which have no filtered sampler: any of ``temperature`` / ``top_k`` /
         ``top_p`` is a ValueError; generate_lockstep takes them.  So is a generation.LatentCondition a TypeError: the
-        persistent launches read the dense tensor (``.dense()``); generate_lockstep takes the latent form."""
+        persistent launches read the dense tensor (``.dense()``); generate_lockstep takes the latent form.  And so is a
+        DeviceUniforms: the persistent launches read an array (``.host(...)``); generate_lockstep draws on the device."""
         from .core import Variable
-        from .generation import refuse_latent, run_many
+        from .generation import refuse_device_uniforms, refuse_latent, run_many
         refuse_latent(condition.data if isinstance(condition, Variable) else condition, 'generate_batch')
+        refuse_device_uniforms(uniforms, 'generate_batch')
         if temperature is not None or top_k is not None or top_p is not None:
             raise ValueError('generate_batch runs persistent launches only, which have no sampling controls: '
                              'use generate_lockstep (any number of sequences) or generate_sequence (n <= 4)')
@@ -1016,7 +1024,13 @@ class WaveNet(Chain):
         sample).  Every step, with and without ``refill``, then starts with one small launch that computes the
         condition column of each live sequence (csrc/generate_cond.hip); T is the longest sequence, ``lengths`` defaults
         to the object's own, and the return value is that of the call with ``condition.dense()``, bit for bit.  The way to
-        convert a corpus whose dense condition does not fit the device."""
+        convert a corpus whose dense condition does not fit the device.
+        ``uniforms`` may be a DeviceUniforms(seed, stream_ids) instead of the (T, N[, nr_mix]) array: every finishing
+        launch then computes its own uniforms (Philox4x32-10 counted by the sequence's step and keyed by the seed;
+        include/vqvae_gen_rng.h), so no array of N x T doubles exists on the host or on the device, only the (N,)
+        stream ids (default arange(N)).  Sequence i's values then depend on (seed, stream_ids[i]), its own condition and
+        the model alone: not on N, on ``group``, on ``refill``, on its position or on the other lengths.  The result is
+        that of the call with ``uniforms.host(steps, n_uniform)``, bit for bit.  ``out`` (N, T) and ``forced`` stay dense."""
         from .core import Variable
         from .generation import LatentCondition, run_lockstep, run_lockstep_refill, sampling_controls
         cd = condition.data if isinstance(condition, Variable) else condition

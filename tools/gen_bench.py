@@ -9,6 +9,8 @@ usage: python tools/gen_bench.py [--workload c2|c5|ref] [--n 1] [--steps 16000] 
        ... --lockstep N / --lengths-n N --latent-cond    the condition kept at the latent rate (generation.LatentCondition: random
            latents of ceil(T / 64) frames instead of the dense (N, Cc, T) array, which is never made); prints the bytes of
            both forms.  With --lengths-n, --refill runs the refilled road only
+       ... --device-uniforms    the uniforms drawn inside the finishing kernels (vqvae_amd.DeviceUniforms) instead of a host
+           array; without it the array's draw and upload are timed and printed
        ... [--temperature 0.8] [--top-k 32] [--top-p 0.95]   sampling controls (every sequence the same); with any of them
        generate_sequence runs the per-step kernels, and --batch refuses"""
 import argparse
@@ -58,6 +60,8 @@ def main():
     ap.add_argument('--temperature', type=float, default=None, help='sampling temperature (0 = greedy); default: none')
     ap.add_argument('--top-k', type=int, default=None, help='keep the k most likely classes; default: none')
     ap.add_argument('--top-p', type=float, default=None, help='nucleus mass in (0, 1]; default: none')
+    ap.add_argument('--device-uniforms', action='store_true', help='the uniforms as a DeviceUniforms(0) drawn inside the kernels '
+                    '(include/vqvae_gen_rng.h) instead of a host array; without it the array\'s draw and upload are timed and printed')
     a = ap.parse_args()
     ctl = dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
     ctl_txt = ''.join(' %s=%g' % (k, v) for k, v in ctl.items() if v is not None) or ' no controls'
@@ -81,6 +85,24 @@ def main():
     dec.to_gpu()
     dec(Variable(x), Variable(c))
     T = a.steps + 1
+
+    def uniforms(rs, shape):
+        """The (T, N, n_uniform) host draw, with the host time and bytes it and its upload cost, or a DeviceUniforms."""
+        if a.device_uniforms:
+            from vqvae_amd import DeviceUniforms
+            print('uniforms: DeviceUniforms(0), %d bytes of stream ids; the host array would be %d bytes' % (8 * shape[1], 8 * int(np.prod(shape))))
+            return DeviceUniforms(0)
+        t0 = time.time()
+        u = rs.uniform(0.01, 0.99, shape)
+        t1 = time.time()
+        d = backend.to_device(u.reshape(-1))
+        backend.synchronize()
+        t2 = time.time()
+        del d
+        print('uniforms: host array %s, %d bytes: draw %.3f s, upload %.3f s (the upload happens again inside the timed call)'
+              % (shape, u.nbytes, t1 - t0, t2 - t1))
+        return u
+
     if a.lengths_n:
         from vqvae_amd.generation import plan_lockstep, plan_refill, refill_slots
         group = a.group if a.group > 4 else 128
@@ -97,7 +119,7 @@ def main():
             cond = backend.zeros((N, Cc, T), np.float32)
             for i in range(N):                               # row by row: the whole array may not fit the host twice
                 cond.flat_view(i * Cc * T, Cc * T).set(rs.standard_normal(Cc * T).astype(np.float32))
-        u = rs.uniform(0.01, 0.99, (T, N, 10 if mol else 1))
+        u = uniforms(rs, (T, N, 10 if mol else 1))
         short = np.minimum(lengths, 65)
         roads = (('refill', True),) if a.refill else (('sorted', False), ('refill', True))
         for _, refill in roads:                              # warm-up of the roads
@@ -130,10 +152,12 @@ def main():
             ctl_txt += ' latent condition (%d bytes, dense %d)' % (cond.nbytes, 4 * a.lockstep * Cc * (a.steps + 1))
         else:
             cond = backend.to_device(rs.standard_normal((a.lockstep, Cc, T)).astype(np.float32))
-        u = rs.uniform(0.01, 0.99, (T, a.lockstep, 10 if mol else 1))
+        u = uniforms(rs, (T, a.lockstep, 10 if mol else 1))
         if a.refill:
             ctl = dict(ctl, refill=True)
             ctl_txt += ' refill'
+        if a.device_uniforms:
+            ctl_txt += ' device uniforms'
         dec.generate_lockstep(cond, u, n_steps=64, group=group, graph_steps=a.graph_steps, **ctl)      # warm-up
         t0 = time.time()
         o = dec.generate_lockstep(cond, u, group=group, graph_steps=a.graph_steps, **ctl)
@@ -161,7 +185,7 @@ def main():
         return
     rs = np.random.RandomState(0)
     cond = backend.to_device(rs.standard_normal((a.n, Cc, T)).astype(np.float32))
-    u = rs.uniform(0.01, 0.99, (T, a.n, 10 if mol else 1))
+    u = uniforms(rs, (T, a.n, 10 if mol else 1))
     pers = not a.per_step_kernels and all(v is None for v in ctl.values())     # controls leave the persistent kernel
     dec.generate_sequence(cond, u, n_steps=64, graph_steps=a.graph_steps, persistent=pers, **ctl)      # warm-up
     t0 = time.time()
