@@ -284,7 +284,9 @@ __device__ __forceinline__ void vq_split3(float x0, float x1, unsigned& h, unsig
 //   so a dot product is within (1.6 d + 7) u S, dist' = |w|^2 - 2 <w,z> within E_ours = (4.2 d + 16) u S (|w|^2 itself: (d + 1) u
 //   |w|^2, the final fma: u S), and the band 2 (E_ours + E_ref) = (16.4 d + 44) u S -> 17 (d + 4) u S (the six-product sweep: 24).
 // fp16 range: products reach 2^30, row sums 2^37 -- far inside fp32; an all-zero row or codebook keeps a finite scale
-// (exponents clamped to >= -60, so that 2^-(kw + kz) stays a normal fp32).
+// (exponents clamped to >= -60: kz, kw <= 74, so the way back 2^(1 - kz - kw) >= 2^-147 is a power of two that fp32 still holds
+// exactly -- as a SUBNORMAL below 2^-126, i.e. for tensors under ~2^-49; the library is built with fp32 denormals on, and
+// tests/test_gpu_vq_domain.py runs both tensors at 2^-55 and an all-zero codebook / latent tensor through this sweep).
 using f16x8v = __attribute__((ext_vector_type(8))) _Float16;
 using f16x2v = __attribute__((ext_vector_type(2))) _Float16;
 __device__ __forceinline__ int vq_expo(float m) {                  // exponent e with m in [2^e, 2^(e+1)), clamped to >= -60
@@ -986,9 +988,53 @@ static int vq_cols_per_block(int dpad) {
   return 0;
 }
 
+// Every shape and matmul-dtype decision of vqvae_vq_nearest_fwd and vqvae_vq_grad_w, in one place: the entry points launch
+// what this says, vqvae_vq_paths reports it.  paths: the VQVAE_VQ_PATH_* bits, -1 where mode 0 refuses d.
+struct VqSelect {
+  int paths, dpad, nw;     // nw: wavefronts of the LDS-staged sweep (0: d too wide)
+  bool x2, pipe16, reg;    // mode 0, d = 64 / 128: fp16 pieces (dtype 3) | either 16-bit sweep (dtype >= 2) | the register sweep
+  bool cand, recheck8, gather_tile, grad_sort;
+};
+static VqSelect vq_select(int B, int d, int T, int k, int mode, int dtype) {
+  VqSelect s = {};
+  const long N = (long)B * T;
+  s.dpad = (d + 1) / 2 * 2;
+  s.nw = vq_cols_per_block(s.dpad);
+  if (mode == 0) {
+    const bool d64 = d == 64 || d == 128;
+    s.x2 = d64 && dtype == 3;           // three fp16 products (dtype 2: six bf16 products)
+    s.pipe16 = d64 && dtype >= 2;
+    s.reg = d64 && !s.pipe16;
+    // the candidate pass pays when re-checking a row against all k codes costs more than sweeping it again
+    s.cand = s.pipe16 && k >= 1024 && N >= 1024;      // (round 5: N = 1920 at k = 8192 1.49 -> 1.32 ms with it; from N = 4096 until then)
+    s.recheck8 = N > 8192;
+  }
+  // (the training shape's 1 920 rows: one launch of the plain kernel is all latency; d <= 254: the tile's 64 (d + 1) floats stay
+  //  inside the 64 KB of dynamic LDS a launch gets without lds_opt_in -- wider codes take the plain kernel)
+  s.gather_tile = N >= 16384 && d <= 254 && B <= 65535;
+  s.grad_sort = !(N <= 8192 && N * k <= (1L << 26));   // small problem: scan form
+  if (mode == 0 && s.nw == 0) { s.paths = -1; return s; }
+  int p = 0;
+  if (mode == 0) {
+    p |= s.x2 ? VQVAE_VQ_PATH_SWEEP_X2 : s.pipe16 ? VQVAE_VQ_PATH_SWEEP_X3 : s.reg ? VQVAE_VQ_PATH_SWEEP_REG
+         : s.nw == 4 ? VQVAE_VQ_PATH_SWEEP_LDS4 : s.nw == 2 ? VQVAE_VQ_PATH_SWEEP_LDS2 : VQVAE_VQ_PATH_SWEEP_LDS1;
+    if (s.cand) p |= VQVAE_VQ_PATH_CANDIDATES;
+    if (s.recheck8) p |= VQVAE_VQ_PATH_RECHECK_R8;
+  }
+  if (s.gather_tile) p |= VQVAE_VQ_PATH_GATHER_TILE;
+  if (s.grad_sort) p |= VQVAE_VQ_PATH_GRAD_SORT;
+  s.paths = p;
+  return s;
+}
+
 }  // namespace vq
 
 using namespace vq;
+
+extern "C" int vqvae_vq_paths(int B, int d, int T, int k, int mode) {
+  if (B <= 0 || d <= 0 || T <= 0 || k <= 0) return -1;
+  return vq_select(B, d, T, k, mode != 0, vqvae_get_matmul_dtype()).paths;
+}
 
 // Forward workspace: wn[k] | 256 bytes of words (wmax_bits[2] at +0, nflag at +64, noverflow at +68) | flagged[N] |
 // split codebook (matmul modes 2 and 3) | candidate re-check: (min, band) and count per flagged row, VQ_CAP candidates
@@ -1101,31 +1147,29 @@ extern "C" int vqvae_vq_nearest_fwd(const float* z, const float* W, int B, int d
   a.ccount = (int32_t*)(wp + p.ccount);
   a.cand = (int32_t*)(wp + p.cand);
   a.overflow = (int32_t*)(wp + p.overflow);
-  bool cand_path = false;
+  const VqSelect sel = vq_select(B, d, T, k, mode != 0, vqvae_get_matmul_dtype());
+  const bool cand_path = sel.cand;
   ProfScope ps(VQVAE_PROF_VQ_NEAREST, st);
   if (mode == 0) {
-    const int dpad = (d + 1) / 2 * 2;
-    const int nw = vq_cols_per_block(dpad);
+    const int dpad = sel.dpad, nw = sel.nw;
     VQ_REQUIRE(nw > 0, "vq_nearest_fwd: d=%d too large for the LDS-staged MFMA path (max ~1000)", d);
     VQ_CHECK_HIP(hipMemsetAsync(a.wmax_bits, 0, 256, st));
     // mode 3: three fp16 products (mode 2: six bf16 products)
-    const bool x2 = (d == 64 || d == 128) && vqvae_get_matmul_dtype() == 3;
+    const bool x2 = sel.x2;
     if (x2) hipLaunchKernelGGL(vq_wnorm_elt_lds_kernel, dim3(cdiv(k, 64)), dim3(64), (size_t)64 * (d + 1) * 4, st, W, k, d, a.wn, a.wmax_bits);      // (x2: d is 64 or 128)
     else hipLaunchKernelGGL(vq_wnorm_kernel, dim3(cdiv(k, 256)), dim3(256), 0, st, W, k, d, a.wn, a.wmax_bits);
     VQ_LAUNCH_CHECK();
     int err = 0;
-    if ((d == 64 || d == 128) && vqvae_get_matmul_dtype() >= 2) {      // modes 2 and 3: the sweep on the 16-bit matrix pipe
+    if (sel.pipe16) {      // modes 2 and 3: the sweep on the 16-bit matrix pipe
       int nb = (int)(((long)k * d / 2 + 255) / 256);
       if (nb > 2048) nb = 2048;
       if (x2) hipLaunchKernelGGL(vq_wsplit2_kernel, dim3(nb), dim3(256), 0, st, W, k, d, a.wmax_bits, a.wsplit);
       else hipLaunchKernelGGL(vq_wsplit_kernel, dim3(nb), dim3(256), 0, st, W, k, d, a.wsplit);
       VQ_LAUNCH_CHECK();
-      // the candidate pass pays when re-checking a row against all k codes costs more than sweeping it again
-      cand_path = k >= 1024 && N >= 1024;      // (round 5: N = 1920 at k = 8192 1.49 -> 1.32 ms with it; from N = 4096 until then)
       if (cand_path) VQ_CHECK_HIP(hipMemsetAsync(a.ccount, 0, (size_t)N * 4, st));
       if (d == 64) err = x2 ? launch_x3<64, 2>(a, cand_path) : launch_x3<64, 3>(a, cand_path);
       else err = x2 ? launch_x3<128, 2>(a, cand_path) : launch_x3<128, 3>(a, cand_path);
-    } else if (d == 64 || d == 128) {
+    } else if (sel.reg) {
       err = d == 64 ? launch_reg<32>(a) : launch_reg<64>(a);
     } else {
       err = nw == 4 ? launch_lds<4>(a, dpad) : nw == 2 ? launch_lds<2>(a, dpad) : launch_lds<1>(a, dpad);
@@ -1141,7 +1185,7 @@ extern "C" int vqvae_vq_nearest_fwd(const float* z, const float* W, int B, int d
       VQ_LAUNCH_CHECK();
       list = a.overflow; nlist = a.noverflow;
     }
-    if (N > 8192) {
+    if (sel.recheck8) {
       if (int e2 = launch_recheck<8>(a, list, nlist)) return e2;
     } else {
       // the training shapes (a few thousand rows, a few dozen of them queued): the launch is one workgroup's chain of 64 d
@@ -1162,9 +1206,7 @@ extern "C" int vqvae_vq_nearest_fwd(const float* z, const float* W, int B, int d
     const long total = (long)B * d * T;
     int nb = (int)((total + 255) / 256);
     if (nb > 4096) nb = 4096;
-    // (the training shape's 1 920 rows: one launch of the plain kernel is all latency; d <= 254: the tile's 64 (d + 1) floats stay
-    //  inside the 64 KB of dynamic LDS a launch gets without lds_opt_in -- wider codes take the plain kernel)
-    if ((long)B * T >= 16384 && d <= 254 && B <= 65535)
+    if (sel.gather_tile)
       hipLaunchKernelGGL(vq_gather_tile_kernel, dim3((T + 63) / 64, B), dim3(256), (size_t)64 * (d + 1) * 4, st, W, idx, B, d, T, e);
     else
       hipLaunchKernelGGL(vq_gather_kernel, dim3(nb), dim3(256), 0, st, W, idx, B, d, T, e);
@@ -1178,7 +1220,7 @@ extern "C" int vqvae_vq_grad_w(const int32_t* idx, const float* gy, int B, int d
                                vqvae_stream_t s) {
   VQ_REQUIRE(idx && gy && gW && ws, "vq_grad_w: null pointer");
   hipStream_t st = (hipStream_t)s;
-  if ((long)B * T <= 8192 && (long)B * T * k <= (1L << 26)) {   // small problem: scan form
+  if (!vq_select(B, d, T, k, 1, 0).grad_sort) {   // small problem: scan form
     hipLaunchKernelGGL(vq_gradw_scan_kernel, dim3(k), dim3(256), (size_t)B * T * 4, st, idx, gy, B, d, T, k, gW, accumulate);
     VQ_LAUNCH_CHECK();
     return 0;

@@ -173,6 +173,7 @@ PROTOTYPES = {
     'vqvae_vq_nearest_fwd': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P,
                                      c_size_t, P]),
     'vqvae_vq_grad_w': (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, P, c_size_t, P]),
+    'vqvae_vq_paths': (c_int, [c_int, c_int, c_int, c_int, c_int]),
     'vqvae_upsample_linear_fwd': (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_long, P]),
     'vqvae_upsample_linear_bwd': (c_int, [P, c_long, c_int, c_int, c_int, c_int, P, P, P, P, P, P,
                                           P, c_long, P]),

@@ -489,6 +489,22 @@ int vqvae_vq_nearest_fwd(const float* z, const float* W, int B, int d, int T, in
 int vqvae_vq_grad_w(const int32_t* idx, const float* gy, int B, int d, int T, int k,
                     float* gW, int accumulate, void* ws, size_t ws_bytes,
                     vqvae_stream_t s);
+/* Which kernels vqvae_vq_nearest_fwd (mode 0/1) and vqvae_vq_grad_w launch for these
+   dims under the current matmul dtype: an OR of VQVAE_VQ_PATH_* bits; -1 where the
+   forward refuses the shape (mode 0, d too wide for the LDS-staged sweep). No device access.
+   Mode 0 sets exactly one sweep bit; mode 1 (every code exactly) sets none of the sweep,
+   candidate and re-check bits.  The gather bit is the form e = W[idx] takes when e is given. */
+#define VQVAE_VQ_PATH_SWEEP_X2 0x001    /* vq_mfma_x3_kernel<d, NP = 2>: three fp16 products (d 64 / 128, matmul dtype 3) */
+#define VQVAE_VQ_PATH_SWEEP_X3 0x002    /* vq_mfma_x3_kernel<d, NP = 3>: six bf16 products (d 64 / 128, matmul dtype 2) */
+#define VQVAE_VQ_PATH_SWEEP_REG 0x004   /* vq_mfma_reg_kernel: fp32 MFMA, latents in registers (d 64 / 128 otherwise) */
+#define VQVAE_VQ_PATH_SWEEP_LDS4 0x008  /* vq_mfma_kernel<4>: fp32 MFMA, any other d up to 238 */
+#define VQVAE_VQ_PATH_SWEEP_LDS2 0x010  /* vq_mfma_kernel<2>: d 239 .. 398 */
+#define VQVAE_VQ_PATH_SWEEP_LDS1 0x020  /* vq_mfma_kernel<1>: d 399 .. 598 */
+#define VQVAE_VQ_PATH_CANDIDATES 0x040  /* candidate sweep + vq_exact_cand_kernel in front of the all-codes re-check */
+#define VQVAE_VQ_PATH_RECHECK_R8 0x080  /* vq_exact_batched_kernel<8> (absent in mode 0: <2>) */
+#define VQVAE_VQ_PATH_GATHER_TILE 0x100 /* vq_gather_tile_kernel (absent: vq_gather_kernel) */
+#define VQVAE_VQ_PATH_GRAD_SORT 0x200   /* vqvae_vq_grad_w: counting sort + piecewise sums (absent: vq_gradw_scan_kernel) */
+int vqvae_vq_paths(int B, int d, int T, int k, int mode);
 
 /* ---- F.resize_images along T, align-corners (net.py:54-55): tables computed by
  *      the host in float64 exactly as Chainer does (v0/v1 int32[Tout], w0/w1 fp32[Tout]);

@@ -121,6 +121,7 @@ CONTRACTS = {
                                       'entry point when the candidate pass runs (k >= 1024 and N >= 1024); flagged / cand / overflow lists '
                                       'are written below the counters before they are read; n_rechecked: written'),
     'vqvae_vq_grad_w': _row(['test_vq_contract'], init='ws: cursor memset by the entry point; base / sorted / part64 written before read'),
+    'vqvae_vq_paths': _row(init=_QUERY),
     # ---- residual block / stack: value tests only so far (tests/test_gpu_kernels.py, test_gpu_model.py, test_gpu_configs.py);
     # their workspaces hold weight slabs and split-K partials, no counters (no global atomics in conv_gemm_*.hip / wgrad.hip
     # besides the profiling totals)

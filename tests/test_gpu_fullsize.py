@@ -171,17 +171,7 @@ def test_full_size_gradients_are_sums_over_shards(gpu):
         assert_close_scaled(g, 0.5 * (g_a[name] + g_b[name]), 2e-4, 'shard sum ' + name)
 
 
-def _vq_indices(gpu, z_dev, W_dev, B, d, T, k, mode):
-    """vqvae_vq_nearest_fwd through the C ABI on resident inputs -> (idx host (B, T), rows re-checked)."""
-    import ctypes as C
-    from vqvae_amd import _lib
-    from vqvae_amd.backend import DeviceArray
-    idx = DeviceArray((B, T), np.int32)
-    nre = DeviceArray((1,), np.int32)
-    ws = gpu.workspace(_lib.load().vqvae_vq_workspace_bytes(B, d, T, k))
-    _lib.call('vqvae_vq_nearest_fwd', z_dev.ptr, W_dev.ptr, B, d, T, k, mode, idx.ptr, None, nre.ptr, ws.ptr, ws.nbytes,
-              gpu.stream())
-    return idx.get(), int(nre.get()[0])
+from vq_domain_ref import vq_indices as _vq_indices          # vqvae_vq_nearest_fwd through the C ABI on resident inputs
 
 
 def test_vq_configs3_full_size_default_path_equals_exact_path(gpu):

@@ -94,7 +94,7 @@ def test_every_compute_export_has_a_contract_row():
     import test_gpu_abi_contract as T
     exports = header_exports()
     from vqvae_amd import _lib
-    assert set(exports) == set(_lib.PROTOTYPES), set(exports) ^ set(_lib.PROTOTYPES)       # 125 symbols
+    assert set(exports) == set(_lib.PROTOTYPES), set(exports) ^ set(_lib.PROTOTYPES)       # 127 symbols
     compute = [e for e in exports if not PLUMBING.match(e)]
     missing = [e for e in compute if e not in T.CONTRACTS]
     assert not missing, 'compute exports without a row in tests/test_gpu_abi_contract.py CONTRACTS: %s' % missing
