@@ -1450,33 +1450,54 @@ extern "C" size_t vqvae_resstack_dil_wgrad_workspace_bytes(const vqvae_resblock_
 // ascending tile order.
 // ---------------------------------------------------------------------------
 namespace vq {
-// one workgroup per (block l, batch item b, 64 gate channels): a thread walks ITS channel's tiles in ascending order (float4
-// per tile: coalesced across the channels) and adds them into its row of an LDS image of the output, which then leaves in
-// whole rows -- deterministic (one owner per channel, fixed order), every byte of `part` read once
+// one workgroup per (block l, batch item b, 64 gate channels), PBR_S waves: wave s owns the output positions
+// [s Tl / PBR_S, (s + 1) Tl / PBR_S) of every channel, and a thread walks the tiles that reach ITS channel's positions in
+// ascending order (float4 per tile: coalesced across the channels; a tile on a boundary is read by both neighbours) and adds
+// what falls on them into its part of an LDS image of the output, which then leaves in whole rows -- deterministic (one
+// owner per output, every output the sum of its tiles in ascending tile order from 0.f, whatever v0 holds), and four times
+// the loads in flight of one wave per 64 channels
 constexpr int PBR_C = 64;
-__global__ __launch_bounds__(PBR_C) void pullback_reduce_kernel(const float* __restrict__ part, const int32_t* __restrict__ v0,
-                                                               int nblocks, int B, int nt, int Cd, int Tl, float* __restrict__ gP, long gP_bstride) {
+constexpr int PBR_S = 4;
+__global__ __launch_bounds__(PBR_C * PBR_S) void pullback_reduce_kernel(const float* __restrict__ part, const int32_t* __restrict__ v0,
+                                                                       int nblocks, int B, int nt, int Cd, int Tl, float* __restrict__ gP, long gP_bstride) {
   extern __shared__ float img[];                 // [PBR_C][Tl + 1]
   const int chunks = Cd / PBR_C;
   const int cchunk = blockIdx.x % chunks;
   const int b = (blockIdx.x / chunks) % B;
   const int l = blockIdx.x / (chunks * B);
-  const int c = cchunk * PBR_C + threadIdx.x;
-  float* row = img + threadIdx.x * (Tl + 1);
-  for (int v = 0; v < Tl; ++v) row[v] = 0.f;
+  const int lane = threadIdx.x % PBR_C, sgm = threadIdx.x / PBR_C;      // sgm: wave-uniform
+  const int c = cchunk * PBR_C + lane;
+  const int pa = (int)((long)sgm * Tl / PBR_S), pb = (int)((long)(sgm + 1) * Tl / PBR_S);
+  float* row = img + lane * (Tl + 1);
+  for (int v = pa; v < pb; ++v) row[v] = 0.f;
+  // the tiles [nlo, nhi) that reach [pa, pb): a tile covers v0 .. v0 + 3
+  int nlo = nt, nhi = 0;
+  for (int n0 = 0; n0 < nt; n0 += PBR_C) {
+    const int n = n0 + lane;
+    bool hit = false;
+    if (n < nt) {
+      const int vb = v0[n * BN];
+      hit = vb + 3 >= pa && vb < pb;
+    }
+    const unsigned long long m = __ballot(hit);
+    if (m) {
+      nlo = min(nlo, n0 + __ffsll((long long)m) - 1);
+      nhi = max(nhi, n0 + 64 - __clzll((long long)m));
+    }
+  }
   const float4* src = reinterpret_cast<const float4*>(part) + (((long)l * B + b) * nt) * Cd + c;
-#pragma unroll 6                                 // (the tiles' loads are independent: six travel together)
-  for (int n = 0; n < nt; ++n) {
+#pragma unroll 8                                 // (the tiles' loads are independent: eight travel together)
+  for (int n = nlo; n < nhi; ++n) {
     const int vb = v0[n * BN];                   // wave-uniform
     const float4 p = src[(long)n * Cd];
-    row[vb] += p.x;
-    if (vb + 1 < Tl) row[vb + 1] += p.y;
-    if (vb + 2 < Tl) row[vb + 2] += p.z;
-    if (vb + 3 < Tl) row[vb + 3] += p.w;
+    if (vb >= pa && vb < pb) row[vb] += p.x;
+    if (vb + 1 >= pa && vb + 1 < pb) row[vb + 1] += p.y;
+    if (vb + 2 >= pa && vb + 2 < pb) row[vb + 2] += p.z;
+    if (vb + 3 >= pa && vb + 3 < pb) row[vb + 3] += p.w;
   }
   __syncthreads();
   float* dst = gP + (long)b * gP_bstride + ((long)l * Cd + cchunk * PBR_C) * Tl;      // PBR_C consecutive rows of Tl: one contiguous run
-  for (int i = threadIdx.x; i < PBR_C * Tl; i += PBR_C) dst[i] = img[(i / Tl) * (Tl + 1) + i % Tl];
+  for (int i = threadIdx.x; i < PBR_C * Tl; i += PBR_C * PBR_S) dst[i] = img[(i / Tl) * (Tl + 1) + i % Tl];
 }
 }  // namespace vq
 
@@ -1487,7 +1508,7 @@ extern "C" int vqvae_pullback_reduce_into(const float* part, const int32_t* v0, 
   VQ_REQUIRE(Cd % vq::PBR_C == 0 && (size_t)vq::PBR_C * (Tl + 1) * 4 <= 64 * 1024, "pullback_reduce: Cd %% 64 == 0, Tl <= 255");
   VQ_REQUIRE(gP_bstride >= (size_t)nblocks * Cd * Tl, "pullback_reduce: batch stride of gP smaller than the rows written");
   const size_t lds = (size_t)vq::PBR_C * (Tl + 1) * sizeof(float);
-  hipLaunchKernelGGL(vq::pullback_reduce_kernel, dim3((unsigned)(nblocks * B * (Cd / vq::PBR_C))), dim3(vq::PBR_C), lds, (hipStream_t)s, part, v0, nblocks, B, T / vq::BN, Cd, Tl, gP, (long)gP_bstride);
+  hipLaunchKernelGGL(vq::pullback_reduce_kernel, dim3((unsigned)(nblocks * B * (Cd / vq::PBR_C))), dim3(vq::PBR_C * vq::PBR_S), lds, (hipStream_t)s, part, v0, nblocks, B, T / vq::BN, Cd, Tl, gP, (long)gP_bstride);
   VQ_LAUNCH_CHECK();
   return 0;
 }

@@ -1133,70 +1133,103 @@ __global__ __launch_bounds__(1024, 4) void wgrad3_dma_kernel(const WgradArgs a) 
   }
 }
 
-// block = (64 outputs) x (4 split groups): each thread sums every 4th split with
-// 4 independent accumulators, then the 4 groups combine through LDS in fixed order.
-// Outputs [0,total) are weight-gradient entries, [total, total + nseg*Mpad) bias entries.
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const WgradArgs a, int nsplit) {
-  __shared__ float red[4][64];
+// A lane owns four adjacent outputs of one slab row and sums every split of them itself: 16-byte loads, up to 16 of them
+// in flight, no LDS and no barrier.  The order of additions per output is fixed (the step's determinism rests on it):
+// group g = 0..3 adds splits g, g+16, ... into v0, g+4, g+20, ... into v1, g+8, ... into v2 and g+12, ... into v3 while
+// sp + 12 < nsplit, the leftover splits of the group (stepping by 4) all into v0; the group is (v0+v1)+(v2+v3) and the
+// output (g0+g1)+(g2+g3).  Walking the splits in ascending order feeds every one of the 16 accumulators in that order.
+// Outputs [0,total) are weight-gradient entries in slab order ([tile row][tile column][128][128]),
+// [total, total + nseg*Mpad) bias entries.
+typedef float wr_f4 __attribute__((ext_vector_type(4), aligned(4)));    // (the workspace is only known to be float-aligned)
+constexpr int WR_THREADS = 128;
+__device__ __forceinline__ wr_f4 wgrad_reduce_sum(const float* __restrict__ p, const long sstride, const int nsplit) {
+  wr_f4 acc[4][4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[g][j] = wr_f4{0.f, 0.f, 0.f, 0.f};
+  int base = 0;
+  for (; base + 16 <= nsplit; base += 16) {              // every group's `sp + 12 < nsplit` holds
+    wr_f4 x[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) x[e] = *reinterpret_cast<const wr_f4*>(p + (long)(base + e) * sstride);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e & 3][e >> 2] += x[e];
+  }
+  const int rem = nsplit - base;                         // 0..15 (uniform)
+  if (rem > 0) {
+    wr_f4 x[15];
+#pragma unroll
+    for (int e = 0; e < 15; ++e)
+      x[e] = e < rem ? *reinterpret_cast<const wr_f4*>(p + (long)(base + e) * sstride) : wr_f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      if (g + 12 < rem) {                                // one more round of four for this group (g = 3 never: rem <= 15)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[g][j] += x[g + 4 * j < 15 ? g + 4 * j : 0];
+      } else {                                           // its leftover splits, all into v0
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (g + 4 * j < rem) acc[g][0] += x[g + 4 * j];
+      }
+    }
+  }
+  wr_f4 grp[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) grp[g] = (acc[g][0] + acc[g][1]) + (acc[g][2] + acc[g][3]);
+  return (grp[0] + grp[1]) + (grp[2] + grp[3]);
+}
+
+__global__ __launch_bounds__(WR_THREADS) void wgrad_reduce_kernel(const WgradArgs a, int nsplit) {
   if (a.skip_flag != nullptr && *a.skip_flag != 0) return;
-  const long ncol = (long)a.ntile_n * BN;
-  const long total = (long)a.ntile_m * BM * ncol;
+  const long total = (long)a.ntile_m * a.ntile_n * (BM * BN);
   const long mpad = (long)a.ntile_m * BM;
   const long total_ext = total + (a.bslabs ? (long)a.nseg * mpad : 0);
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  for (long base = (long)blockIdx.x * 64; base < total_ext; base += (long)gridDim.x * 64) {
-    const long i = base + tx;
-    bool ok = i < total_ext;
-    const bool is_bias = i >= total;
-    int row = 0, s = 0, ci = 0;
-    const float* p = a.slabs;
-    long sstride = (long)a.ntile_m * a.ntile_n * (BM * BN);
-    if (ok && !is_bias) {
-      const int colg = (int)(i % ncol);
-      row = (int)(i / ncol);
-      const int ntg = colg / BN, col = colg % BN;
+  const long i = ((long)blockIdx.x * WR_THREADS + threadIdx.x) * 4;      // total and mpad are multiples of 4
+  if (i >= total_ext) return;
+  if (i < total) {
+    const int col = (int)(i % BN);
+    const int r = (int)((i / BN) % BM);
+    const long tile = i / (BM * BN);
+    const int ntg = (int)(tile % a.ntile_n), mt = (int)(tile / a.ntile_n);
+    int s = 0;
 #pragma unroll
-      for (int k = 1; k < MAXSEG; ++k)
-        if (k < a.nseg && ntg >= a.seg[k].tile0) s = k;
-      ci = (ntg - a.seg[s].tile0) * BN + col;
-      ok = row < a.M && ci < a.seg[s].cin && a.seg[s].gw != nullptr;
-      const int mt = row / BM, r = row % BM;
-      p = a.slabs + ((long)mt * a.ntile_n + ntg) * (BM * BN) + r * BN + col;
-    } else if (ok) {
-      const long bi = i - total;
-      s = (int)(bi / mpad);
-      row = (int)(bi % mpad);
-      ok = row < a.M && (a.seg[s].gb || a.seg[s].gb2 || (s == 0 && a.ngbl > 0));
-      p = a.bslabs + (long)s * mpad + row;
-      sstride = (long)a.nseg * mpad;
+    for (int k = 1; k < MAXSEG; ++k)
+      if (k < a.nseg && ntg >= a.seg[k].tile0) s = k;
+    const WSeg& sg = a.seg[s];
+    const int ci = (ntg - sg.tile0) * BN + col;
+    const int row = mt * BM + r;
+    const int nok = sg.gw != nullptr && row < a.M ? min(4, sg.cin - ci) : 0;    // valid outputs among the four
+    if (nok <= 0) return;
+    const wr_f4 v = wgrad_reduce_sum(a.slabs + i, total, nsplit);
+    float* dst = sg.gw + (long)row * sg.gw_co_stride + (long)ci * sg.gw_ci_stride;
+    if (nok == 4 && sg.gw_ci_stride == 1) {
+      wr_f4* d4 = reinterpret_cast<wr_f4*>(dst);
+      *d4 = a.accumulate ? *d4 + v : v;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < nok) {
+          float* d = dst + (long)j * sg.gw_ci_stride;
+          *d = a.accumulate ? *d + v[j] : v[j];
+        }
     }
-    float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-    if (ok) {
-      int sp = ty;
-      for (; sp + 12 < nsplit; sp += 16) {
-        v0 += p[(long)sp * sstride];
-        v1 += p[(long)(sp + 4) * sstride];
-        v2 += p[(long)(sp + 8) * sstride];
-        v3 += p[(long)(sp + 12) * sstride];
-      }
-      for (; sp < nsplit; sp += 4) v0 += p[(long)sp * sstride];
-    }
-    __syncthreads();
-    red[ty][tx] = (v0 + v1) + (v2 + v3);
-    __syncthreads();
-    if (ty == 0 && ok) {
-      const float v = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
-      const WSeg& sg = a.seg[s];
-      if (!is_bias) {
-        float* dst = sg.gw + (long)row * sg.gw_co_stride + (long)ci * sg.gw_ci_stride;
-        *dst = a.accumulate ? *dst + v : v;
-      } else {
-        if (sg.gb) sg.gb[row] = a.accumulate ? sg.gb[row] + v : v;
-        if (sg.gb2) sg.gb2[row] = a.accumulate ? sg.gb2[row] + v : v;
-        if (s == 0)
-          for (int l = 0; l < a.ngbl; ++l)
-            if (a.gbl[l]) a.gbl[l][row] = a.accumulate ? a.gbl[l][row] + v : v;
-      }
+  } else {
+    const long bi = i - total;
+    const int s = (int)(bi / mpad);
+    const int row = (int)(bi % mpad);
+    const WSeg& sg = a.seg[s];
+    if (row >= a.M || !(sg.gb || sg.gb2 || (s == 0 && a.ngbl > 0))) return;
+    const wr_f4 v = wgrad_reduce_sum(a.bslabs + bi, (long)a.nseg * mpad, nsplit);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int rj = row + j;
+      if (rj >= a.M) break;
+      if (sg.gb) sg.gb[rj] = a.accumulate ? sg.gb[rj] + v[j] : v[j];
+      if (sg.gb2) sg.gb2[rj] = a.accumulate ? sg.gb2[rj] + v[j] : v[j];
+      if (s == 0)
+        for (int l = 0; l < a.ngbl; ++l)
+          if (a.gbl[l]) a.gbl[l][rj] = a.accumulate ? a.gbl[l][rj] + v[j] : v[j];
     }
   }
 }
@@ -1387,10 +1420,10 @@ int launch_wgrad(WgradArgs& w, const WgradPlan& p, float* ws, int tag, hipStream
   if (int e = select_wgrad(w, p, fast, f)) return e;
   hipLaunchKernelGGL(wgrad_form_kernel(f), f.grid, dim3(f.threads), 0, st, w);
   VQ_LAUNCH_CHECK();
+  // one lane per four outputs (bias entries included), no grid stride: 1 285 workgroups for a four-block dilated launch
   const long total = (long)p.ntile_m * BM * p.ntile_n * BN + (long)p.nseg * p.ntile_m * BM;
-  int nb = (int)((total + 63) / 64);
-  if (nb > 8192) nb = 8192;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nb), dim3(256), 0, st, w, p.nsplit);
+  const int nb = (int)((total / 4 + WR_THREADS - 1) / WR_THREADS);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nb), dim3(WR_THREADS), 0, st, w, p.nsplit);
   VQ_LAUNCH_CHECK();
   return 0;
 }
