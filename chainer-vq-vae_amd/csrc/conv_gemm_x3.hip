@@ -783,7 +783,7 @@ __global__ __launch_bounds__(512, 1) void lin128_stream_kernel(const Lin128Args 
     tile += stride;
     if (tile >= a.ntiles) break;
   }
-  if (a.amax_out != nullptr) amax_commit(am, a.amax_out);
+  if (a.amax_out != nullptr) amax_commit(YPRE ? am * PRESPLIT_AMAX_UP : am, a.amax_out);
 #undef L128_FETCH
 #undef L128_STAGE
 #undef L128_XLOAD

@@ -262,6 +262,7 @@ __global__ __launch_bounds__(64 * GS_WAVES) void gate_bwd_strip_kernel(const Gem
     __syncthreads();
     if (tid == 0) {
       for (int i = 1; i < GS_WAVES; ++i) m = fmaxf(m, red[i]);
+      m *= PRESPLIT_AMAX_UP;                     // gh is stored pre-split: cover what it decodes to
       atomicMax(od.amax_out + (blockIdx.x & (AMAX_SLOTS - 1)), __builtin_bit_cast(unsigned, m));
     }
   }

@@ -195,6 +195,10 @@ __device__ __forceinline__ float wave_max(float m) {
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
   return m;
 }
+// A tensor stored PRE-SPLIT (presplit_pair) decodes to hi + lo, 22 significant bits rounded to nearest: up to 2^-23 (relative)
+// ABOVE the fp32 value it was made from.  The epilogues collect max |fp32 value|; what they publish for a pre-split output is
+// that times 1 + 2^-22, so that the published word is never below the maximum of what the tensor's readers decode.
+constexpr float PRESPLIT_AMAX_UP = 1.f + 0x1p-22f;
 // m >= 0: this thread's max |value stored|.  EVERY thread of the workgroup must call (two barriers).
 __device__ __forceinline__ void amax_commit(float m, unsigned* dst) {
   __shared__ float red[16];
@@ -853,7 +857,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[2
           }
         }
     }
-    if (od.amax_out != nullptr) amax_commit(am, od.amax_out);
+    if (od.amax_out != nullptr) amax_commit((OUT & 1) != 0 ? am * PRESPLIT_AMAX_UP : am, od.amax_out);
   }
 }
 

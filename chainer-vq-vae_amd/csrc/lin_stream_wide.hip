@@ -182,7 +182,7 @@ __global__ __launch_bounds__(512, 1) void lin256_stream_kernel(const LinWideArgs
     tile += stride;
     if (tile >= a.ntiles) break;
   }
-  if (a.amax_out != nullptr) amax_commit(am, a.amax_out);
+  if (a.amax_out != nullptr) amax_commit(am * PRESPLIT_AMAX_UP, a.amax_out);      // (x_{l+1} is always stored pre-split here)
 #undef LW_FETCH
 #undef LW_STAGE
 #undef LW_XLOAD

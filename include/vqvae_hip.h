@@ -346,7 +346,9 @@ typedef struct {
   uint32_t* gx;             /* bwd out: max |gx|     (the previous block's g_res); may be NULL         */
   /* pre-split storage (VQVAE_STORE_*_F16X2; NULL / ignored otherwise).  With VQVAE_STORE_X_F16X2 `x` above holds the
    * SCALE words of x (the res_scale of the block before) and x_max its actual maximum (that block's `res`); with an
-   * fp32 x both are the same group.  With VQVAE_STORE_GH_F16X2 `gh` still receives the actual maximum.              */
+   * fp32 x both are the same group.  With VQVAE_STORE_GH_F16X2 `gh` still receives the actual maximum.  The maximum
+   * published for a tensor that is stored pre-split (`res`, `gh`) is that of the fp32 values times 1 + 2^-22: never below,
+   * and within 2^-21 of, the maximum of what the stored dwords decode to.                                            */
   const uint32_t* x_max;    /* fwd in : actual max |x| (enters the bound of the residual output)              */
   uint32_t* res_scale;      /* fwd out: scale words of the pre-split residual output (zeroed by the caller)    */
   uint32_t* gh_scale;       /* bwd out: scale words of the pre-split gh_out (zeroed by the caller)             */

@@ -10,7 +10,7 @@
 Every case also compares the result with float64 / the oracle at the bar the entry point's existing test uses.
 
 CONTRACTS lists every compute export of the header (tests/test_host_zoned.py fails when one has no row) with the tests
-of this file that apply each contract to it -- an empty tuple means NOT applied here, and says where the entry point is
+of this file -- or, for the packed chain, of tests/test_gpu_abi_contract_chain.py -- that apply each contract to it -- an empty tuple means NOT applied here, and says where the entry point is
 covered by value instead -- and, under `init`, who initialises what the entry point keeps in caller memory.  That column is
 the record of the reading that has to precede a poisoned workspace: a counter, cursor or flag word in a workspace may only
 start as NaN when the entry point's own host code initialises it.
@@ -23,6 +23,7 @@ Shown able to fail (one-line mutations built into a scratch copy of csrc/ and ru
   maxima:      `amax_commit` skipping the atomicMax of a launch's LAST workgroup: test_conv1d_contract fails in every
                matmul mode with "published max |y|" / "published max |gx|" (words 0 against 8.96), and
                test_published_maximum_conv fails for the spike in the last tile of the last batch item (`last_all`).
+The same three mutations planted in code of the packed chain are recorded in tests/test_gpu_abi_contract_chain.py.
 """
 import ctypes as C
 import zlib
@@ -38,6 +39,8 @@ from zoned import In, Out, Ws, run_contract
 pytestmark = pytest.mark.gpu
 
 _CONV = ('test_conv1d_contract',)
+_CHAIN = ('test_packed_chain_contract', 'test_packed_chain_contract_bf16')       # tests/test_gpu_abi_contract_chain.py
+_CHAIN_MAX = ('test_packed_chain_contract', 'test_published_maximum_chain')
 _NONE = ()
 
 
@@ -122,8 +125,9 @@ CONTRACTS = {
                                       'are written below the counters before they are read; n_rechecked: written'),
     'vqvae_vq_grad_w': _row(['test_vq_contract'], init='ws: cursor memset by the entry point; base / sorted / part64 written before read'),
     'vqvae_vq_paths': _row(init=_QUERY),
-    # ---- residual block / stack: value tests only so far (tests/test_gpu_kernels.py, test_gpu_model.py, test_gpu_configs.py);
-    # their workspaces hold weight slabs and split-K partials, no counters (no global atomics in conv_gemm_*.hip / wgrad.hip
+    # ---- residual block / stack.  The packed latent-rate-condition chain (the twelve entry points from vqvae_resblock_fwd_packed
+    # on) is driven entry point by entry point in tests/test_gpu_abi_contract_chain.py (_CHAIN*: tests of that module).  The
+    # workspaces hold weight slabs and split-K partials, no counters (no global atomics in conv_gemm_*.hip / wgrad.hip
     # besides the profiling totals)
     'vqvae_resblock_workspace_bytes': _row(init=_QUERY),
     'vqvae_resblock_bf16_storage': _row(init=_QUERY),
@@ -134,18 +138,28 @@ CONTRACTS = {
     'vqvae_resblock_fwd': _row(['test_resblock_unpacked_contract'], init='ws: weight slabs + gate scratch, written by the call'),
     'vqvae_resblock_bwd': _row(['test_resblock_unpacked_contract'], init='grads_accumulate = 0: every given gradient fully written'),
     'vqvae_resblock_wgrad': _row(['test_resblock_unpacked_contract']),
-    'vqvae_resblock_fwd_packed': _row(init='res / res_scale / gh words: zeroed by the caller (not applied here)'),
-    'vqvae_resblock_bwd_packed': _row(init='not applied here'),
-    'vqvae_resstack_pack': _row(init='not applied here'),
-    'vqvae_resstack_skip_fwd': _row(init='skip_amax_out: zeroed by the caller (not applied here)'),
-    'vqvae_resstack_skip_prepare': _row(init='not applied here'),
-    'vqvae_resstack_skip_fwd_prepared': _row(init='not applied here'),
-    'vqvae_resstack_gcond_bwd': _row(init='not applied here'),
-    'vqvae_resstack_skip_wgrad': _row(init='not applied here'),
-    'vqvae_resstack_res_wgrad': _row(init='not applied here'),
-    'vqvae_resstack_dil_wgrad': _row(init='not applied here'),
-    'vqvae_pullback_reduce': _row(init='not applied here'),
-    'vqvae_pullback_reduce_into': _row(init='not applied here'),
+    'vqvae_resblock_fwd_packed': _row(_CHAIN, maxima=_CHAIN_MAX,
+                                      init='amax->res, amax->res_scale: zeroed by the caller, raised / word 0 set; gates: the tanh half is left '
+                                           'unwritten under VQVAE_STORE_GATES_SIG; bf16-stored tensors: the first half of the buffer; ws: unused '
+                                           'beside its size check (the slabs are `packed`)'),
+    'vqvae_resblock_bwd_packed': _row(_CHAIN, maxima=_CHAIN_MAX,
+                                      init='amax->gh, amax->gx, amax->gh_scale: zeroed by the caller; gh, gx, pb_part fully written (pb_part: '
+                                           'all four latent positions of every tile)'),
+    'vqvae_resstack_pack': _row(_CHAIN, init='packed: the slabs the packed chain reads and the maxima / norm words of each block are written; '
+                                             'the condition-projection slabs and the res slabs of a block with has_res = 0 are not (compared '
+                                             'through the entry points that read the image)'),
+    'vqvae_resstack_skip_fwd': _row(_CHAIN, maxima=_CHAIN_MAX, init='skip_amax_out: zeroed by the caller; accumulate = 1: skip is the addend; '
+                                                                   'ws: slabs, bias sums, weight maxima written before the GEMM reads them'),
+    'vqvae_resstack_skip_prepare': _row(_CHAIN, init='ws: slabs | bias sums | weight maxima written; the tail of the shared workspace is not'),
+    'vqvae_resstack_skip_fwd_prepared': _row(_CHAIN, maxima=_CHAIN_MAX, init='ws: input (as vqvae_resstack_skip_prepare left it); '
+                                                                            'skip_amax_out: zeroed by the caller'),
+    'vqvae_resstack_gcond_bwd': _row(['test_packed_chain_contract'], init='accumulate = 1: gcond is the addend; ws: slabs written before read'),
+    'vqvae_resstack_skip_wgrad': _row(_CHAIN, init='accumulate = 1: gWs, gbs are the addends; ws: split-K partials written before the reduce'),
+    'vqvae_resstack_res_wgrad': _row(_CHAIN, init='as skip_wgrad; blocks with g_res[l] == NULL are skipped'),
+    'vqvae_resstack_dil_wgrad': _row(_CHAIN + ('test_dil_wgrad_dma_contract_presplit', 'test_dil_wgrad_dma_contract_bf16'),
+                                     init='as skip_wgrad; NULL gWd[l] / gbd[l] are skipped'),
+    'vqvae_pullback_reduce': _row(['test_packed_chain_contract'], init='gP fully written (every output starts from 0.f)'),
+    'vqvae_pullback_reduce_into': _row(['test_packed_chain_contract'], init='the rows of the group inside gP_bstride; the rest keeps its bits'),
     # ---- generation: zones only by design, and never a poisoned workspace (vqvae_wavenet_gen_run's workspace holds the
     # flags its workgroups wait on; the call zero-fills it at t0 == 0).  Not applied here: tests/test_gpu_generate*.py.
     'vqvae_wavenet_gen_step': _row(init='device state zero-filled by the caller ("initialize")'),
@@ -336,7 +350,8 @@ def test_absmax_and_contract_check(gpu):
 # --------------------------------------------------------------------------- #
 # losses
 # --------------------------------------------------------------------------- #
-@pytest.mark.parametrize('q,B,T', [(3, 1, 1), (50, 3, 21), (256, 1, 65), (50, 1, 20001), (256, 3, 63), (3, 5, 13)])
+@pytest.mark.parametrize('q,B,T', [(3, 1, 1), (50, 3, 21), (256, 1, 65), (50, 1, 20001), (256, 3, 63), (3, 5, 13),
+                                     (3, 1, 4), (50, 3, 20), (256, 2, 128)])       # T % 4 == 0: xent_bwd4_kernel
 def test_softmax_xent_contract(gpu, q, B, T):
     """Class counts that do not divide by four, row counts around the 64-row workgroup, logits of +-80, a row of equal
     logits, targets 0 and q - 1; the bound published beside gy against the looseness the header states for it."""

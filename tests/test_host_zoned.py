@@ -1,6 +1,7 @@
 """The red-zone checker of tests/zoned.py on NumPy buffers (no GPU): an instrument that cannot fail proves nothing, so
 every planted write must be reported at the offset it was planted at, and an intact buffer must pass.  Also: every
-compute export of include/vqvae_hip.h has a row in the contract table of tests/test_gpu_abi_contract.py."""
+compute export of include/vqvae_hip.h has a row in the contract table of tests/test_gpu_abi_contract.py, and the tests a row
+names exist there or in tests/test_gpu_abi_contract_chain.py."""
 import os
 import re
 
@@ -92,6 +93,7 @@ def header_exports():
 
 def test_every_compute_export_has_a_contract_row():
     import test_gpu_abi_contract as T
+    import test_gpu_abi_contract_chain as TC
     exports = header_exports()
     from vqvae_amd import _lib
     assert set(exports) == set(_lib.PROTOTYPES), set(exports) ^ set(_lib.PROTOTYPES)       # 127 symbols
@@ -105,4 +107,5 @@ def test_every_compute_export_has_a_contract_row():
         # a row that claims a contract names the test that applies it, and that test exists
         for key in ('zones', 'inputs_only', 'maxima'):
             for test in row[key]:
-                assert hasattr(T, test), '%s: %s names %s, which is not in the file' % (name, key, test)
+                assert callable(getattr(T, test, None)) or callable(getattr(TC, test, None)), \
+                    '%s: %s names %s, which is in neither module' % (name, key, test)
