@@ -14,5 +14,6 @@ from .updaters import (VQVAE_ParallelUpdater, VQVAE_StandardUpdater,  # noqa: F4
 from .utils import VQ, ExponentialMovingAverage, MuLaw, StraightThrough, straight_through  # noqa: F401
 from .wavenet import ResidualBlock, ResidualNet, WaveNet  # noqa: F401
 from .generation import DeviceUniforms, LatentCondition  # noqa: F401
+from .corpus import CorpusView, ResidentCorpus, ResidentCorpusIterator  # noqa: F401
 from .synthesis import synthesize, synthesize_many  # noqa: F401
 from .reporting import LogReport, PlotReport, PrintReport  # noqa: F401

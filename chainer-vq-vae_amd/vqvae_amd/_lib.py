@@ -92,6 +92,11 @@ class GenRng(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('ids', P)]
 
 
+class Corpus(C.Structure):
+    """vqvae_corpus (include/vqvae_corpus.h): the device-resident corpus, or a view of it (view NULL = the identity)."""
+    _fields_ = [(n, P) for n in ('samples', 'offset', 'length', 'speaker', 'view')] + [('n_view', C.c_int32)]
+
+
 # name -> (restype, argtypes); this table IS the list of symbols the header declares
 PROTOTYPES = {
     'vqvae_last_error_string': (c_char_p, []),
@@ -331,6 +336,14 @@ GEN_RNG_PROTOTYPES = {
 }
 GEN_RNG_ABI_VERSION = 1           # vqvae_gen_rng_abi_version()
 
+# include/vqvae_corpus.h: minibatches drawn on the device from a corpus that lives there, a tenth table and version
+CORPUS_PROTOTYPES = {
+    'vqvae_corpus_abi_version': (c_int, []),
+    'vqvae_corpus_draw': (c_int, [C.POINTER(Corpus), C.c_uint64, c_int, C.c_uint64, c_int, c_int, c_int, c_int, c_int, P, c_int,
+                                  P, P, P, P, P, P, P]),
+}
+CORPUS_ABI_VERSION = 1            # vqvae_corpus_abi_version()
+
 # elementwise op codes / profiler tags (mirror the header)
 MAX_STACK_GROUP = 24              # blocks per resstack call (MAXSEG in csrc/gemm_common.h)
 STORE_X_BF16, STORE_RES_BF16 = 2, 4
@@ -374,7 +387,8 @@ def load():
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     lib = C.CDLL(LIB_PATH)
     for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES, KMEANS_PROTOTYPES, OPTIM_PROTOTYPES,
-                  SAMPLING_PROTOTYPES, GEN_SLOTS_PROTOTYPES, GEN_COND_PROTOTYPES, GEN_RNG_PROTOTYPES):
+                  SAMPLING_PROTOTYPES, GEN_SLOTS_PROTOTYPES, GEN_COND_PROTOTYPES, GEN_RNG_PROTOTYPES,
+                  CORPUS_PROTOTYPES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)           # AttributeError if the symbol is missing
             fn.restype = res
@@ -406,6 +420,9 @@ def load():
     if lib.vqvae_gen_rng_abi_version() != GEN_RNG_ABI_VERSION:
         raise ImportError('libvqvae_hip.so at %s has device-uniforms ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
                           % (LIB_PATH, lib.vqvae_gen_rng_abi_version(), GEN_RNG_ABI_VERSION))
+    if lib.vqvae_corpus_abi_version() != CORPUS_ABI_VERSION:
+        raise ImportError('libvqvae_hip.so at %s has resident-corpus ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
+                          % (LIB_PATH, lib.vqvae_corpus_abi_version(), CORPUS_ABI_VERSION))
     _lib = lib
     return lib
 

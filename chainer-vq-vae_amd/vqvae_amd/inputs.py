@@ -43,6 +43,12 @@ def mulaw_thresholds(mu=256):
     return _key_f32(hi).astype(np.float32)
 
 
+def peak_normalise(wave):
+    """utils.py:58-59: the waveform divided by its absolute maximum, float32 (crop_or_pad and corpus.ResidentCorpus)."""
+    raw = np.asarray(wave, np.float32)
+    return (raw / np.abs(raw).max()).astype(np.float32)
+
+
 def crop_or_pad(wave, length, start=None, rng=random):
     """The padding / trimming branch of Preprocess.__call__ (utils.py:57-58, 65-81) for one loaded
     and silence-trimmed waveform: peak-normalise, then zero-pad to ``length + 1`` samples or take
@@ -50,8 +56,7 @@ def crop_or_pad(wave, length, start=None, rng=random):
     reference's unseeded ``random``).  Zero padding of the waveform IS the reference's padding of
     the bins with quantize // 2, because MuLaw.transform(0.0) == quantize // 2 (utils.py:74)."""
     L = length + 1                                                 # utils.py:47
-    raw = np.asarray(wave, np.float32)
-    raw = (raw / np.abs(raw).max()).astype(np.float32)             # utils.py:58-59
+    raw = peak_normalise(wave)                                     # utils.py:58-59
     if len(raw) <= L:
         return np.concatenate((raw, np.zeros(L - len(raw), np.float32)))
     if start is None:
