@@ -15,5 +15,6 @@ from .utils import VQ, ExponentialMovingAverage, MuLaw, StraightThrough, straigh
 from .wavenet import ResidualBlock, ResidualNet, WaveNet  # noqa: F401
 from .generation import DeviceUniforms, LatentCondition  # noqa: F401
 from .corpus import CorpusView, ResidentCorpus, ResidentCorpusIterator  # noqa: F401
+from .ingest import (DeviceIngest, corpus_files, read_wav, resample_taps, write_wav)  # noqa: F401
 from .synthesis import synthesize, synthesize_many  # noqa: F401
 from .reporting import LogReport, PlotReport, PrintReport  # noqa: F401

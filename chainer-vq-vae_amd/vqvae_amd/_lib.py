@@ -344,6 +344,19 @@ CORPUS_PROTOTYPES = {
 }
 CORPUS_ABI_VERSION = 1            # vqvae_corpus_abi_version()
 
+# include/vqvae_ingest.h: decode, resample, trim and normalise raw audio into a corpus's waveforms, an eleventh table and version
+INGEST_PROTOTYPES = {
+    'vqvae_ingest_abi_version': (c_int, []),
+    'vqvae_ingest_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'vqvae_ingest_resample': (c_int, [P, c_int, c_int, P, P, c_int, c_int, P, c_int, c_int, c_int, P, P, c_int, P]),
+    'vqvae_ingest_trim_bounds': (c_int, [P, P, P, c_int, c_int, c_double, P, c_size_t, P, P]),
+    'vqvae_ingest_pack': (c_int, [P, P, P, P, c_int, c_int, P, P]),
+}
+INGEST_ABI_VERSION = 1            # vqvae_ingest_abi_version()
+INGEST_TILE = 1024                # VQVAE_INGEST_TILE
+INGEST_MAX_TAPS = 1 << 22         # VQVAE_INGEST_MAX_TAPS
+INGEST_MAX_WINDOW = 16384         # VQVAE_INGEST_MAX_WINDOW
+
 # elementwise op codes / profiler tags (mirror the header)
 MAX_STACK_GROUP = 24              # blocks per resstack call (MAXSEG in csrc/gemm_common.h)
 STORE_X_BF16, STORE_RES_BF16 = 2, 4
@@ -388,7 +401,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES, KMEANS_PROTOTYPES, OPTIM_PROTOTYPES,
                   SAMPLING_PROTOTYPES, GEN_SLOTS_PROTOTYPES, GEN_COND_PROTOTYPES, GEN_RNG_PROTOTYPES,
-                  CORPUS_PROTOTYPES):
+                  CORPUS_PROTOTYPES, INGEST_PROTOTYPES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)           # AttributeError if the symbol is missing
             fn.restype = res
@@ -423,6 +436,9 @@ def load():
     if lib.vqvae_corpus_abi_version() != CORPUS_ABI_VERSION:
         raise ImportError('libvqvae_hip.so at %s has resident-corpus ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
                           % (LIB_PATH, lib.vqvae_corpus_abi_version(), CORPUS_ABI_VERSION))
+    if lib.vqvae_ingest_abi_version() != INGEST_ABI_VERSION:
+        raise ImportError('libvqvae_hip.so at %s has ingest ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
+                          % (LIB_PATH, lib.vqvae_ingest_abi_version(), INGEST_ABI_VERSION))
     _lib = lib
     return lib
 

@@ -152,6 +152,52 @@ class ResidentCorpus(_Utterances):
         self.samples = None
         return self
 
+    @classmethod
+    def from_arrays(cls, raws, srs, speakers, sr=16000, res_type='kaiser_fast', top_db=20, batch_bytes=64 << 20,
+                    skip_bad=False):
+        """The corpus from raw audio, preprocessed on the device (vqvae_amd.ingest, include/vqvae_ingest.h): ``raws`` are
+        arrays (frames,) or (frames, channels), int16 or floating, at the sample rates ``srs`` (or one for all).  They are
+        decoded to mono, resampled to ``sr``, silence-trimmed at ``top_db`` and peak-normalised there, in batches of at most
+        ``batch_bytes`` of raw audio; utterance order is input order.  A wave that is all zeros, holds a non-finite sample,
+        is empty or too short to trim is a ValueError naming its index, or with ``skip_bad`` is left out and listed in
+        ``corpus.skipped`` as (index, reason)."""
+        from . import ingest
+        raws = list(raws)
+        srs = [srs] * len(raws) if np.ndim(srs) == 0 else list(srs)
+        if len(srs) != len(raws):
+            raise ValueError('ResidentCorpus: %d sample rates for %d waves' % (len(srs), len(raws)))
+        items = [ingest._Array(raw, s, 'wave %d' % i) for i, (raw, s) in enumerate(zip(raws, srs))]
+        return cls._from_items(items, speakers, ingest.DeviceIngest(sr, res_type, top_db), batch_bytes, skip_bad,
+                               lambda i: i)
+
+    @classmethod
+    def from_files(cls, files, speakers, sr=16000, res_type='kaiser_fast', top_db=20, batch_bytes=64 << 20, skip_bad=False):
+        """``from_arrays`` for WAV files (ingest.read_wav; ingest.corpus_files lists a VCTK, ARCTIC or 'vs' tree): the
+        headers are read first, the samples batch by batch.  Errors and ``corpus.skipped`` name the file."""
+        from . import ingest
+        files = [str(f) for f in files]
+        items = [ingest._File(f) for f in files]
+        return cls._from_items(items, speakers, ingest.DeviceIngest(sr, res_type, top_db), batch_bytes, skip_bad,
+                               lambda i: files[i])
+
+    @classmethod
+    def _from_items(cls, items, speakers, front, batch_bytes, skip_bad, label):
+        speakers = list(speakers)
+        if not items:
+            raise ValueError('ResidentCorpus: no waves')
+        if len(speakers) != len(items):
+            raise ValueError('ResidentCorpus: %d speakers for %d waves' % (len(speakers), len(items)))
+        _check_description([1] * len(items), speakers)
+        samples, lengths, keep, skipped = front.ingest(items, batch_bytes, skip_bad, 'ResidentCorpus')
+        self = cls.__new__(cls)
+        self._describe(*_check_description(lengths.tolist(), [speakers[i] for i in keep]))
+        self.samples = samples
+        self.skipped = [(label(i), reason) for i, reason in skipped]
+        self._offset_dev = backend.to_device(self.offsets)
+        self._length_dev = backend.to_device(self.lengths)
+        self._speaker_dev = backend.to_device(self.speakers)
+        return self
+
     def _describe(self, lengths, speakers):
         self.corpus = self
         self.lengths, self.speakers = lengths, speakers
