@@ -16,5 +16,6 @@ from .wavenet import ResidualBlock, ResidualNet, WaveNet  # noqa: F401
 from .generation import DeviceUniforms, LatentCondition  # noqa: F401
 from .corpus import CorpusView, ResidentCorpus, ResidentCorpusIterator  # noqa: F401
 from .ingest import (DeviceIngest, corpus_files, read_wav, resample_taps, write_wav)  # noqa: F401
+from .frontend import (LatentCodes, condition_many, encode_many, frontend_many, plan_chunks)  # noqa: F401
 from .synthesis import synthesize, synthesize_many  # noqa: F401
 from .reporting import LogReport, PlotReport, PrintReport  # noqa: F401

@@ -97,6 +97,12 @@ class Corpus(C.Structure):
     _fields_ = [(n, P) for n in ('samples', 'offset', 'length', 'speaker', 'view')] + [('n_view', C.c_int32)]
 
 
+class RaggedConvDesc(C.Structure):
+    """vqvae_ragged_conv_desc (include/vqvae_ragged.h): one conv stage over a ragged batch."""
+    _fields_ = [(n, C.c_int32) for n in ('n', 'cin', 'cout', 'K', 'stride', 'pad', 'dil', 'relu', 'blocked_out')] + \
+               [('ttot_out', C.c_int64), ('x_cstride', C.c_int64)]
+
+
 # name -> (restype, argtypes); this table IS the list of symbols the header declares
 PROTOTYPES = {
     'vqvae_last_error_string': (c_char_p, []),
@@ -357,6 +363,16 @@ INGEST_TILE = 1024                # VQVAE_INGEST_TILE
 INGEST_MAX_TAPS = 1 << 22         # VQVAE_INGEST_MAX_TAPS
 INGEST_MAX_WINDOW = 16384         # VQVAE_INGEST_MAX_WINDOW
 
+# include/vqvae_ragged.h: the encoder's and ConditionEmbed's convs over a ragged batch and the two gathers, a twelfth table and version
+RAGGED_PROTOTYPES = {
+    'vqvae_ragged_abi_version': (c_int, []),
+    'vqvae_ragged_conv_workspace_bytes': (c_size_t, [C.POINTER(RaggedConvDesc)]),
+    'vqvae_ragged_conv_fwd': (c_int, [C.POINTER(RaggedConvDesc), P, P, P, P, P, P, P, P, c_size_t, P]),
+    'vqvae_ragged_code_gather': (c_int, [P, P, C.c_int64, c_int, c_int, P, P]),
+    'vqvae_ragged_speaker_gather': (c_int, [P, P, c_int, c_int, c_int, P, P]),
+}
+RAGGED_ABI_VERSION = 1            # vqvae_ragged_abi_version()
+
 # elementwise op codes / profiler tags (mirror the header)
 MAX_STACK_GROUP = 24              # blocks per resstack call (MAXSEG in csrc/gemm_common.h)
 STORE_X_BF16, STORE_RES_BF16 = 2, 4
@@ -401,7 +417,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES, KMEANS_PROTOTYPES, OPTIM_PROTOTYPES,
                   SAMPLING_PROTOTYPES, GEN_SLOTS_PROTOTYPES, GEN_COND_PROTOTYPES, GEN_RNG_PROTOTYPES,
-                  CORPUS_PROTOTYPES, INGEST_PROTOTYPES):
+                  CORPUS_PROTOTYPES, INGEST_PROTOTYPES, RAGGED_PROTOTYPES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)           # AttributeError if the symbol is missing
             fn.restype = res
@@ -439,6 +455,9 @@ def load():
     if lib.vqvae_ingest_abi_version() != INGEST_ABI_VERSION:
         raise ImportError('libvqvae_hip.so at %s has ingest ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
                           % (LIB_PATH, lib.vqvae_ingest_abi_version(), INGEST_ABI_VERSION))
+    if lib.vqvae_ragged_abi_version() != RAGGED_ABI_VERSION:
+        raise ImportError('libvqvae_hip.so at %s has ragged-front-end ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
+                          % (LIB_PATH, lib.vqvae_ragged_abi_version(), RAGGED_ABI_VERSION))
     _lib = lib
     return lib
 

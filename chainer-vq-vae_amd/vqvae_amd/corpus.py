@@ -118,6 +118,12 @@ class _Utterances(object):
     def hours(self, sr=16000):
         return float(np.sum(self.lengths, dtype=np.int64)) / float(sr) / 3600.0
 
+    def encode(self, encoder, vq, chunk_bytes=1 << 30):
+        """The discrete codes of these utterances, whole (frontend.LatentCodes): the encoder's ragged convs read every
+        utterance in place from the corpus buffer through its offsets and lengths, nothing is copied or sliced."""
+        from .frontend import encode_corpus
+        return encode_corpus(self, encoder, vq, chunk_bytes)
+
 
 class ResidentCorpus(_Utterances):
     """``waves``: loaded, silence-trimmed waveforms (what inputs.crop_or_pad takes); ``speakers``: one int id each.

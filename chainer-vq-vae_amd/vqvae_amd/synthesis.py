@@ -78,7 +78,8 @@ def synthesize(encoder, vq, decoder, condition_embed, x_enc, global_condition, r
 
 def synthesize_many(encoder, vq, decoder, condition_embed, waves, global_condition, rng=None,
                     quantize=256, use_logistic=False, n_steps=None, group=128, refill=True,
-                    temperature=None, top_k=None, top_p=None, return_output=False, latent_condition=False):
+                    temperature=None, top_k=None, top_p=None, return_output=False, latent_condition=False,
+                    batched_frontend=False):
     """``synthesize`` for a list of waveforms of different lengths (a validation set, a corpus).
 
     waves: list of N normalised waveforms, each a host or device float32 array of T_i + 1 samples (any shape that
@@ -101,6 +102,11 @@ def synthesize_many(encoder, vq, decoder, condition_embed, waves, global_conditi
         default model (123 GB for 300 utterances of up to 10 s at 16 kHz), the latent form 32 bytes per sample of each
         utterance.  On the default decoder the step is also a quarter faster with it (the gate launches read a
         contiguous column).  The default is False because the call without it is the call as it was.
+    batched_frontend: with ``latent_condition``, encode, quantise and embed ALL utterances per launch
+        (frontend.frontend_many: the ragged convs of include/vqvae_ragged.h, where every tap stays inside its own
+        utterance) instead of one utterance at a time with n = 1: 12 calls and two uploads (waves, tables) per chunk instead
+        of about 20 launches and two uploads per utterance.  A ValueError without ``latent_condition``.  The default is
+        False: the call without it launches exactly what it launched before.
     Returns the list of N host waves, utterance i of its own length T_i, as synthesize returns them (mu-law expanded
     for the softmax output); with ``return_output`` the list of (wave, output) pairs."""
     from .generation import DeviceUniforms
@@ -110,15 +116,23 @@ def synthesize_many(encoder, vq, decoder, condition_embed, waves, global_conditi
                           np.int32).reshape(-1)
     if speakers.shape != (N,):
         raise ValueError('synthesize_many: one speaker id per waveform (%d), got %s' % (N, speakers.shape))
+    if batched_frontend and not latent_condition:
+        raise ValueError('synthesize_many: batched_frontend needs latent_condition=True (the ragged front end writes the '
+                         'latent-rate condition)')
     conds = []
     with core.using_config('train', False), core.no_backprop_mode():
-        for w, spk in zip(waves, speakers):
+        for w, spk in ([] if batched_frontend else zip(waves, speakers)):
             xd = w if backend.is_device(w) else backend.to_device(np.asarray(w, np.float32))
             xd = xd.reshape(1, 1, xd.size, 1)
             e = vq(encoder(Variable(xd)))                                                  # generate.py:95-96
             c = condition_embed(e, Variable(backend.to_device(np.array([spk], np.int32)))).data   # generate.py:97-98
             conds.append(_latent_condition(c, condition_embed) if latent_condition else c.reshape(c.shape[1], c.shape[2]))
-    if latent_condition:
+    if batched_frontend:
+        from .frontend import frontend_many
+        cond = frontend_many(encoder, vq, condition_embed, waves, speakers)
+        lengths = cond.lengths
+        Tmax = cond.shape[2]
+    elif latent_condition:
         from .generation import LatentCondition
         cond = LatentCondition.concatenate(conds)
         lengths = cond.lengths
