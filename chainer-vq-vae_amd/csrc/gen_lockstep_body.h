@@ -575,7 +575,8 @@ inline SampledArgs smp_finish_args(const vqvae_gen_desc* d, const vqvae_gen_samp
 }
 
 // Embed, the residual blocks, proj1, proj2 of one step for 5..VQVAE_GEN_MAX_LOCKSTEP columns, each product launched
-// by `launch(args, stream)` (returns 0 or an error code): the logits of the step are in d->logits afterwards.
+// by `launch(args, stream)` (returns 0 or an error code): the logits of the step are in d->logits afterwards.  The
+// caller has asked gen_validate_blocks (gen_step.h) about the blocks.
 template <class Launch>
 int ls_step_products(const vqvae_gen_desc* d, Launch launch, hipStream_t st) {
   const int n = d->n, R = d->residual, half = d->dilated / 2;
@@ -595,9 +596,6 @@ int ls_step_products(const vqvae_gen_desc* d, Launch launch, hipStream_t st) {
   float* h_out = d->h1;
   for (int l = 0; l < d->n_blocks; ++l) {
     const vqvae_gen_block& bk = d->blocks[l];
-    VQ_REQUIRE(bk.conv_W && bk.conv_b && bk.res_W && bk.res_b && bk.skip_W && bk.skip_b && bk.ring && bk.dilation >= 1,
-               "gen_step: block %d incomplete", l);
-    VQ_REQUIRE(d->cond_dim == 0 || (bk.cond_W && bk.cond_b), "gen_step: block %d has no condition projection", l);
     LsGemmArgs c = base();
     c.epi = LS_EPI_GATE; c.W0 = bk.conv_W; c.b0 = bk.conv_b; c.rows0 = half; c.K = 2 * R;
     if (d->cond_dim) {

@@ -15,18 +15,12 @@
 // (step, sequence); a grid-stride loop over steps * n * ceil(n_uniform / 2) blocks; every store is to
 // out[(s * n + q) * n_uniform + j] with s < steps, q < n, j < n_uniform.  No LDS, no atomics.
 #include "gen_lockstep_body.h"
+#include "gen_step.h"
 #include "../../include/vqvae_gen_rng.h"
 
 #include <limits.h>
 
 namespace vq {
-
-int gen_validate_desc_rng(const vqvae_gen_desc* d);                 // generate.hip
-int ls_launch(const LsGemmArgs& g, hipStream_t st);                 // generate_lockstep.hip
-typedef int (*SlotsFinish)(const vqvae_gen_desc* d, const vqvae_gen_sampling* controls, const LsSlots& p, const void* ctx,
-                           hipStream_t st);
-int gen_step_slots_impl(const vqvae_gen_desc* d, const vqvae_gen_slots* slots, const vqvae_gen_sampling* s, const char* who,
-                        SlotsFinish finish, const void* ctx, hipStream_t st);   // generate_slots.hip
 
 constexpr int RNG_FILL_THREADS = 256;
 constexpr int RNG_FILL_MAX_BLOCKS = 4096;
@@ -72,16 +66,11 @@ __global__ __launch_bounds__(SMP_THREADS) void gen_rng_slots_sampled_finish_kern
   smp_finish_body(a, p, u);
 }
 
-__global__ __launch_bounds__(64) void gen_rng_advance_kernel(int* step, int max_steps) {
-  const int t = *step;
-  if (threadIdx.x == 0 && t < max_steps) *step = t + 1;
-}
+__global__ __launch_bounds__(64) void gen_rng_advance_kernel(int* step, int max_steps) { gen_advance(step, max_steps); }
 
 static LsPhiloxUniforms philox_of(const vqvae_gen_rng* rng) {
   return LsPhiloxUniforms{(unsigned long long)rng->seed, reinterpret_cast<const unsigned long long*>(rng->ids), 0};
 }
-
-static bool controls_of(const vqvae_gen_sampling* s) { return s && (s->temperature || s->top_k || s->top_p); }
 
 static int slots_finish_rng(const vqvae_gen_desc* d, const vqvae_gen_sampling* controls, const LsSlots& p, const void* ctx,
                             hipStream_t st) {
@@ -149,22 +138,17 @@ extern "C" int vqvae_sample_logits_rng(const float* logits, int n, int out_dim, 
 extern "C" int vqvae_wavenet_gen_step_rng(const vqvae_gen_desc* d, const vqvae_gen_sampling* s, const vqvae_gen_rng* rng,
                                           vqvae_stream_t stream) {
   VQ_REQUIRE(rng, "gen_step_rng: null rng");
-  const int bad = gen_validate_desc_rng(d);
+  int bad = gen_validate_desc_rng(d);
   if (bad != 0) return bad;
   VQ_REQUIRE(d->n > VQVAE_GEN_MAX_N, "gen_step_rng: d->n must be %d..%d sequences (got %d); for fewer fill an array with "
              "vqvae_gen_rng_fill", VQVAE_GEN_MAX_N + 1, VQVAE_GEN_MAX_LOCKSTEP, d->n);
   VQ_REQUIRE(d->sample_mode != VQVAE_GEN_NONE, "gen_step_rng: sample_mode VQVAE_GEN_NONE draws nothing: use vqvae_wavenet_gen_step");
-  const bool controls = controls_of(s);
+  const bool controls = gen_controls_set(s);
   VQ_REQUIRE(!controls || d->sample_mode != VQVAE_GEN_MOL || (!s->top_k && !s->top_p),
              "gen_step_rng: the mixture of logistics takes a temperature only (top_k and top_p must be NULL)");
   VQ_REQUIRE(d->sample_mode != VQVAE_GEN_SOFTMAX || d->out_dim <= (controls ? SMP_MAXOUT : LS_MAXOUT),
              "gen_step_rng: at most %d classes", controls ? SMP_MAXOUT : LS_MAXOUT);
-  for (int l = 0; l < d->n_blocks; ++l) {     // before the first launch, not between the launches
-    const vqvae_gen_block& bk = d->blocks[l];
-    VQ_REQUIRE(bk.conv_W && bk.conv_b && bk.res_W && bk.res_b && bk.skip_W && bk.skip_b && bk.ring && bk.dilation >= 1,
-               "gen_step_rng: block %d incomplete", l);
-    VQ_REQUIRE(d->cond_dim == 0 || (bk.cond_W && bk.cond_b), "gen_step_rng: block %d has no condition projection", l);
-  }
+  if ((bad = gen_validate_blocks(d, "gen_step_rng")) != 0) return bad;
   hipStream_t st = (hipStream_t)stream;
   const int rc = ls_step_products(d, ls_launch, st);
   if (rc != 0) return rc;

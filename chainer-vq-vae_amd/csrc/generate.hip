@@ -15,8 +15,7 @@
 // Weights are read in their Chainer layout (no packing); 15.8 MB of fp32 weights stay L2/MALL resident.
 #include <algorithm>
 
-#include "common.h"
-#include "../../include/vqvae_sampling.h"
+#include "gen_step.h"
 
 namespace vq {
 
@@ -262,9 +261,6 @@ __global__ __launch_bounds__(256) void gen_finish_kernel(GenFinishArgs a) {
   if (tid == 0) *a.step = t + 1;
 }
 
-int gen_step_lockstep(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st);   // generate_lockstep.hip: the batch in MFMA columns
-int gen_finish_sampled(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st);  // sampling.hip: finish + advance
-
 // What every step entry point rejects before it launches anything (generate_slots.hip asks the same of its descriptor).
 static int gen_validate_desc_impl(const vqvae_gen_desc* d, bool array_uniforms) {
   VQ_REQUIRE(d, "gen_step: null descriptor");
@@ -291,9 +287,10 @@ int gen_validate_desc_rng(const vqvae_gen_desc* d) { return gen_validate_desc_im
 // One step.  smp == nullptr: vqvae_wavenet_gen_step; else the sampling controls of include/vqvae_sampling.h, which
 // replace the finish launch and nothing else.
 int gen_step_impl(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st) {
-  const int bad = gen_validate_desc(d);
+  int bad = gen_validate_desc(d);
   if (bad != 0) return bad;
   if (d->n > GEN_NB) return gen_step_lockstep(d, smp, st);   // n <= 4: the kernels above, as before
+  if ((bad = gen_validate_blocks(d, "gen_step")) != 0) return bad;
   const int n = d->n, R = d->residual, half = d->dilated / 2;
 
   GenConvArgs e{};   // embed: pad-free 2-tap conv on [previous input, current input] (modules.py:234, 247-248)
@@ -306,9 +303,6 @@ int gen_step_impl(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStr
   float* h_out = d->h1;
   for (int l = 0; l < d->n_blocks; ++l) {
     const vqvae_gen_block& bk = d->blocks[l];
-    VQ_REQUIRE(bk.conv_W && bk.conv_b && bk.res_W && bk.res_b && bk.skip_W && bk.skip_b && bk.ring && bk.dilation >= 1,
-               "gen_step: block %d incomplete", l);
-    VQ_REQUIRE(d->cond_dim == 0 || (bk.cond_W && bk.cond_b), "gen_step: block %d has no condition projection", l);
     GenConvArgs c{};
     c.W = bk.conv_W; c.b = bk.conv_b; c.Wc = d->cond_dim ? bk.cond_W : nullptr; c.bc = bk.cond_b;
     c.x_old = bk.ring; c.x_new = h_in; c.cond = d->cond; c.cond_bstride = d->cond_bstride; c.cond_cstride = d->cond_cstride;

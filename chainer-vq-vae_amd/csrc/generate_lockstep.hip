@@ -20,6 +20,7 @@
 // The kernel bodies live in gen_lockstep_body.h, shared with the slot-table form of generate_slots.hip; here they are
 // instantiated with the identity policy (column c is sequence c at the global step).
 #include "gen_lockstep_body.h"
+#include "gen_step.h"
 
 namespace vq {
 
@@ -29,10 +30,7 @@ __global__ __launch_bounds__(LS_THREADS) void gen_lockstep_gemm_kernel(LsGemmArg
 // so it is advanced by a launch of its own after this one.
 __global__ __launch_bounds__(256) void gen_lockstep_finish_kernel(LsFinishArgs a) { ls_finish_body(a, LsIdentity{}); }
 
-__global__ __launch_bounds__(64) void gen_lockstep_advance_kernel(int* step, int max_steps) {
-  const int t = *step;
-  if (threadIdx.x == 0 && t < max_steps) *step = t + 1;
-}
+__global__ __launch_bounds__(64) void gen_lockstep_advance_kernel(int* step, int max_steps) { gen_advance(step, max_steps); }
 
 int ls_launch(const LsGemmArgs& g, hipStream_t st) {   // also the products of gen_rng.hip's step
   hipLaunchKernelGGL(gen_lockstep_gemm_kernel, ls_gemm_grid(g), dim3(LS_THREADS), 0, st, g);
@@ -43,12 +41,11 @@ int ls_launch(const LsGemmArgs& g, hipStream_t st) {   // also the products of g
 // One step for 5..VQVAE_GEN_MAX_LOCKSTEP sequences; vqvae_wavenet_gen_step (generate.hip) has validated the descriptor's
 // dimensions, head weights, state buffers and sampling fields.  smp != nullptr (include/vqvae_sampling.h): the filtered
 // sampler of sampling.hip takes the place of the finish and advance launches.
-int gen_finish_sampled(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st);
 int gen_step_lockstep(const vqvae_gen_desc* d, const vqvae_gen_sampling* smp, hipStream_t st) {
   VQ_REQUIRE(d->n >= 1 && d->n <= VQVAE_GEN_MAX_LOCKSTEP, "gen_step: n must be 1..%d sequences (got %d)", VQVAE_GEN_MAX_LOCKSTEP, d->n);
   VQ_REQUIRE(d->sample_mode != VQVAE_GEN_SOFTMAX || d->out_dim <= LS_MAXOUT, "gen_step: at most %d classes", LS_MAXOUT);
-  const int rc = ls_step_products(d, ls_launch, st);
-  if (rc != 0) return rc;
+  int rc = gen_validate_blocks(d, "gen_step");
+  if (rc != 0 || (rc = ls_step_products(d, ls_launch, st)) != 0) return rc;
 
   if (smp) return gen_finish_sampled(d, smp, st);
   if (d->sample_mode != VQVAE_GEN_NONE || d->logits_out) {

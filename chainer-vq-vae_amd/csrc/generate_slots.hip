@@ -13,11 +13,9 @@
 // counted with a ballot and take queue[next + rank] in slot order.  No atomics: one wave reads the table, every lane
 // writes its own two slots, lane 0 writes next / live / the tick, so the assignment is a pure function of the inputs.
 #include "gen_lockstep_body.h"
-#include "../../include/vqvae_gen_slots.h"
+#include "gen_step.h"
 
 namespace vq {
-
-int gen_validate_desc(const vqvae_gen_desc* d);   // generate.hip
 
 __global__ __launch_bounds__(LS_THREADS) void gen_slots_gemm_kernel(LsGemmArgs a, LsSlots p) { ls_gemm_body(a, p); }
 
@@ -137,27 +135,19 @@ extern "C" int vqvae_gen_slots_init(const vqvae_gen_desc* d, const vqvae_gen_slo
 // One tick.  finish == nullptr: the finishing kernels above read the descriptor's array of uniforms; else `finish`
 // launches the finishing kernel (gen_rng.hip: the uniforms drawn on the device; d->uniforms may then be null).
 namespace vq {
-int gen_validate_desc_rng(const vqvae_gen_desc* d);   // generate.hip
-typedef int (*SlotsFinish)(const vqvae_gen_desc* d, const vqvae_gen_sampling* controls, const LsSlots& p, const void* ctx,
-                           hipStream_t st);
 int gen_step_slots_impl(const vqvae_gen_desc* d, const vqvae_gen_slots* slots, const vqvae_gen_sampling* s, const char* who,
                         SlotsFinish finish, const void* ctx, hipStream_t st) {
   int bad = slots_validate(d, slots, who);
   if (bad != 0) return bad;
   if ((bad = finish ? gen_validate_desc_rng(d) : gen_validate_desc(d)) != 0) return bad;
-  const bool controls = s && (s->temperature || s->top_k || s->top_p);
+  const bool controls = gen_controls_set(s);
   VQ_REQUIRE(d->sample_mode != VQVAE_GEN_NONE || d->logits_out, "%s: sample_mode VQVAE_GEN_NONE needs logits_out", who);
   VQ_REQUIRE(!controls || d->sample_mode != VQVAE_GEN_NONE,
              "%s: sampling controls need sample_mode VQVAE_GEN_SOFTMAX or VQVAE_GEN_MOL", who);
   VQ_REQUIRE(!controls || d->sample_mode != VQVAE_GEN_MOL || (!s->top_k && !s->top_p),
              "%s: the mixture of logistics takes a temperature only (top_k and top_p must be NULL)", who);
   VQ_REQUIRE(d->sample_mode != VQVAE_GEN_SOFTMAX || d->out_dim <= LS_MAXOUT, "%s: at most %d classes", who, LS_MAXOUT);
-  for (int l = 0; l < d->n_blocks; ++l) {
-    const vqvae_gen_block& bk = d->blocks[l];
-    VQ_REQUIRE(bk.conv_W && bk.conv_b && bk.res_W && bk.res_b && bk.skip_W && bk.skip_b && bk.ring && bk.dilation >= 1,
-               "%s: block %d incomplete", who, l);
-    VQ_REQUIRE(d->cond_dim == 0 || (bk.cond_W && bk.cond_b), "%s: block %d has no condition projection", who, l);
-  }
+  if ((bad = gen_validate_blocks(d, who)) != 0) return bad;
   LsSlots p{};
   p.slot_seq = slots->slot_seq; p.slot_t = slots->slot_t; p.live_count = slots->live; p.steps = slots->steps;
   p.x_prev = d->x_prev; p.nseq = slots->n_seq;

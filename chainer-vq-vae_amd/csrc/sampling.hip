@@ -14,19 +14,13 @@
 // The kernel's body lives in gen_lockstep_body.h, shared with the slot-table form of generate_slots.hip; here it is
 // instantiated with the identity policy (workgroup b is sequence b at the global step).
 #include "gen_lockstep_body.h"
+#include "gen_step.h"
 
 namespace vq {
 
-int gen_step_impl(const vqvae_gen_desc* d, const vqvae_gen_sampling* s, hipStream_t st);   // generate.hip
-
 __global__ __launch_bounds__(SMP_THREADS) void gen_sampled_finish_kernel(SampledArgs a) { smp_finish_body(a, LsIdentity{}); }
 
-__global__ __launch_bounds__(64) void gen_sampled_advance_kernel(int* step, int max_steps) {
-  const int t = *step;
-  if (threadIdx.x == 0 && t < max_steps) *step = t + 1;
-}
-
-static bool smp_neutral(const vqvae_gen_sampling* s) { return !s || (!s->temperature && !s->top_k && !s->top_p); }
+__global__ __launch_bounds__(64) void gen_sampled_advance_kernel(int* step, int max_steps) { gen_advance(step, max_steps); }
 
 // The last two launches of a step with controls (called by gen_step_impl and gen_step_lockstep in place of their own
 // finish): the descriptor has been validated by then.
@@ -47,7 +41,7 @@ using namespace vq;
 extern "C" int vqvae_sampling_abi_version(void) { return 1; }
 
 extern "C" int vqvae_wavenet_gen_step_sampled(const vqvae_gen_desc* d, const vqvae_gen_sampling* s, vqvae_stream_t st) {
-  if (smp_neutral(s)) return vqvae_wavenet_gen_step(d, st);
+  if (!gen_controls_set(s)) return vqvae_wavenet_gen_step(d, st);
   VQ_REQUIRE(d, "gen_step_sampled: null descriptor");
   VQ_REQUIRE(d->sample_mode == VQVAE_GEN_SOFTMAX || d->sample_mode == VQVAE_GEN_MOL,
              "gen_step_sampled: sampling controls need sample_mode VQVAE_GEN_SOFTMAX or VQVAE_GEN_MOL");

@@ -69,6 +69,12 @@ def _upload_controls(sampling):
     return s, arrays
 
 
+def sampling_layout(mode, out_dim):
+    """(uniforms a step draws per sequence, dtype of a sample): one and an int32 class for the softmax output, nr_mix =
+    out_dim // 3 and a float32 value for the mixture of logistics."""
+    return (1, np.int32) if mode == _lib.GEN_SOFTMAX else (out_dim // 3, np.float32)
+
+
 # ---- the uniforms drawn on the device (include/vqvae_gen_rng.h, csrc/gen_rng.hip) -------------------------------------
 _U32 = np.uint64(0xFFFFFFFF)
 _SH32 = np.uint64(32)
@@ -198,28 +204,26 @@ def sample_logits(logits, uniforms, mode=_lib.GEN_SOFTMAX, temperature=None, top
     (vqvae_sample_logits_rng); with an array ``step`` is not read."""
     backend.require_device(logits)
     n, out_dim = logits.shape
-    softmax = mode == _lib.GEN_SOFTMAX
-    sampling = sampling_controls(n, temperature, top_k, top_p, not softmax, 'sample_logits')
+    n_uniform, dtype = sampling_layout(mode, out_dim)
+    sampling = sampling_controls(n, temperature, top_k, top_p, mode != _lib.GEN_SOFTMAX, 'sample_logits')
+    rng = None
     if isinstance(uniforms, DeviceUniforms):
         if not 0 <= int(step) <= _INT_MAX:
             raise ValueError('sample_logits: step must be in [0, 2**31), got %r' % (step,))
         rng, keep_ids = uniforms.upload(n, 'sample_logits')
-        out = backend.zeros((n,), np.int32 if softmax else np.float32)
-        probs = DeviceArray((n, out_dim), np.float32) if return_probs else None
-        s, keep = (None, None) if sampling is None else _upload_controls(sampling)
-        _lib.call('vqvae_sample_logits_rng', logits.ptr, n, out_dim, mode, float(log_scale_min), C.byref(rng), int(step),
-                  1 if softmax else max(out_dim // 3, 1), None if s is None else C.byref(s), out.ptr,
-                  None if probs is None else probs.ptr, _S())
-        backend.synchronize()                               # the ids and the control arrays go out of scope here
-        return (out, probs) if return_probs else out
-    u = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(n, -1)
-    u_dev = backend.to_device(u.reshape(-1))
-    out = backend.zeros((n,), np.int32 if softmax else np.float32)
+    else:
+        u = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(n, -1)
+        u_dev = backend.to_device(u.reshape(-1))
+    out = backend.zeros((n,), dtype)
     probs = DeviceArray((n, out_dim), np.float32) if return_probs else None
     s, keep = (None, None) if sampling is None else _upload_controls(sampling)
-    _lib.call('vqvae_sample_logits', logits.ptr, n, out_dim, mode, float(log_scale_min), u_dev.ptr, u.shape[1],
-              None if s is None else C.byref(s), out.ptr, None if probs is None else probs.ptr, _S())
-    backend.synchronize()                                   # u_dev and the control arrays go out of scope here
+    tail = (None if s is None else C.byref(s), out.ptr, None if probs is None else probs.ptr, _S())
+    if rng is not None:
+        _lib.call('vqvae_sample_logits_rng', logits.ptr, n, out_dim, mode, float(log_scale_min), C.byref(rng), int(step),
+                  max(n_uniform, 1), *tail)
+    else:
+        _lib.call('vqvae_sample_logits', logits.ptr, n, out_dim, mode, float(log_scale_min), u_dev.ptr, u.shape[1], *tail)
+    backend.synchronize()                  # the uniforms or the stream ids, and the control arrays, go out of scope here
     return (out, probs) if return_probs else out
 
 
@@ -427,6 +431,96 @@ def refuse_device_uniforms(uniforms, who):
                         % who)
 
 
+def _uniform_source(uniforms, n, columns, steps, n_uniform):
+    """The uniforms of ``n`` sequences that run ``steps`` steps in a state of ``columns`` columns, a host array or a
+    DeviceUniforms -> (the device array the descriptor points at or None, the GenRng the step draws from or None, what
+    the GenRng points to).  Up to 4 columns run the matrix-vector kernels or the persistent kernel, which read an array:
+    a DeviceUniforms fills it on the device (at most steps * 4 * n_uniform doubles) and the generator is dropped.  More
+    columns draw inside the step's finishing launch and have no array."""
+    count = steps * n * n_uniform
+    if isinstance(uniforms, DeviceUniforms):
+        rng, ids = uniforms.upload(n, 'generate_sequence' if columns <= _lib.GEN_MAX_N else 'generate_lockstep')
+        if columns > _lib.GEN_MAX_N:
+            return None, rng, ids
+        u_dev = DeviceArray((max(1, count),), np.float64)
+        _lib.call('vqvae_gen_rng_fill', C.byref(rng), 0, steps, n, n_uniform, u_dev.ptr, _S())
+        return u_dev, None, ids
+    u = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(-1)
+    if u.size < count:
+        raise ValueError('generate_sequence: need %d uniform doubles (steps, n, %d), got %d' % (count, n_uniform, u.size))
+    return backend.to_device(u[:max(1, count)]), None, None
+
+
+def step_launcher(d, smp=None, rng=None, table=None, lat=None):
+    """The callable that issues one step of the descriptor ``d`` on the main stream: the entry point that goes with the
+    sampling controls ``smp`` (GenSampling), the generator ``rng`` (GenRng) and the slot table ``table`` (GenSlots), each
+    None when absent, and, for a latent condition, the launch that computes the step's condition column (``lat``, a
+    GenLatentCond) in front of it.  The structs are read at every call."""
+    dp, sp, rp, tp = [None if s is None else C.byref(s) for s in (d, smp, rng, table)]
+    if table is not None and rng is not None:
+        name, args = 'vqvae_wavenet_gen_step_slots_rng', (dp, tp, sp, rp)
+    elif table is not None:
+        name, args = 'vqvae_wavenet_gen_step_slots', (dp, tp, sp)
+    elif rng is not None:
+        name, args = 'vqvae_wavenet_gen_step_rng', (dp, sp, rp)
+    elif smp is not None:
+        name, args = 'vqvae_wavenet_gen_step_sampled', (dp, sp)
+    else:
+        name, args = 'vqvae_wavenet_gen_step', (dp,)
+
+    def step():
+        if lat is not None:               # with a table: reads what vqvae_gen_slots_init or the previous tick's scheduler left
+            _lib.call('vqvae_gen_cond_column', C.byref(lat), dp, tp, _S())
+        _lib.call(name, *(args + (_S(),)))
+    return step
+
+
+class Replay(object):
+    """``steps`` calls of ``step`` on the main stream.  run(0) issues them eagerly (profilers, debugging); run(graph_steps)
+    captures per = min(graph_steps, steps) of them as a hipGraph and launches it ceil(steps / per) times, the surplus
+    steps being device no-ops; both synchronise.  launch() is one more launch of the graph, past the end a device
+    no-op; close() synchronises and destroys the graph, whatever happened before."""
+
+    def __init__(self, step, steps):
+        self.step, self.steps, self.graph = step, steps, None
+
+    def run(self, graph_steps=8):
+        if not graph_steps:
+            for _ in range(self.steps):
+                self.step()
+        elif self.steps:
+            per = max(1, min(int(graph_steps), self.steps))
+            graph = C.c_void_p()
+            _lib.call('vqvae_graph_capture_begin', _S())
+            try:
+                for _ in range(per):
+                    self.step()
+            finally:
+                _lib.call('vqvae_graph_capture_end', _S(), C.byref(graph))
+            self.graph = graph
+            for _ in range((self.steps + per - 1) // per):
+                self.launch()
+        backend.synchronize()
+
+    def launch(self):
+        _lib.call('vqvae_graph_launch', self.graph, _S())
+
+    def close(self):
+        graph, self.graph = self.graph, None
+        if graph is not None:
+            try:
+                backend.synchronize()
+            finally:
+                _lib.call('vqvae_graph_destroy', graph)
+
+
+def _check_persistent(ws, hint=''):
+    """The status word at the head of a persistent launch's workspace: non-zero when a bounded spin ran out."""
+    status = int(ws.flat_view(0, 1).get()[0])
+    if status:
+        raise RuntimeError('persistent generation kernel gave up waiting (status %d)%s' % (status, hint))
+
+
 class GenerationState(object):
     """Device state behind WaveNet.initialize(n): zero queues (modules.py:58-67, 232-244) as
     per-block rings of ``dilation`` slots, the 2-sample embed queue, the step counter."""
@@ -487,6 +581,27 @@ class GenerationState(object):
         d.sample_mode = _lib.GEN_NONE
         d.max_steps = _INT_MAX
         self.desc = d
+        self._bound = []
+
+    def bind(self, cond, uniforms, n_uniform, forced, out, logits_out, sample_mode, max_steps, keep=()):
+        """The per-run fields of the descriptor, written here and nowhere else; returns the descriptor.
+        ``cond``: the dense condition (rows, condition_dim, T), read at the sequence's step, or a column buffer
+        (rows, condition_dim) that a launch in front of the step fills.  ``uniforms``, ``forced``, ``out`` (rows, T) and
+        ``logits_out`` are device arrays or None.  The descriptor holds raw pointers: every array given, and whatever
+        ``keep`` lists besides (what the structs next to the descriptor point to), stays alive until the next bind."""
+        d = self.desc
+        if cond.ndim == 3:
+            Cc, T = cond.shape[1:]
+            d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = cond.ptr, Cc * T, T, 1
+        else:
+            d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = cond.ptr, cond.shape[1], 1, 0
+        d.uniforms, d.n_uniform = None if uniforms is None else uniforms.ptr, n_uniform
+        d.forced_next = None if forced is None else forced.ptr
+        d.out, d.out_bstride = (None, 0) if out is None else (out.ptr, out.shape[1])
+        d.logits_out = None if logits_out is None else logits_out.ptr
+        d.sample_mode, d.max_steps = sample_mode, max_steps
+        self._bound = [cond, uniforms, forced, out, logits_out] + list(keep)
+        return d
 
     # ---- reference-shaped single step: WaveNet.generate(x, condition) (modules.py:246-255) ----
     def step_logits(self, x, condition):
@@ -498,27 +613,21 @@ class GenerationState(object):
             raise ValueError('generate: condition must hold (n, condition_dim, 1, 1) = (%d, %d, 1, 1) '
                              'values, got %s' % (n, self.cond_dim, condition.shape))
         self.x_cur.copy_from(x)
-        d = self.desc
-        d.sample_mode = _lib.GEN_NONE
-        d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = condition.ptr, self.cond_dim, 1, 0
-        d.uniforms = d.forced_next = d.out = d.logits_out = None
-        d.max_steps = _INT_MAX
-        _lib.call('vqvae_wavenet_gen_step', C.byref(d), _S())
-        self._keep = (x, condition)
+        d = self.bind(condition.reshape(n, self.cond_dim), None, 1, None, None, None, _lib.GEN_NONE, _INT_MAX, keep=(x,))
+        step_launcher(d)()
         return self.logits.copy().reshape(n, self.out_dim, 1, 1)
 
     # ---- the whole loop of generate.py:105-145 on the device ----------------------------------
     def run(self, condition, uniforms, mode, n_steps=None, forced=None, return_logits=False,
             graph_steps=8, persistent=False, chunk=4096, sampling=None, col_seq=None):
         """``sampling``: None or the tuple of sampling_controls(n, ...).  With controls every step ends in the filtered
-        sampler of csrc/sampling.hip (vqvae_wavenet_gen_step_sampled) and ``persistent`` is not honoured: the persistent
-        kernel has no filtered form, the run is a replayed hipGraph of per-step launches.
+        sampler of csrc/sampling.hip and ``persistent`` is not honoured: the persistent kernel has no filtered form, the
+        run is a replayed hipGraph of per-step launches (step_launcher picks the entry point).
         ``condition`` may be a LatentCondition (per-step launches only): every step then starts with the launch that
-        computes its condition column (vqvae_gen_cond_column), and ``col_seq`` (n,) int32 on the device, or None for the
-        identity, says which of the object's sequences sits in which column.
-        ``uniforms`` may be a DeviceUniforms with one stream id per column: n <= 4 fills the array on the device
-        (vqvae_gen_rng_fill) and runs as with an array, more columns draw in the finishing launch
-        (vqvae_wavenet_gen_step_rng)."""
+        computes its condition column, and ``col_seq`` (n,) int32 on the device, or None for the identity, says which
+        of the object's sequences sits in which column.
+        ``uniforms`` may be a DeviceUniforms with one stream id per column: n <= 4 fills the array on the device and runs
+        as with an array, more columns draw in the finishing launch (_uniform_source)."""
         n = self.n
         latent = isinstance(condition, LatentCondition)
         if latent:
@@ -536,66 +645,24 @@ class GenerationState(object):
         steps = T - 1 if n_steps is None else int(n_steps)          # generate.py:105
         if not 0 <= steps <= T:
             raise ValueError('generate_sequence: n_steps must be in [0, %d]' % T)
-        softmax = mode == _lib.GEN_SOFTMAX
-        n_uniform = 1 if softmax else self.out_dim // 3
-        rng = None
-        if isinstance(uniforms, DeviceUniforms):
-            # n <= 4 runs the matrix-vector kernels or the persistent kernel, which read an array: it is filled on the
-            # device (at most steps * 4 * n_uniform doubles).  More sequences draw inside the step's finishing launch.
-            rng, self._rng_ids = uniforms.upload(n, 'generate_sequence' if n <= _lib.GEN_MAX_N else 'generate_lockstep')
-            u_dev = None
-            if n <= _lib.GEN_MAX_N:
-                u_dev = DeviceArray((max(1, steps * n * n_uniform),), np.float64)
-                _lib.call('vqvae_gen_rng_fill', C.byref(rng), 0, steps, n, n_uniform, u_dev.ptr, _S())
-                rng = None
-        else:
-            u = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(-1)
-            if u.size < steps * n * n_uniform:
-                raise ValueError('generate_sequence: need %d uniform doubles (steps, n, %d), got %d'
-                                 % (steps * n * n_uniform, n_uniform, u.size))
-            u_dev = backend.to_device(u[:max(1, steps * n * n_uniform)])
-        out = backend.zeros((n, T), np.int32 if softmax else np.float32)     # generate.py:103
-        forced_dev = None
-        if forced is not None:
-            forced_dev = backend.to_device(np.ascontiguousarray(
-                forced, dtype=np.int32 if softmax else np.float32).reshape(-1)[:steps * n])
+        n_uniform, dtype = sampling_layout(mode, self.out_dim)
+        u_dev, rng, ids = _uniform_source(uniforms, n, n, steps, n_uniform)
+        out = backend.zeros((n, T), dtype)                                   # generate.py:103
+        forced_dev = None if forced is None else backend.to_device(
+            np.ascontiguousarray(forced, dtype=dtype).reshape(-1)[:steps * n])
         logits_out = DeviceArray((max(steps, 1), n, self.out_dim), np.float32) if return_logits else None
-        d = self.desc
-        d.sample_mode = mode
+        cond, lat = condition, None
         if latent:
             # the step reads the compact column its first launch wrote: (n, cond_dim), unit stride, no time axis
-            self._column = backend.zeros((n, self.cond_dim), np.float32)
-            lat = condition.struct(self._column, col_seq)
-            d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = self._column.ptr, self.cond_dim, 1, 0
-        else:
-            d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = condition.ptr, self.cond_dim * T, T, 1
-        d.uniforms, d.n_uniform = None if u_dev is None else u_dev.ptr, n_uniform
-        d.forced_next = None if forced_dev is None else forced_dev.ptr
-        d.out, d.out_bstride = out.ptr, T
-        d.logits_out = None if logits_out is None else logits_out.ptr
+            cond = backend.zeros((n, self.cond_dim), np.float32)
+            lat = condition.struct(cond, col_seq)
         if int(self.step.get()[0]) != 0:
             raise RuntimeError('generate_sequence starts from fresh queues: call initialize(n) first')
-        d.max_steps = steps
-        smp = None
-        if sampling is not None:
-            smp, self._controls = _upload_controls(sampling)
+        smp, controls = (None, None) if sampling is None else _upload_controls(sampling)
+        d = self.bind(cond, u_dev, n_uniform, forced_dev, out, logits_out, mode, steps, keep=(condition, col_seq, ids, controls))
+        if smp is not None or rng is not None:
             persistent = False
-        if rng is not None:
-            persistent = False
-
-            def network_step():
-                _lib.call('vqvae_wavenet_gen_step_rng', C.byref(d), None if smp is None else C.byref(smp), C.byref(rng), _S())
-        elif smp is None:
-            def network_step():
-                _lib.call('vqvae_wavenet_gen_step', C.byref(d), _S())
-        else:
-            def network_step():
-                _lib.call('vqvae_wavenet_gen_step_sampled', C.byref(d), C.byref(smp), _S())
-        step = network_step
-        if latent:
-            def step():
-                _lib.call('vqvae_gen_cond_column', C.byref(lat), C.byref(d), None, _S())
-                network_step()
+        step = step_launcher(d, smp, rng, lat=lat)
         nbytes = 0
         if steps and persistent:
             # the library picks the width class (<= 256 or <= 512 channels per vector); shapes outside
@@ -609,31 +676,15 @@ class GenerationState(object):
                 _lib.call('vqvae_wavenet_gen_run', C.byref(d), t0, min(chunk, steps - t0), ws.ptr,
                           ws.nbytes, _S())
             backend.synchronize()
-            status = int(ws.flat_view(0, 1).get()[0])
             self._last_ws = ws
-            if status:
-                raise RuntimeError('persistent generation kernel gave up waiting (status %d): are all '
-                                   'its workgroups resident?' % status)
+            _check_persistent(ws, ': are all its workgroups resident?')
             self.step.set(np.array([steps], np.int32))
-        elif steps and not graph_steps:                # eager launches (profilers, debugging)
-            for _ in range(steps):
-                step()
-            backend.synchronize()
         elif steps:
-            per = max(1, min(int(graph_steps), steps))
-            graph = C.c_void_p()
-            _lib.call('vqvae_graph_capture_begin', _S())
+            replay = Replay(step, steps)
             try:
-                for _ in range(per):
-                    step()
+                replay.run(graph_steps)
             finally:
-                _lib.call('vqvae_graph_capture_end', _S(), C.byref(graph))
-            try:
-                for _ in range((steps + per - 1) // per):        # surplus steps are device no-ops
-                    _lib.call('vqvae_graph_launch', graph, _S())
-                backend.synchronize()
-            finally:
-                _lib.call('vqvae_graph_destroy', graph)
+                replay.close()
         d.max_steps = _INT_MAX
         return (out, logits_out) if return_logits else out
 
@@ -651,56 +702,50 @@ def run_many(wavenet, condition, uniforms, mode, n_steps=None, group=_lib.GEN_MA
         condition = condition.reshape(condition.shape[:3])
     N, Cc, T = condition.shape
     steps = T - 1 if n_steps is None else int(n_steps)
-    softmax = mode == _lib.GEN_SOFTMAX
     u = np.asarray(uniforms, np.float64)
     u = u.reshape(u.shape[0], N, -1)
     lib = _lib.load()
     jobs = []
     for g0 in range(0, N, group):
         n = min(group, N - g0)
-        st = GenerationState(wavenet, n)
-        d = st.desc
-        n_uniform = 1 if softmax else st.out_dim // 3
+        st = GenerationState(wavenet, n)                       # holds the descriptor and, after bind, what it points to
+        n_uniform, dtype = sampling_layout(mode, st.out_dim)
         if u.shape[0] < steps or u.shape[2] < n_uniform:
             raise ValueError('generate_batch: need (steps, N, %d) uniform doubles, got %s' % (n_uniform, u.shape))
         u_dev = backend.to_device(np.ascontiguousarray(u[:max(steps, 1), g0:g0 + n, :n_uniform]).reshape(-1))
-        out = backend.zeros((n, T), np.int32 if softmax else np.float32)
-        cview = condition.flat_view(g0 * Cc * T, n * Cc * T, (n, Cc, T))
-        d.sample_mode = mode
-        d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = cview.ptr, Cc * T, T, 1
-        d.uniforms, d.n_uniform = u_dev.ptr, n_uniform
-        d.forced_next = d.logits_out = None
-        d.out, d.out_bstride = out.ptr, T
-        d.max_steps = steps
+        out = backend.zeros((n, T), dtype)
+        d = st.bind(condition.flat_view(g0 * Cc * T, n * Cc * T, (n, Cc, T)), u_dev, n_uniform, None, out, None, mode, steps)
         nbytes = lib.vqvae_wavenet_gen_run_workspace_bytes(C.byref(d))
         if not nbytes:
             raise ValueError('persistent generation: ' + lib.vqvae_last_error_string().decode())
-        ws = DeviceArray((nbytes // 4 + 1,), np.int32)
-        jobs.append((st, d, out, ws, u_dev, cview))
+        jobs.append((st, out, DeviceArray((nbytes // 4 + 1,), np.int32)))
     backend.synchronize()                  # buffers above were prepared on the main stream
     # every workgroup of a launch must be resident at once (its waves wait for each other): the
     # library knows the width class's workgroup count and the kernel's occupancy on this device
-    resident = min(lib.vqvae_wavenet_gen_run_concurrency(C.byref(j[1])) for j in jobs)
+    resident = min(lib.vqvae_wavenet_gen_run_concurrency(C.byref(st.desc)) for st, _, _ in jobs)
     max_streams = max(1, min(max_streams, resident))
     for t0 in range(0, steps, chunk):
-        for i, (st, d, out, ws, _, _) in enumerate(jobs):
-            _lib.call('vqvae_wavenet_gen_run', C.byref(d), t0, min(chunk, steps - t0), ws.ptr, ws.nbytes,
+        for i, (st, out, ws) in enumerate(jobs):
+            _lib.call('vqvae_wavenet_gen_run', C.byref(st.desc), t0, min(chunk, steps - t0), ws.ptr, ws.nbytes,
                       backend.pool_stream(i % max_streams))
     backend.synchronize()
     res = []
-    for st, d, out, ws, _, _ in jobs:
-        status = int(ws.flat_view(0, 1).get()[0])
-        if status:
-            raise RuntimeError('persistent generation kernel gave up waiting (status %d)' % status)
+    for st, out, ws in jobs:
+        _check_persistent(ws)
         res.append(out.get())
     return np.concatenate(res, axis=0)
 
 
 class LockstepState(GenerationState):
-    """The same descriptor and buffers for 1..128 sequences: vqvae_wavenet_gen_step runs n > 4 on the lockstep
+    """The same descriptor and buffers for 1..128 sequences: the step entry points run n > 4 on the lockstep
     kernels (csrc/generate_lockstep.hip, the batch in MFMA columns).  The persistent kernel stays at n <= 4, so
     ``run`` is used with ``persistent=False``."""
     max_n = _lib.GEN_MAX_LOCKSTEP
+
+
+def _check_group(group):
+    if not _lib.GEN_MAX_N < group <= _lib.GEN_MAX_LOCKSTEP:
+        raise ValueError('generate_lockstep: group must be %d..%d, got %d' % (_lib.GEN_MAX_N + 1, _lib.GEN_MAX_LOCKSTEP, group))
 
 
 def plan_lockstep(N, T, lengths=None, n_steps=None, group=_lib.GEN_MAX_LOCKSTEP):
@@ -710,8 +755,7 @@ def plan_lockstep(N, T, lengths=None, n_steps=None, group=_lib.GEN_MAX_LOCKSTEP)
     ties in the caller's order) before they are cut into groups of <= ``group``, so that a group stops at its
     longest member; without, groups are consecutive slices.  A group of fewer than 5 is filled up to 5 with
     repeats of its last member."""
-    if not _lib.GEN_MAX_N < group <= _lib.GEN_MAX_LOCKSTEP:
-        raise ValueError('generate_lockstep: group must be %d..%d, got %d' % (_lib.GEN_MAX_N + 1, _lib.GEN_MAX_LOCKSTEP, group))
+    _check_group(group)
     if lengths is None:
         full = T - 1 if n_steps is None else int(n_steps)
         if not 0 <= full <= T:
@@ -739,35 +783,26 @@ def plan_lockstep(N, T, lengths=None, n_steps=None, group=_lib.GEN_MAX_LOCKSTEP)
     return steps, groups
 
 
-def _device_group_runner(wavenet, condition, mode, graph_steps, return_logits):
-    """One group of run_lockstep on the device: fresh LockstepState, the group's condition rows gathered into one
-    array, a replayed hipGraph of per-step launches on the main stream."""
+def _group_runner(wavenet, condition, mode, graph_steps, return_logits):
+    """One group of run_lockstep on the device: fresh LockstepState, a replayed hipGraph of per-step launches on the main
+    stream.  The group's rows of a dense condition are gathered into one array (a view when they are consecutive).  From
+    a LatentCondition no rows are gathered: the group's indices (repeats of the last member included) go to the device
+    as ``col_seq`` and every step computes its (n, condition_dim) column."""
     N, Cc, T = condition.shape
 
     def run_group(idx, u, forced, steps, sampling=None):
         n = len(idx)
-        if (np.diff(idx) == 1).all():
-            cview = condition.flat_view(int(idx[0]) * Cc * T, n * Cc * T, (n, Cc, T))
+        cond, col_seq = condition, None
+        if isinstance(condition, LatentCondition):
+            col_seq = backend.to_device(np.ascontiguousarray(idx, dtype=np.int32))
+        elif (np.diff(idx) == 1).all():
+            cond = condition.flat_view(int(idx[0]) * Cc * T, n * Cc * T, (n, Cc, T))
         else:
-            cview = DeviceArray((n, Cc, T), np.float32)
-            backend.copy_many([(cview.flat_view(j * Cc * T, Cc * T), condition.flat_view(int(i) * Cc * T, Cc * T))
+            cond = DeviceArray((n, Cc, T), np.float32)
+            backend.copy_many([(cond.flat_view(j * Cc * T, Cc * T), condition.flat_view(int(i) * Cc * T, Cc * T))
                                for j, i in enumerate(idx)])
-        st = LockstepState(wavenet, n)
-        res = st.run(cview, u, mode, steps, forced, return_logits, graph_steps, persistent=False, sampling=sampling)
-        if return_logits:
-            return res[0].get(), res[1].get()[:steps]
-        return res.get(), None
-    return run_group
-
-
-def _latent_group_runner(wavenet, condition, mode, graph_steps, return_logits):
-    """One group of run_lockstep from a LatentCondition: no condition rows are gathered; the group's indices (repeats of
-    the last member included) go to the device as ``col_seq`` and every step computes its (n, condition_dim) column."""
-    def run_group(idx, u, forced, steps, sampling=None):
-        st = LockstepState(wavenet, len(idx))
-        col_seq = backend.to_device(np.ascontiguousarray(idx, dtype=np.int32))
-        res = st.run(condition, u, mode, steps, forced, return_logits, graph_steps, persistent=False, sampling=sampling,
-                     col_seq=col_seq)
+        res = LockstepState(wavenet, n).run(cond, u, mode, steps, forced, return_logits, graph_steps, persistent=False,
+                                            sampling=sampling, col_seq=col_seq)
         if return_logits:
             return res[0].get(), res[1].get()[:steps]
         return res.get(), None
@@ -787,6 +822,38 @@ def _lockstep_uniforms(uniforms, N, T, max_steps, n_uniform):
     if u.shape[0] < max_steps or u.shape[2] < n_uniform:
         raise ValueError('generate_lockstep: need (%d, %d, %d) uniform doubles, got %s' % (max_steps, N, n_uniform, u.shape))
     return u
+
+
+def _lockstep_args(wavenet, condition, uniforms, mode, n_steps, lengths, forced, return_logits, group):
+    """The argument work of run_lockstep and run_lockstep_refill -> (condition (N, Cc, T), N, T, steps (N,), groups,
+    n_uniform, max_steps, the checked uniforms, the checked forced values (steps', N) or None, zeroed host ``out``
+    (N, T), zeroed host ``logits`` (max_steps, N, out_dim) or None)."""
+    if isinstance(condition, LatentCondition) and lengths is None:
+        lengths = condition.lengths
+    if condition.ndim == 4:
+        condition = condition.reshape(condition.shape[:3])
+    N, Cc, T = condition.shape
+    steps, groups = plan_lockstep(N, T, lengths, n_steps, group)
+    out_dim = wavenet.proj2.W.shape[0]
+    n_uniform, dtype = sampling_layout(mode, out_dim)
+    max_steps = int(steps.max()) if N else 0
+    u = _lockstep_uniforms(uniforms, N, T, max_steps, n_uniform)
+    if forced is not None:
+        forced = np.asarray(forced).reshape(-1, N)
+        if forced.shape[0] < max_steps:
+            raise ValueError('generate_lockstep: forced must be (steps, N) = (%d, %d), got %s' % (max_steps, N, forced.shape))
+    out = np.zeros((N, T), dtype)                                                # generate.py:103
+    logits = np.zeros((max_steps, N, out_dim), np.float32) if return_logits else None
+    return condition, N, T, steps, groups, n_uniform, max_steps, u, forced, out, logits
+
+
+def _scatter(out, logits, steps, idx, o, lg):
+    """Row j of a run's result ``o`` (and column j of its logits ``lg``) is sequence idx[j]: its own steps go to its row of
+    ``out``; what a sequence that kept running (or a stub) wrote past them is discarded."""
+    for j, i in enumerate(idx):
+        out[i, :steps[i]] = o[j, :steps[i]]
+        if logits is not None:
+            logits[:steps[i], i] = lg[:steps[i], j]
 
 
 def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None, forced=None, return_logits=False,
@@ -809,26 +876,9 @@ def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None,
     ``uniforms`` may be a DeviceUniforms: a group then gets the generator with its members' stream ids (gathered with the
     group's indices, repeats included) in place of an array, and the values are those of the call with
     ``uniforms.host(steps, n_uniform)``."""
-    latent = isinstance(condition, LatentCondition)
-    if latent and lengths is None:
-        lengths = condition.lengths
-    if condition.ndim == 4:
-        condition = condition.reshape(condition.shape[:3])
-    N, Cc, T = condition.shape
-    steps, groups = plan_lockstep(N, T, lengths, n_steps, group)
-    softmax = mode == _lib.GEN_SOFTMAX
-    out_dim = wavenet.proj2.W.shape[0]
-    n_uniform = 1 if softmax else out_dim // 3
-    max_steps = int(steps.max()) if N else 0
-    u = _lockstep_uniforms(uniforms, N, T, max_steps, n_uniform)
-    if forced is not None:
-        forced = np.asarray(forced).reshape(-1, N)
-        if forced.shape[0] < max_steps:
-            raise ValueError('generate_lockstep: forced must be (steps, N) = (%d, %d), got %s' % (max_steps, N, forced.shape))
-    run_group = _run_group or (_latent_group_runner if latent else _device_group_runner)(
-        wavenet, condition, mode, graph_steps, return_logits)
-    out = np.zeros((N, T), np.int32 if softmax else np.float32)                  # generate.py:103
-    logits = np.zeros((max_steps, N, out_dim), np.float32) if return_logits else None
+    condition, N, T, steps, groups, n_uniform, max_steps, u, forced, out, logits = _lockstep_args(
+        wavenet, condition, uniforms, mode, n_steps, lengths, forced, return_logits, group)
+    run_group = _run_group or _group_runner(wavenet, condition, mode, graph_steps, return_logits)
     for idx, gsteps in groups:
         # a DeviceUniforms has no (steps, n) array on either side: the group gets its members' stream ids
         ug = u.gather(idx) if isinstance(u, DeviceUniforms) else np.ascontiguousarray(u[:max(gsteps, 1), idx, :n_uniform])
@@ -837,10 +887,7 @@ def run_lockstep(wavenet, condition, uniforms, mode, n_steps=None, lengths=None,
             o, lg = run_group(idx, ug, fg, gsteps)
         else:
             o, lg = run_group(idx, ug, fg, gsteps, tuple(None if a is None else a[idx] for a in sampling))
-        for j, i in enumerate(idx):
-            out[i, :steps[i]] = o[j, :steps[i]]           # a shorter sequence kept running: its tail is discarded
-            if return_logits:
-                logits[:steps[i], i] = lg[:steps[i], j]
+        _scatter(out, logits, steps, idx, o, lg)          # a shorter sequence kept running: its tail is discarded
     return (out, logits) if return_logits else out
 
 
@@ -855,8 +902,7 @@ def refill_queue(steps):
 
 def refill_slots(n_queue, group=_lib.GEN_MAX_LOCKSTEP):
     """S = clamp(min(sequences to run, group), 5, 128): the slot count of a refilled run."""
-    if not _lib.GEN_MAX_N < group <= _lib.GEN_MAX_LOCKSTEP:
-        raise ValueError('generate_lockstep: group must be %d..%d, got %d' % (_lib.GEN_MAX_N + 1, _lib.GEN_MAX_LOCKSTEP, group))
+    _check_group(group)
     return max(_lib.GEN_MAX_N + 1, min(int(n_queue), int(group)))
 
 
@@ -913,89 +959,45 @@ class LockstepRefill(object):
         self.n_slots = S = refill_slots(len(queue), group)
         self.ticks, self.placement = plan_refill(steps, S)
         max_steps = int(steps.max())
-        softmax = mode == _lib.GEN_SOFTMAX
         st = self.state = LockstepState(wavenet, S)
-        self._rng = None
-        if isinstance(u, DeviceUniforms):                  # the (N,) stream ids, uploaded once; no array of uniforms
-            n_uniform = 1 if softmax else st.out_dim // 3
-            self._rng, u_dev = u.upload(N, 'generate_lockstep')
-        else:
+        n_uniform, dtype = sampling_layout(mode, st.out_dim)
+        if not isinstance(u, DeviceUniforms):
             n_uniform = u.shape[2]
-            u_dev = backend.to_device(np.ascontiguousarray(u[:max_steps]).reshape(-1))
-        self._keep = [condition, backend.to_device(steps), backend.to_device(queue), u_dev]
-        self.out = backend.zeros((N, T), np.int32 if softmax else np.float32)
+        u_dev, rng, ids = _uniform_source(u, N, S, max_steps, n_uniform)     # S > 4: a generator is kept, nothing is filled
+        steps_dev, queue_dev = backend.to_device(steps), backend.to_device(queue)
+        self.out = backend.zeros((N, T), dtype)
         self.logits_out = backend.zeros((max_steps, N, st.out_dim), np.float32) if return_logits else None
-        self.slot_seq = backend.zeros((S,), np.int32)
-        self.slot_t = backend.zeros((S,), np.int32)
-        self.next = backend.zeros((1,), np.int32)
-        self.live = backend.zeros((1,), np.int32)
+        self.slot_seq, self.slot_t = backend.zeros((S,), np.int32), backend.zeros((S,), np.int32)
+        self.next, self.live = backend.zeros((1,), np.int32), backend.zeros((1,), np.int32)
         self.started = backend.to_device(np.full((N, 2), -1, np.int32))
-        d = self.desc = st.desc
-        d.sample_mode = mode
-        self._lat = None
+        cond, lat = condition, None
         if isinstance(condition, LatentCondition):
             # rows are addressed by the sequence: (N, condition_dim); a tick's first launch writes the live slots' rows
-            self.column = backend.zeros((N, Cc), np.float32)
-            self._lat = condition.struct(self.column)
-            d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = self.column.ptr, Cc, 1, 0
-        else:
-            d.cond, d.cond_bstride, d.cond_cstride, d.cond_follows_step = condition.ptr, Cc * T, T, 1
-        d.uniforms, d.n_uniform = None if self._rng is not None else u_dev.ptr, n_uniform
-        d.forced_next = None
-        if forced is not None:
-            self._keep.append(backend.to_device(np.ascontiguousarray(
-                forced[:max_steps], dtype=np.int32 if softmax else np.float32).reshape(-1)))
-            d.forced_next = self._keep[-1].ptr
-        d.out, d.out_bstride = self.out.ptr, T
-        d.logits_out = None if self.logits_out is None else self.logits_out.ptr
-        d.max_steps = self.ticks
+            cond = self.column = backend.zeros((N, Cc), np.float32)
+            lat = condition.struct(self.column)
+        forced_dev = None if forced is None else backend.to_device(
+            np.ascontiguousarray(forced[:max_steps], dtype=dtype).reshape(-1))
+        smp, controls = (None, None) if sampling is None else _upload_controls(sampling)
+        d = self.desc = st.bind(cond, u_dev, n_uniform, forced_dev, self.out, self.logits_out, mode, self.ticks,
+                                keep=(condition, steps_dev, queue_dev, ids, controls))
         t = self.table = _lib.GenSlots()
-        t.n_seq, t.steps, t.queue, t.n_queue = N, self._keep[1].ptr, self._keep[2].ptr, len(queue)
+        t.n_seq, t.steps, t.queue, t.n_queue = N, steps_dev.ptr, queue_dev.ptr, len(queue)
         t.next, t.slot_seq, t.slot_t, t.live = self.next.ptr, self.slot_seq.ptr, self.slot_t.ptr, self.live.ptr
         t.started = self.started.ptr
-        self._smp = None
-        if sampling is not None:
-            self._smp, controls = _upload_controls(sampling)
-            self._keep.append(controls)
-        self._graph = None
+        self.tick = step_launcher(d, smp, rng, t, lat)
+        self._replay = Replay(self.tick, self.ticks)
         _lib.call('vqvae_gen_slots_init', C.byref(d), C.byref(t), _S())
-
-    def tick(self):
-        if self._lat is not None:         # reads the table vqvae_gen_slots_init or the previous tick's scheduler left behind
-            _lib.call('vqvae_gen_cond_column', C.byref(self._lat), C.byref(self.desc), C.byref(self.table), _S())
-        smp = None if self._smp is None else C.byref(self._smp)
-        if self._rng is not None:
-            _lib.call('vqvae_wavenet_gen_step_slots_rng', C.byref(self.desc), C.byref(self.table), smp, C.byref(self._rng), _S())
-        else:
-            _lib.call('vqvae_wavenet_gen_step_slots', C.byref(self.desc), C.byref(self.table), smp, _S())
 
     def replay(self):
         """One more launch of the captured graph (``graph_steps`` ticks); past the end a device no-op."""
-        _lib.call('vqvae_graph_launch', self._graph, _S())
+        self._replay.launch()
 
     def run(self, graph_steps=8):
-        if not graph_steps:
-            for _ in range(self.ticks):
-                self.tick()
-        elif self.ticks:
-            per = max(1, min(int(graph_steps), self.ticks))
-            self._graph = C.c_void_p()
-            _lib.call('vqvae_graph_capture_begin', _S())
-            try:
-                for _ in range(per):
-                    self.tick()
-            finally:
-                _lib.call('vqvae_graph_capture_end', _S(), C.byref(self._graph))
-            for _ in range((self.ticks + per - 1) // per):
-                self.replay()
-        backend.synchronize()
+        self._replay.run(graph_steps)
         return self
 
     def close(self):
-        if self._graph is not None:
-            backend.synchronize()
-            _lib.call('vqvae_graph_destroy', self._graph)
-            self._graph = None
+        self._replay.close()
 
 
 def _device_refill_runner(wavenet, condition, mode, graph_steps, group, return_logits):
@@ -1018,28 +1020,11 @@ def run_lockstep_refill(wavenet, condition, uniforms, mode, n_steps=None, length
     ``_run(steps, u, forced, sampling)`` -> (out (N, T), logits (max steps, N, out_dim) or None), both in the caller's
     order, stands in for the device in host tests; ``u`` is the (max steps, N, n_uniform) array or, when ``uniforms`` is a
     DeviceUniforms, that object with its (N,) stream ids spelled out."""
-    if isinstance(condition, LatentCondition) and lengths is None:
-        lengths = condition.lengths
-    if condition.ndim == 4:
-        condition = condition.reshape(condition.shape[:3])
-    N, Cc, T = condition.shape
-    steps, _ = plan_lockstep(N, T, lengths, n_steps, group)              # the same step counts and argument errors
-    softmax = mode == _lib.GEN_SOFTMAX
-    out_dim = wavenet.proj2.W.shape[0]
-    n_uniform = 1 if softmax else out_dim // 3
-    max_steps = int(steps.max()) if N else 0
-    u = _lockstep_uniforms(uniforms, N, T, max_steps, n_uniform)
-    if forced is not None:
-        forced = np.asarray(forced).reshape(-1, N)
-        if forced.shape[0] < max_steps:
-            raise ValueError('generate_lockstep: forced must be (steps, N) = (%d, %d), got %s' % (max_steps, N, forced.shape))
-    out = np.zeros((N, T), np.int32 if softmax else np.float32)                  # generate.py:103
-    logits = np.zeros((max_steps, N, out_dim), np.float32) if return_logits else None
+    # the same step counts and argument errors as run_lockstep; its groups are not used
+    condition, N, T, steps, _, n_uniform, max_steps, u, forced, out, logits = _lockstep_args(
+        wavenet, condition, uniforms, mode, n_steps, lengths, forced, return_logits, group)
     if max_steps:
         run = _run or _device_refill_runner(wavenet, condition, mode, graph_steps, group, return_logits)
         o, lg = run(steps, u if isinstance(u, DeviceUniforms) else u[:max_steps, :, :n_uniform], forced, sampling)
-        for i in range(N):                        # the device wrote nothing past a sequence's own steps; a stub may have
-            out[i, :steps[i]] = o[i, :steps[i]]
-            if return_logits:
-                logits[:steps[i], i] = lg[:steps[i], i]
+        _scatter(out, logits, steps, range(N), o, lg)   # the device wrote nothing past a sequence's own steps; a stub may have
     return (out, logits) if return_logits else out

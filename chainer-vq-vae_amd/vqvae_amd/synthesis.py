@@ -20,6 +20,18 @@ def _latent_condition(cond, condition_embed):
     return LatentCondition.from_condition(cond, condition_embed.local_embed5.W.shape[0], condition_embed.upscale_factor)
 
 
+def _draw_uniforms(rng, decoder, use_logistic, steps, n):
+    """The uniforms of ``steps`` steps of ``n`` sequences as generate.py draws them, (steps, n[, nr_mix]) host doubles; a
+    DeviceUniforms is passed through: its numbers are drawn on the device, where they are consumed, and no array
+    exists on either side."""
+    from .generation import DeviceUniforms
+    if isinstance(rng, DeviceUniforms):
+        return rng
+    if use_logistic:
+        return rng.uniform(0, 1, (max(steps, 1), n, decoder.proj2.W.shape[0] // 3))     # generate.py:117
+    return rng.random_sample((max(steps, 1), n))                     # inside numpy.random.choice, generate.py:136
+
+
 def synthesize(encoder, vq, decoder, condition_embed, x_enc, global_condition, rng=None,
                quantize=256, use_logistic=False, n_steps=None, persistent=True, lockstep=False,
                temperature=None, top_k=None, top_p=None, latent_condition=False):
@@ -46,7 +58,6 @@ def synthesize(encoder, vq, decoder, condition_embed, x_enc, global_condition, r
         (mu-law expanded for the softmax output), output = the raw sampled bins / values."""
     if latent_condition and not lockstep:
         raise ValueError('synthesize: latent_condition needs lockstep=True (generate_sequence reads the full-rate condition)')
-    from .generation import DeviceUniforms
     rng = np.random.RandomState() if rng is None else rng
     xd = x_enc if backend.is_device(x_enc) else backend.to_device(np.asarray(x_enc, np.float32))
     gd = global_condition if backend.is_device(global_condition) else \
@@ -59,13 +70,7 @@ def synthesize(encoder, vq, decoder, condition_embed, x_enc, global_condition, r
     cond = _latent_condition(condition.data, condition_embed) if latent_condition else condition.data
     T = cond.shape[2]
     steps = T - 1 if n_steps is None else n_steps                   # generate.py:105
-    nr_mix = decoder.proj2.W.shape[0] // 3
-    if isinstance(rng, DeviceUniforms):
-        u = rng                                                      # drawn on the device, where it is consumed
-    elif use_logistic:
-        u = rng.uniform(0, 1, (max(steps, 1), n, nr_mix))            # generate.py:117
-    else:
-        u = rng.random_sample((max(steps, 1), n))                    # inside numpy.random.choice, generate.py:136
+    u = _draw_uniforms(rng, decoder, use_logistic, steps, n)
     if lockstep:
         out = decoder.generate_lockstep(cond, u, n_steps=steps, temperature=temperature, top_k=top_k, top_p=top_p)
     else:
@@ -109,7 +114,6 @@ def synthesize_many(encoder, vq, decoder, condition_embed, waves, global_conditi
         False: the call without it launches exactly what it launched before.
     Returns the list of N host waves, utterance i of its own length T_i, as synthesize returns them (mu-law expanded
     for the softmax output); with ``return_output`` the list of (wave, output) pairs."""
-    from .generation import DeviceUniforms
     rng = np.random.RandomState() if rng is None else rng
     N = len(waves)
     speakers = np.asarray(global_condition.get() if backend.is_device(global_condition) else global_condition,
@@ -144,13 +148,7 @@ def synthesize_many(encoder, vq, decoder, condition_embed, waves, global_conditi
         backend.copy_many([(cond.flat_view((i * Cc + ch) * Tmax, int(L)), c.flat_view(ch * int(L), int(L)))
                            for i, (c, L) in enumerate(zip(conds, lengths)) for ch in range(Cc)])
     steps = Tmax - 1 if n_steps is None else n_steps
-    nr_mix = decoder.proj2.W.shape[0] // 3
-    if isinstance(rng, DeviceUniforms):
-        u = rng                                                      # no (Tmax - 1, N[, nr_mix]) array on either side
-    elif use_logistic:
-        u = rng.uniform(0, 1, (max(steps, 1), N, nr_mix))            # generate.py:117
-    else:
-        u = rng.random_sample((max(steps, 1), N))                    # inside numpy.random.choice, generate.py:136
+    u = _draw_uniforms(rng, decoder, use_logistic, steps, N)
     out = decoder.generate_lockstep(cond, u, n_steps=n_steps, lengths=lengths, group=group, refill=refill,
                                     temperature=temperature, top_k=top_k, top_p=top_p)
     wave = out if use_logistic else MuLaw(quantize).itransform(out)

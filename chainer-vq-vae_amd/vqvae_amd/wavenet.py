@@ -932,13 +932,19 @@ class WaveNet(Chain):
                                'WaveNet.initialize(n): call initialize(n) again')
         return st
 
+    def _gen_args(self, condition):
+        """(the condition's array or LatentCondition, the sample mode of this decoder's output) for the generate_* calls."""
+        from .core import Variable
+        return (condition.data if isinstance(condition, Variable) else condition,
+                _lib.GEN_MOL if self.use_logistic else _lib.GEN_SOFTMAX)
+
     def generate(self, x, condition):
         """modules.py:246-255: one step.  x (n, input_dim, 1, 1), condition (n, condition_dim, 1, 1)
         -> logits Variable (n, out_dim, 1, 1); the queues advance by one sample."""
         from .core import Variable
         from .generation import refuse_latent
         xd = x.data if isinstance(x, Variable) else x
-        cd = condition.data if isinstance(condition, Variable) else condition
+        cd, _ = self._gen_args(condition)
         refuse_latent(cd, 'generate')
         backend.require_device(xd, cd)
         return Variable(self._gen_state().step_logits(xd, cd))
@@ -970,14 +976,12 @@ class WaveNet(Chain):
         host draws and uploads nothing.  The kernels of this call (n <= 4) keep reading an array, so it is filled on the
         device first, (steps, n[, nr_mix]) doubles; every other argument means what it means with an array, and the
         result is that of the call with ``uniforms.host(steps, n_uniform)``, bit for bit."""
-        from .core import Variable
         from .generation import refuse_latent, sampling_controls
-        cd = condition.data if isinstance(condition, Variable) else condition
+        cd, mode = self._gen_args(condition)
         refuse_latent(cd, 'generate_sequence')
         sampling = sampling_controls(cd.shape[0], temperature, top_k, top_p, self.use_logistic, 'generate_sequence')
         backend.require_device(cd)
         self.initialize(cd.shape[0])
-        mode = _lib.GEN_MOL if self.use_logistic else _lib.GEN_SOFTMAX
         return self._gen_state().run(cd, uniforms, mode, n_steps, forced, return_logits, graph_steps,
                                      persistent, sampling=sampling)
 
@@ -991,16 +995,14 @@ class WaveNet(Chain):
         ``top_p`` is a ValueError; generate_lockstep takes them.  So is a generation.LatentCondition a TypeError: the
         persistent launches read the dense tensor (``.dense()``); generate_lockstep takes the latent form.  And so is a
         DeviceUniforms: the persistent launches read an array (``.host(...)``); generate_lockstep draws on the device."""
-        from .core import Variable
         from .generation import refuse_device_uniforms, refuse_latent, run_many
-        refuse_latent(condition.data if isinstance(condition, Variable) else condition, 'generate_batch')
+        cd, mode = self._gen_args(condition)
+        refuse_latent(cd, 'generate_batch')
         refuse_device_uniforms(uniforms, 'generate_batch')
         if temperature is not None or top_k is not None or top_p is not None:
             raise ValueError('generate_batch runs persistent launches only, which have no sampling controls: '
                              'use generate_lockstep (any number of sequences) or generate_sequence (n <= 4)')
-        cd = condition.data if isinstance(condition, Variable) else condition
         backend.require_device(cd)
-        mode = _lib.GEN_MOL if self.use_logistic else _lib.GEN_SOFTMAX
         return run_many(self, cd, uniforms, mode, n_steps, group, max_streams)
 
     def generate_lockstep(self, condition, uniforms, n_steps=None, lengths=None, forced=None, return_logits=False,
@@ -1031,15 +1033,10 @@ class WaveNet(Chain):
         stream ids (default arange(N)).  Sequence i's values then depend on (seed, stream_ids[i]), its own condition and
         the model alone: not on N, on ``group``, on ``refill``, on its position or on the other lengths.  The result is
         that of the call with ``uniforms.host(steps, n_uniform)``, bit for bit.  ``out`` (N, T) and ``forced`` stay dense."""
-        from .core import Variable
         from .generation import LatentCondition, run_lockstep, run_lockstep_refill, sampling_controls
-        cd = condition.data if isinstance(condition, Variable) else condition
+        cd, mode = self._gen_args(condition)
         sampling = sampling_controls(cd.shape[0], temperature, top_k, top_p, self.use_logistic, 'generate_lockstep')
         if not isinstance(cd, LatentCondition):
             backend.require_device(cd)
-        mode = _lib.GEN_MOL if self.use_logistic else _lib.GEN_SOFTMAX
-        if refill:
-            return run_lockstep_refill(self, cd, uniforms, mode, n_steps, lengths, forced, return_logits, graph_steps,
-                                       group, sampling=sampling)
-        return run_lockstep(self, cd, uniforms, mode, n_steps, lengths, forced, return_logits, graph_steps, group,
-                            sampling=sampling)
+        return (run_lockstep_refill if refill else run_lockstep)(
+            self, cd, uniforms, mode, n_steps, lengths, forced, return_logits, graph_steps, group, sampling=sampling)
