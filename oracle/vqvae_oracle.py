@@ -29,6 +29,16 @@ Parity pin status
   the same operators (tests/test_oracle_torch.py): **parity unpinned** for these
   parts -- no vector produced by Chainer itself exists to pin them on.
 
+* The COMPOSITION of these parts (``vae_forward`` / ``vae_backward`` /
+  ``train_step``'s gradient bookkeeping, ``ema_update``, ``mol_loss_*``,
+  ``wavenet_initialize`` / ``wavenet_generate_step``, ``flatten_params``' names):
+  PINNED against fixtures computed by the reference's own ``net.py``,
+  ``WaveNet/modules.py``, ``updaters.py`` and ``utils.py`` running unmodified on a
+  Chainer stand-in over torch float64 (``tests/golden/make_golden_model.py`` ->
+  ``tests/golden/ref_*.npz``; tests/test_host_reference_model.py).  The stand-in
+  maps each Chainer primitive onto a torch operator, so the primitives themselves
+  stay as the previous item says.
+
 All functions are dtype-generic (float32 for parity, float64 for gradient
 checks).  Internal layout is (B, C, T); the Chainer boundary layout (B, C, T, 1)
 is handled by ``squeeze4``/``expand4``.

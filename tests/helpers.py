@@ -37,6 +37,38 @@ MOL = dict(d=32, k=64, n_loop=4, n_layer=7, filter_size=2, input_dim=1, residual
            dilated=64, skip=64, out_dim=30, local_dim=32, global_dim=32, n_speaker=7)   # 28 blocks
 
 
+MOL_SHALLOW = dict(MOL, n_loop=1, n_layer=4)          # the MoL model of tests/golden/ref_model_mol.npz
+
+
+def named_tweak(name):
+    """The parameter tweaks the reference-model fixtures record by NAME (tests/golden/make_golden_model.py
+    and the tests that replay them): 'none'; 'mol_output' (test_mol_deep_stack_matches_oracle's trained-like
+    output layer); 'biases:<seed>' (every decoder bias 0.1 N(0, 1), so that no bias term is a silent zero);
+    several joined by '+'."""
+    def one(part, P):
+        if part == 'none':
+            return
+        if part == 'mol_output':
+            W, b = P['decoder']['proj2']
+            W[10:20] *= 30.0          # means spread over the sample range
+            b[20:30] = 2.5            # log-scales ~ 2.5 -> inv_std ~ 0.08
+            return
+        kind, seed = part.split(':')
+        assert kind == 'biases', part
+        rs = np.random.RandomState(int(seed))
+        dec = P['decoder']
+        for key in ('embed', 'proj1', 'proj2'):
+            dec[key][1][...] += (0.1 * rs.standard_normal(dec[key][1].shape)).astype(dec[key][1].dtype)
+        for blk in dec['blocks']:
+            for key in ('conv', 'condition_proj', 'res', 'skip'):
+                blk[key][1][...] += (0.1 * rs.standard_normal(blk[key][1].shape)).astype(blk[key][1].dtype)
+
+    def tweak(P):
+        for part in name.split('+'):
+            one(part, P)
+    return tweak
+
+
 def build_model(cfg, seed=0, ema_decay=None, use_logistic=False, tweak=None):
     """Builds (oracle params P, device model) with IDENTICAL initial weights."""
     import vqvae_amd as V
