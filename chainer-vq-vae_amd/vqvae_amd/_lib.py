@@ -103,6 +103,11 @@ class RaggedConvDesc(C.Structure):
                [('ttot_out', C.c_int64), ('x_cstride', C.c_int64)]
 
 
+class MetricsDesc(C.Structure):
+    """vqvae_metrics_desc (include/vqvae_metrics.h): one STFT / log-mel / distance call over a ragged list."""
+    _fields_ = [(n, C.c_int32) for n in ('n', 'n_fft', 'hop', 'n_mels', 'n_mcep')] + [('floor', c_float), ('ftot', C.c_int64), ('stride', C.c_int64)]
+
+
 # name -> (restype, argtypes); this table IS the list of symbols the header declares
 PROTOTYPES = {
     'vqvae_last_error_string': (c_char_p, []),
@@ -373,6 +378,20 @@ RAGGED_PROTOTYPES = {
 }
 RAGGED_ABI_VERSION = 1            # vqvae_ragged_abi_version()
 
+# include/vqvae_metrics.h: ragged STFT, log-mel and the per-utterance distances, a thirteenth table and version
+METRICS_PROTOTYPES = {
+    'vqvae_metrics_abi_version': (c_int, []),
+    'vqvae_metrics_stft_mel_workspace_bytes': (c_size_t, [C.POINTER(MetricsDesc)]),
+    'vqvae_metrics_distances_workspace_bytes': (c_size_t, [C.POINTER(MetricsDesc)]),
+    'vqvae_metrics_stft_mel': (c_int, [C.POINTER(MetricsDesc), P, P, P, P, P, P, P, P, P, c_size_t, P]),
+    'vqvae_metrics_distances': (c_int, [C.POINTER(MetricsDesc), P, P, P, P, P, P, P, P, c_size_t, P]),
+}
+METRICS_ABI_VERSION = 1           # vqvae_metrics_abi_version()
+METRICS_TILE = 32                 # VQVAE_METRICS_TILE
+METRICS_THREADS = 256             # VQVAE_METRICS_THREADS
+METRICS_MAX_NFFT = 2048           # VQVAE_METRICS_MAX_NFFT
+METRICS_MAX_MELS = 128            # VQVAE_METRICS_MAX_MELS
+
 # elementwise op codes / profiler tags (mirror the header)
 MAX_STACK_GROUP = 24              # blocks per resstack call (MAXSEG in csrc/gemm_common.h)
 STORE_X_BF16, STORE_RES_BF16 = 2, 4
@@ -417,7 +436,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES, KMEANS_PROTOTYPES, OPTIM_PROTOTYPES,
                   SAMPLING_PROTOTYPES, GEN_SLOTS_PROTOTYPES, GEN_COND_PROTOTYPES, GEN_RNG_PROTOTYPES,
-                  CORPUS_PROTOTYPES, INGEST_PROTOTYPES, RAGGED_PROTOTYPES):
+                  CORPUS_PROTOTYPES, INGEST_PROTOTYPES, RAGGED_PROTOTYPES, METRICS_PROTOTYPES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)           # AttributeError if the symbol is missing
             fn.restype = res
@@ -458,6 +477,9 @@ def load():
     if lib.vqvae_ragged_abi_version() != RAGGED_ABI_VERSION:
         raise ImportError('libvqvae_hip.so at %s has ragged-front-end ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
                           % (LIB_PATH, lib.vqvae_ragged_abi_version(), RAGGED_ABI_VERSION))
+    if lib.vqvae_metrics_abi_version() != METRICS_ABI_VERSION:
+        raise ImportError('libvqvae_hip.so at %s has audio-metrics ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
+                          % (LIB_PATH, lib.vqvae_metrics_abi_version(), METRICS_ABI_VERSION))
     _lib = lib
     return lib
 
