@@ -29,6 +29,7 @@
 // Every address is formed in 64 bits.  Stores: log_mel[m * stride + f] (and mel_pw) for m < n_mels, mag[b * stride + f] for b < nb, both for
 // f < ftot only; out[3 i + 0 .. 2]; plain vector stores.
 #include "common.h"
+#include "ragged_seg.h"
 #include "../../include/vqvae_metrics.h"
 
 namespace vq {
@@ -50,16 +51,6 @@ struct StftArgs {
 // where sample s of a staged tile is kept (see above); monotonic, so the image of [0, len) ends at mt_skew(len - 1)
 __host__ __device__ __forceinline__ int mt_skew(int s) { return s + (s >> 5) + (s >> 10); }
 
-// the utterance of frame f: the largest i with frame_off[i] <= f (frame_off ascending from 0)
-__device__ __forceinline__ int mt_find_utterance(const int64_t* frame_off, int n, long long f) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if ((long long)frame_off[mid] <= f) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 static size_t mt_lds_direct(int nb) { return (size_t)MT_TILE * (sizeof(long long) + sizeof(int)) + (size_t)nb * MT_TILE * sizeof(float); }
 static size_t mt_lds_staged(int n_fft, int hop, int nb) {
   return mt_lds_direct(nb) + ((size_t)mt_skew(n_fft + (MT_TILE - 1) * hop - 1) + 1) * sizeof(float);
@@ -78,7 +69,7 @@ __global__ __launch_bounds__(MT_THREADS) void metrics_stft_mel_kernel(StftArgs a
   const int nv = left < MT_TILE ? (int)left : MT_TILE;         // frames of this tile, >= 1
   if (tid < MT_TILE) {
     const long long f = f0 + (tid < nv ? tid : nv - 1);        // a column past the end repeats the last frame: computed, never stored
-    const int i = mt_find_utterance(a.frame_off, a.n, f);
+    const int i = ragged_find_segment(a.frame_off, a.n, f);      // the utterance of frame f
     s_g[tid] = (long long)a.off_in[i] + (f - (long long)a.frame_off[i]) * a.hop;
     s_utt[tid] = i;
   }

@@ -29,6 +29,7 @@
 // Every address is formed in 64 bits.  Stores: y[m * ttot_out + j] (ragged) or y[cout * off_out[i] + m * len_out[i] + jl]
 // (blocked) for m < cout and j < ttot_out only; plain vector stores.
 #include "gemm_common.h"
+#include "ragged_seg.h"
 #include "../../include/vqvae_ragged.h"
 
 namespace vq {
@@ -45,16 +46,6 @@ struct RaggedArgs {
   long long ttot_out, x_cstride;
   int n, cin, cout, K, stride, pad, dil, relu, blocked;
 };
-
-// the segment of output column j: the largest i with off_out[i] <= j (off_out ascending from 0)
-__device__ __forceinline__ int ragged_find_segment(const int64_t* off_out, int n, long long j) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if ((long long)off_out[mid] <= j) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // T2 = 1: 64 x 64 tiles, a wave one 32 x 32 accumulator; T2 = 2: 128 x 128 tiles, a wave a 2 x 2 block of them (rows
 // wm * 32 + 64 mi, columns wn * 32 + 64 ni), so that a fragment split once serves two products and a staged word twice the

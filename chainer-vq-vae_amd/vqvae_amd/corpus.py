@@ -13,7 +13,7 @@ import operator
 
 import numpy as np
 
-from . import _lib, backend
+from . import _lib, backend, ragged
 from .backend import DeviceArray
 from .generation import philox4x32_10
 from .inputs import IndexInput, StreamingInputIterator, _Pinned, mulaw_thresholds, peak_normalise
@@ -207,7 +207,7 @@ class ResidentCorpus(_Utterances):
     def _describe(self, lengths, speakers):
         self.corpus = self
         self.lengths, self.speakers = lengths, speakers
-        self.offsets = np.concatenate(([0], np.cumsum(lengths[:-1], dtype=np.int64))).astype(np.int64)
+        self.offsets = ragged.offsets(lengths)
         self.utterances = np.arange(len(lengths), dtype=np.int32)
         self._view_dev = None
 

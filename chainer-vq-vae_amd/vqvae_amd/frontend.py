@@ -16,7 +16,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, backend, core
+from . import _lib, backend, core, ragged
 from .backend import DeviceArray
 
 _S = backend.stream
@@ -52,18 +52,10 @@ def plan_chunks(lengths, widths, chunk_bytes):
     if int(chunk_bytes) < 1:
         raise ValueError('plan_chunks: chunk_bytes must be positive, got %r' % (chunk_bytes,))
     per = stage_lengths(lengths, len(widths) - 1) * np.asarray(widths, np.int64)[:, None]     # elements per (stage, utterance)
-    chunks, start, run = [], 0, np.zeros(len(widths), np.int64)
-    for u in range(len(lengths)):
-        if per[:, u].max() >= _CAP:
-            raise ValueError('plan_chunks: utterance %d (%d samples) alone reaches 2^31 elements in one stage' % (u, lengths[u]))
-        new = run + per[:, u]
-        if u > start and (4 * new.max() > int(chunk_bytes) or new.max() >= _CAP):
-            chunks.append((start, u))
-            start, new = u, per[:, u].copy()
-        run = new
-    if len(lengths) > start:
-        chunks.append((start, len(lengths)))
-    return chunks
+    if (per >= _CAP).any():
+        u = int(np.nonzero((per >= _CAP).any(axis=0))[0][0])
+        raise ValueError('plan_chunks: utterance %d (%d samples) alone reaches 2^31 elements in one stage' % (u, lengths[u]))
+    return ragged.plan_runs(per, chunk_bytes, cap=_CAP)
 
 
 class LatentCodes(object):
@@ -74,11 +66,8 @@ class LatentCodes(object):
     uploaded when the device buffer is first asked for."""
 
     def __init__(self, tl, indices, k):
-        tl = np.asarray(tl)
-        if tl.ndim != 1 or tl.size == 0 or tl.dtype.kind not in 'iu' or (tl < 1).any():
-            raise ValueError('LatentCodes: tl must be (N,) latent lengths >= 1 with N >= 1, got %r' % (tl,))
-        self.tl = tl.astype(np.int32)
-        self.offsets = np.concatenate([[0], np.cumsum(self.tl, dtype=np.int64)]).astype(np.int64)
+        self.tl = ragged.check_lengths(tl, 'LatentCodes').astype(np.int32)
+        self.offsets = ragged.offsets(self.tl, total=True)
         self.k = int(k)
         if self.k < 1:
             raise ValueError('LatentCodes: k must be at least 1, got %r' % (k,))
@@ -119,8 +108,7 @@ class LatentCodes(object):
 
     def to_host(self):
         """List of N int32 host arrays (one device-to-host copy, kept)."""
-        flat = self._flat()
-        return [flat[int(a):int(b)].copy() for a, b in zip(self.offsets[:-1], self.offsets[1:])]
+        return ragged.split(self._flat(), self.offsets)
 
     @staticmethod
     def _path(path):
@@ -226,8 +214,7 @@ class _Tables(object):
         L = np.asarray(per_stage_lengths, np.int64)
         S, n = L.shape
         self.n, self.lengths = n, L
-        self.off = np.zeros((S, n + 1), np.int64)
-        np.cumsum(L, axis=1, out=self.off[:, 1:])
+        self.off = np.stack([ragged.offsets(row, total=True) for row in L])
         in_off = np.ascontiguousarray(in_off, np.int64).reshape(-1)
         i64 = np.concatenate([in_off, self.off.reshape(-1)])
         raw = np.concatenate([i64.view(np.uint8), np.ascontiguousarray(L, np.int32).reshape(-1).view(np.uint8)])
@@ -293,7 +280,7 @@ def _encode_chunk(enc, W, tb, x_ptr, bufs, idx_ptr, want_e, latents=None):
               None, ws.ptr, ws.nbytes, _S())
     if latents is not None:
         z = DeviceArray((d, T), np.float32, _block=y._block, _ptr=y.ptr).get()
-        latents += [z[:, int(a):int(b)].copy() for a, b in zip(tb.off[depth, :-1], tb.off[depth, 1:])]
+        latents += ragged.split(z, tb.off[depth])
     return e
 
 
@@ -306,35 +293,6 @@ def _condition_chunk(cond, tb, s, e_ptr, bufs, local_ptr):
         y_ptr = local_ptr if last else bufs.get(which, Wc.shape[0] * T).ptr
         _conv(tb, src, T, tb.off_ptr(s), s, s, Wc, bc, y_ptr, (3, 1, dil, dil), True, blocked=last)
         src, which = y_ptr, which ^ 1
-
-
-def _stage_waves(waves, who):
-    """The sizes of the list's waves, and a function that lays a run of them end to end on the device (host waves: one
-    copy per run; device waves: one batched copy)."""
-    waves = list(waves)
-    for i, w in enumerate(waves):
-        if backend.is_device(w):
-            if w.dtype != np.float32:
-                raise ValueError('%s: wave %d is a %s device array, float32 needed' % (who, i, w.dtype))
-        else:
-            waves[i] = np.ascontiguousarray(w, np.float32).reshape(-1)
-    sizes = np.array([w.size for w in waves], np.int64)
-
-    def upload(start, stop):
-        offs = np.concatenate([[0], np.cumsum(sizes[start:stop])]).astype(np.int64)
-        part = waves[start:stop]
-        if not any(backend.is_device(w) for w in part):
-            return backend.to_device(np.concatenate(part) if len(part) > 1 else part[0], np.float32)
-        stage = np.zeros(int(offs[-1]), np.float32)
-        for w, o in zip(part, offs):
-            if not backend.is_device(w):
-                stage[int(o):int(o) + w.size] = w
-        buf = backend.to_device(stage, np.float32) if any(not backend.is_device(w) for w in part) \
-            else DeviceArray((int(offs[-1]),), np.float32)
-        backend.copy_many([(buf.flat_view(int(o), w.size), w.reshape(-1)) for w, o in zip(part, offs) if backend.is_device(w)])
-        return buf
-
-    return sizes, upload
 
 
 def _run(who, encoder, vq, condition_embed, lengths, source, speakers, chunk_bytes, codes_in=None, latents=None):
@@ -364,7 +322,7 @@ def _run(who, encoder, vq, condition_embed, lengths, source, speakers, chunk_byt
     if cond is not None:
         spk = _speakers(speakers, N, E.shape[0], who)
     Cl = cond[-1][0].shape[0] if cond is not None else 0
-    lat_off = np.concatenate([[0], np.cumsum(tl, dtype=np.int64)]).astype(np.int64)
+    lat_off = ragged.offsets(tl, total=True)
     if enc is not None:
         widths = [1] + [Wb[0].shape[0] for Wb in enc]
         widths[-1] = max(widths[-1], Cl)
@@ -398,17 +356,6 @@ def _run(who, encoder, vq, condition_embed, lengths, source, speakers, chunk_byt
     return out_codes, out_cond
 
 
-def _wave_source(waves, who):
-    sizes, upload = _stage_waves(waves, who)
-
-    def source(start, stop):
-        buf = upload(start, stop)
-        off = np.concatenate([[0], np.cumsum(sizes[start:stop])[:-1]]).astype(np.int64)
-        return buf.ptr, off, buf
-
-    return sizes, source
-
-
 # --------------------------------------------------------------------------- #
 # the public calls
 # --------------------------------------------------------------------------- #
@@ -418,7 +365,7 @@ def encode_many(encoder, vq, waves, chunk_bytes=1 << 30, return_latents=False):
     host waves are uploaded with one copy per chunk.  The result does not depend on ``chunk_bytes``.
     ``return_latents``: also the encoder's output z of every utterance, a list of host arrays (d, tl_i) (one copy back
     per chunk: for analysis and tests), returned as (codes, latents)."""
-    sizes, source = _wave_source(waves, 'encode_many')
+    sizes, source = ragged.wave_source(waves, 'encode_many')
     latents = [] if return_latents else None
     codes = _run('encode_many', encoder, vq, None, sizes, source, None, chunk_bytes, latents=latents)[0]
     return (codes, latents) if return_latents else codes
@@ -427,15 +374,8 @@ def encode_many(encoder, vq, waves, chunk_bytes=1 << 30, return_latents=False):
 def encode_corpus(corpus, encoder, vq, chunk_bytes=1 << 30):
     """``ResidentCorpus.encode`` / ``CorpusView.encode``: the utterances are read in place from the corpus buffer through
     its offsets and lengths; nothing is copied."""
-    base = corpus.corpus
-    if getattr(base, 'samples', None) is None:
-        raise RuntimeError('encode: this corpus is a description only (nothing on the device)')
-    utt = np.asarray(corpus.utterances, np.int64)
-
-    def source(start, stop):
-        return base.samples.ptr, base.offsets[utt[start:stop]], None
-
-    return _run('encode', encoder, vq, None, np.asarray(corpus.lengths, np.int64), source, None, chunk_bytes)[0]
+    lengths, source = ragged.wave_source(corpus, 'encode')
+    return _run('encode', encoder, vq, None, lengths, source, None, chunk_bytes)[0]
 
 
 def condition_many(vq, condition_embed, codes, speakers, chunk_bytes=1 << 30):
@@ -448,6 +388,6 @@ def condition_many(vq, condition_embed, codes, speakers, chunk_bytes=1 << 30):
 def frontend_many(encoder, vq, condition_embed, waves, speakers, chunk_bytes=1 << 30, return_codes=False):
     """``encode_many`` and ``condition_many`` in one pass over the chunks, the condition stack reading the e the
     nearest-code search already wrote.  Returns the LatentCondition, with ``return_codes`` (condition, codes)."""
-    sizes, source = _wave_source(waves, 'frontend_many')
+    sizes, source = ragged.wave_source(waves, 'frontend_many')
     codes, cond = _run('frontend_many', encoder, vq, condition_embed, sizes, source, speakers, chunk_bytes)
     return (cond, codes) if return_codes else cond

@@ -12,7 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, backend, core
+from . import _lib, backend, core, ragged
 from .backend import DeviceArray
 
 _S = backend.stream
@@ -245,9 +245,7 @@ class LatentCondition(object):
     def __init__(self, tl, Cl, G, upscale, local=None, global_vec=None):
         """The description alone (``local`` and ``global_vec`` None) is enough to plan a run; from_latents and
         from_condition fill the device buffers in."""
-        tl = np.asarray(tl)
-        if tl.ndim != 1 or tl.size == 0 or tl.dtype.kind not in 'iu' or (tl < 1).any():
-            raise ValueError('LatentCondition: tl must be (N,) latent lengths >= 1 with N >= 1, got %r' % (tl,))
+        tl = ragged.check_lengths(tl, 'LatentCondition')
         if int(Cl) < 0 or int(G) < 0 or int(Cl) + int(G) < 1 or int(upscale) < 1:
             raise ValueError('LatentCondition: needs Cl >= 0, G >= 0, Cl + G >= 1 and upscale >= 1, got %r, %r, %r' % (Cl, G, upscale))
         if int(upscale) * int(tl.max()) > _INT_MAX:
@@ -255,7 +253,7 @@ class LatentCondition(object):
         self.tl = tl.astype(np.int32)
         self.Cl, self.G, self.upscale = int(Cl), int(G), int(upscale)
         sizes = self.Cl * self.tl.astype(np.int64)
-        self.local_off = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+        self.local_off = ragged.offsets(sizes)
         self.local_size = int(sizes.sum())
         self.local, self.global_vec = local, global_vec
         self._tables = None
@@ -402,16 +400,15 @@ class LatentCondition(object):
             out = DeviceArray((N, Cc, Tmax), np.float32)
             expand(out, 0, N, int(self.tl[0]), Tmax)
             return out
-        out = backend.zeros((N, Cc, Tmax), np.float32)
-        pairs, keep = [], []
-        for q in range(N):
+        keep = []
+
+        def alone(q):                                      # sequence q expanded on its own, (Cc, T_q), kept until the copies are done
             Tl = int(self.tl[q])
-            T = self.upscale * Tl
-            y = DeviceArray((Cc, T), np.float32)
-            expand(y, q, 1, Tl, T)
-            keep.append(y)
-            pairs += [(out.flat_view((q * Cc + ch) * Tmax, T), y.flat_view(ch * T, T)) for ch in range(Cc)]
-        backend.copy_many(pairs)
+            keep.append(DeviceArray((Cc, self.upscale * Tl), np.float32))
+            expand(keep[-1], q, 1, Tl, self.upscale * Tl)
+            return keep[-1]
+
+        out = ragged.pack_padded(map(alone, range(N)), self.lengths, Cc, Tmax)     # zeroes the output, then walks the map
         backend.synchronize()                              # the per-sequence buffers go out of scope here
         return out
 

@@ -15,7 +15,7 @@ import struct
 
 import numpy as np
 
-from . import _lib, backend
+from . import _lib, backend, ragged
 from .backend import DeviceArray
 from .inputs import _Pinned
 
@@ -271,9 +271,9 @@ class DeviceIngest(object):
         taps, (L, M, J) = self.taps(first.sr)
         U = len(items)
         n_in = np.array([it.frames for it in items], np.int32)
-        in_off = np.concatenate(([0], np.cumsum(n_in[:-1], dtype=np.int64))).astype(np.int64)
+        in_off = ragged.offsets(n_in)
         n_out = np.array([resampled_length(n, L, M) for n in n_in], np.int32)
-        y_off = np.concatenate(([0], np.cumsum(n_out[:-1], dtype=np.int64))).astype(np.int64)
+        y_off = ragged.offsets(n_out)
         per_frame = first.channels * first.dtype.itemsize
         nbytes = int(n_in.sum(dtype=np.int64)) * per_frame
         flat = stage.array[:nbytes].view(first.dtype)
@@ -406,8 +406,7 @@ class DeviceIngest(object):
             raise ValueError('DeviceIngest.run: %d sample rates for %d waves' % (len(srs), len(raws)))
         items = [_Array(raw, sr, 'wave %d' % i) for i, (raw, sr) in enumerate(zip(raws, srs))]
         samples, lengths, _, _ = self.ingest(items, batch_bytes, False, 'DeviceIngest.run')
-        offsets = np.concatenate(([0], np.cumsum(lengths[:-1])))
-        return [samples.flat_view(int(o), int(n)) for o, n in zip(offsets, lengths)], lengths
+        return [samples.flat_view(int(o), int(n)) for o, n in zip(ragged.offsets(lengths), lengths)], lengths
 
     def preprocess_wave(self, raw, sr_in):
         """One wave as ``synthesize`` takes it: device float32 (1, 1, T, 1) (generate.py:43-50)."""

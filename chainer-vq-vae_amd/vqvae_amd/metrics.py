@@ -19,7 +19,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, backend
+from . import _lib, backend, ragged
 from .backend import DeviceArray
 
 _S = backend.stream
@@ -134,41 +134,7 @@ def plan_chunks(frames, width, chunk_bytes):
     frames = np.asarray(frames, np.int64).reshape(-1)
     if int(width) < 1 or int(chunk_bytes) < 1:
         raise ValueError('plan_chunks: width and chunk_bytes must be positive, got %r and %r' % (width, chunk_bytes))
-    chunks, start, run = [], 0, 0
-    for u in range(len(frames)):
-        new = run + int(frames[u])
-        if u > start and 4 * int(width) * new > int(chunk_bytes):
-            chunks.append((start, u))
-            start, new = u, int(frames[u])
-        run = new
-    if len(frames) > start:
-        chunks.append((start, len(frames)))
-    return chunks
-
-
-# --------------------------------------------------------------------------- #
-# where the waves are
-# --------------------------------------------------------------------------- #
-def _source(waves, who):
-    """(lengths (N,) int64, source(start, stop) -> (device pointer of x, off_in (n,) int64, what to keep alive))."""
-    from .corpus import _Utterances
-    from .frontend import _stage_waves
-    if isinstance(waves, _Utterances):
-        base = waves.corpus
-        if getattr(base, 'samples', None) is None:
-            raise RuntimeError('%s: this corpus is a description only (nothing on the device)' % who)
-        utt = np.asarray(waves.utterances, np.int64)
-        return np.asarray(waves.lengths, np.int64), lambda start, stop: (base.samples.ptr, base.offsets[utt[start:stop]], None)
-    sizes, upload = _stage_waves(waves, who)
-    if sizes.size == 0:
-        raise ValueError('%s: no utterances' % who)
-
-    def source(start, stop):
-        buf = upload(start, stop)
-        off = np.concatenate([[0], np.cumsum(sizes[start:stop])[:-1]]).astype(np.int64)
-        return buf.ptr, off, buf
-
-    return sizes, source
+    return ragged.plan_runs((int(width) * frames)[None], chunk_bytes)
 
 
 def _frames(lengths, cfg, who):
@@ -199,7 +165,7 @@ def _workspace(query, d, who):
 
 def _stft_mel(cfg, tabs, x_ptr, off_in, frames, log_mel_ptr, mag_ptr, stride, mel_ptr=None):
     """One launch over a run of utterances; returns the device frame_off table (kept by the caller while it is read)."""
-    frame_off = np.concatenate([[0], np.cumsum(frames, dtype=np.int64)]).astype(np.int64)
+    frame_off = ragged.offsets(frames, total=True)
     seg = backend.to_device(np.concatenate([np.ascontiguousarray(off_in, np.int64).reshape(-1), frame_off]))
     d = _desc(cfg, len(frames), frame_off[-1], stride)
     ws, need = _workspace('vqvae_metrics_stft_mel_workspace_bytes', d, 'features_many')
@@ -216,7 +182,7 @@ class RaggedFeatures(object):
     def __init__(self, cfg, frames, log_mel, mag, mel=None):
         self.cfg = cfg
         self.frames = np.asarray(frames, np.int64)
-        self.frame_off = np.concatenate([[0], np.cumsum(self.frames, dtype=np.int64)]).astype(np.int64)
+        self.frame_off = ragged.offsets(self.frames, total=True)
         self.log_mel, self.mag, self.mel = log_mel, mag, mel
         self._host = None
 
@@ -231,8 +197,7 @@ class RaggedFeatures(object):
             raise IndexError('RaggedFeatures.utterance: utterance %d of %d' % (i, len(self.frames)))
         if self._host is None:
             self._host = [None if t is None else t.get() for t in (self.log_mel, self.mag, self.mel)]
-        a, b = int(self.frame_off[i]), int(self.frame_off[i + 1])
-        blocks = tuple(None if t is None else t[:, a:b].copy() for t in self._host)
+        blocks = tuple(None if t is None else ragged.split(t, self.frame_off[i:i + 2])[0] for t in self._host)
         return blocks if self.mel is not None else blocks[:2]
 
 
@@ -249,7 +214,7 @@ def features_many(waves, cfg, magnitudes=False, chunk_bytes=1 << 30, mel_powers=
     if not isinstance(cfg, MelConfig):
         raise TypeError('features_many: cfg must be a MelConfig, got %r' % (type(cfg),))
     host_tabs = tables(cfg)
-    lengths, source = _source(waves, 'features_many')
+    lengths, source = ragged.wave_source(waves, 'features_many')
     frames = _frames(lengths, cfg, 'features_many')
     chunks = plan_chunks(frames, cfg.nb if magnitudes else cfg.n_mels, chunk_bytes)
     feats = RaggedFeatures(cfg, frames, None, None)
@@ -279,8 +244,8 @@ def compare_many(reference, test, cfg, chunk_bytes=1 << 30):
     if not isinstance(cfg, MelConfig):
         raise TypeError('compare_many: cfg must be a MelConfig, got %r' % (type(cfg),))
     host_tabs = tables(cfg)
-    len_a, src_a = _source(reference, 'compare_many')
-    len_b, src_b = _source(test, 'compare_many')
+    len_a, src_a = ragged.wave_source(reference, 'compare_many')
+    len_b, src_b = ragged.wave_source(test, 'compare_many')
     if len(len_a) != len(len_b):
         raise ValueError('compare_many: %d reference and %d test utterances' % (len(len_a), len(len_b)))
     frames = _frames(np.minimum(len_a, len_b), cfg, 'compare_many')

@@ -8,7 +8,7 @@ path; `serializers.load_npz(path, link, prefix)` loads the reference's snapshot 
 """
 import numpy as np
 
-from . import backend, core
+from . import backend, core, ragged
 from .core import Variable
 from .utils import MuLaw
 
@@ -143,10 +143,8 @@ def synthesize_many(encoder, vq, decoder, condition_embed, waves, global_conditi
         Tmax = cond.shape[2]
     else:
         lengths = np.array([c.shape[1] for c in conds], np.int64)
-        Cc, Tmax = conds[0].shape[0], int(lengths.max())
-        cond = backend.zeros((N, Cc, Tmax), np.float32)
-        backend.copy_many([(cond.flat_view((i * Cc + ch) * Tmax, int(L)), c.flat_view(ch * int(L), int(L)))
-                           for i, (c, L) in enumerate(zip(conds, lengths)) for ch in range(Cc)])
+        Tmax = int(lengths.max())
+        cond = ragged.pack_padded(conds, lengths, conds[0].shape[0], Tmax)
     steps = Tmax - 1 if n_steps is None else n_steps
     u = _draw_uniforms(rng, decoder, use_logistic, steps, N)
     out = decoder.generate_lockstep(cond, u, n_steps=n_steps, lengths=lengths, group=group, refill=refill,

@@ -29,6 +29,17 @@ def assert_close_scaled(got, want, tol=1e-4, name=''):
     assert err <= tol, '%s: max err %.3e of scale %.3e (tol %g)' % (name, err, scale, tol)
 
 
+def _bits(a):
+    """The array's bits as unsigned integers of its item size: equality of these is bit equality (-0.0 and NaNs included)."""
+    a = np.ascontiguousarray(a)
+    return a.view({1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
+def _same(got, want, what=''):
+    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
+    np.testing.assert_array_equal(_bits(got), _bits(want), what)
+
+
 SMALL = dict(d=32, k=64, n_loop=2, n_layer=3, filter_size=2, input_dim=256, residual=64,
              dilated=64, skip=64, out_dim=256, local_dim=32, global_dim=32, n_speaker=7)
 

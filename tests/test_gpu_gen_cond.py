@@ -9,6 +9,7 @@ import pytest
 
 import gen_cond_ref as R
 import helpers as H
+from helpers import _bits
 import vqvae_oracle as O
 from test_gpu_generate import _decoder, _random_biases
 from zoned import In, Out, run_contract
@@ -16,10 +17,6 @@ from zoned import In, Out, run_contract
 pytestmark = pytest.mark.gpu
 
 TL11 = (3, 1, 2, 3, 1, 2, 2, 1, 3, 1, 2)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _latent(gpu, cfg, tl, seed, upscale=64):

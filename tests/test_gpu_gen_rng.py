@@ -9,6 +9,7 @@ import pytest
 
 import gen_rng_ref as R
 import helpers as H
+from helpers import _bits, _same
 import vqvae_oracle as O
 from test_gpu_generate import _cond, _decoder, _random_biases
 from zoned import In, Out, run_contract
@@ -20,16 +21,6 @@ HIGH_IDS = [2 ** 40 + 3, 5, 2 ** 64 - 1]     # ... and in the ids
 TL11 = (3, 1, 2, 3, 1, 2, 2, 1, 3, 1, 2)
 LENGTHS11 = np.array([48, 17, 33, 48, 9, 40, 25, 1, 48, 2, 31])
 IDS11 = np.array([900, 2 ** 33 + 1, 7, 2 ** 63, 4, 3, 2, 1, 0, 2 ** 64 - 1, 12], np.uint64)     # permuted, not arange
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def _same(got, want, what=''):
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    np.testing.assert_array_equal(_bits(got), _bits(want), what)
 
 
 def _same_pair(a, b, what=''):

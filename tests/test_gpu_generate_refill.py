@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+from helpers import _bits
 import vqvae_oracle as O
 from helpers import assert_close
 from test_gpu_generate import _cond, _decoder, _random_biases
@@ -16,10 +17,6 @@ from zoned import In, Out, run_contract
 pytestmark = pytest.mark.gpu
 
 LENGTHS11 = np.array([40, 7, 23, 1, 40, 12, 2, 31, 23, 9, 18])
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _both(gpu, dec, cond, u, **kw):

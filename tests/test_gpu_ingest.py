@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+from helpers import _bits, _same
 import ingest_ref as R
 from test_host_ingest import n_in_for, raw_wave, trim_signals
 from zoned import In, Out, ZonedArray, run_contract
@@ -15,16 +16,6 @@ from zoned import In, Out, ZonedArray, run_contract
 pytestmark = pytest.mark.gpu
 
 TILE = 1024
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def _same(got, want, what=''):
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    np.testing.assert_array_equal(_bits(got), _bits(want), what)
 
 
 # ---- 1. resample -------------------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+from helpers import _bits
 import ragged_frontend_ref as R
 import vqvae_oracle as O
 from zoned import In, Out, run_contract
@@ -79,10 +80,6 @@ def _links(P):
     for link in (enc, vq, ce):
         link.to_gpu()
     return enc, vq, ce
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype.itemsize == 4 else np.uint8)
 
 
 def _blocks(cond):

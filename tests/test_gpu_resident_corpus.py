@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+from helpers import _bits, _same
 import resident_corpus_ref as R
 from zoned import In, Out, run_contract
 
@@ -14,16 +15,6 @@ pytestmark = pytest.mark.gpu
 
 SEED = 2 ** 40 + 71                          # bits above 32 set
 BATCH = 5
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def _same(got, want, what=''):
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    np.testing.assert_array_equal(_bits(got), _bits(want), what)
 
 
 def _normalised(w):
