@@ -1,4 +1,4 @@
-// The one segment search of the ragged kernels (ragged_front.hip, audio_metrics.hip): N segments laid end to end along
+// The one segment search of the ragged kernels (ragged_front.hip, audio_metrics.hip, audio_pitch.hip): N segments laid end to end along
 // one axis, described by the prefix table off (off[0] = 0, ascending).
 #ifndef VQ_RAGGED_SEG_H_
 #define VQ_RAGGED_SEG_H_

@@ -108,6 +108,12 @@ class MetricsDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('n', 'n_fft', 'hop', 'n_mels', 'n_mcep')] + [('floor', c_float), ('ftot', C.c_int64), ('stride', C.c_int64)]
 
 
+class PitchDesc(C.Structure):
+    """vqvae_pitch_desc (include/vqvae_pitch.h): one YIN / pair-statistics call over a ragged list."""
+    _fields_ = [(n, C.c_int32) for n in ('n', 'sr', 'frame', 'hop')] + \
+               [(n, C.c_double) for n in ('fmin', 'fmax', 'threshold', 'min_power')] + [('ftot', C.c_int64)]
+
+
 # name -> (restype, argtypes); this table IS the list of symbols the header declares
 PROTOTYPES = {
     'vqvae_last_error_string': (c_char_p, []),
@@ -392,6 +398,20 @@ METRICS_THREADS = 256             # VQVAE_METRICS_THREADS
 METRICS_MAX_NFFT = 2048           # VQVAE_METRICS_MAX_NFFT
 METRICS_MAX_MELS = 128            # VQVAE_METRICS_MAX_MELS
 
+# include/vqvae_pitch.h: ragged YIN F0 and the per-pair pitch statistics, a fourteenth table and version
+PITCH_PROTOTYPES = {
+    'vqvae_pitch_abi_version': (c_int, []),
+    'vqvae_pitch_yin_workspace_bytes': (c_size_t, [C.POINTER(PitchDesc)]),
+    'vqvae_pitch_compare_workspace_bytes': (c_size_t, [C.POINTER(PitchDesc)]),
+    'vqvae_pitch_yin': (c_int, [C.POINTER(PitchDesc), P, P, P, P, P, P, c_size_t, P]),
+    'vqvae_pitch_compare': (c_int, [C.POINTER(PitchDesc), P, P, P, P, P, c_size_t, P]),
+}
+PITCH_ABI_VERSION = 1             # vqvae_pitch_abi_version()
+PITCH_THREADS = 256               # VQVAE_PITCH_THREADS
+PITCH_MAX_TILE = 4                # VQVAE_PITCH_MAX_TILE
+PITCH_MAX_FRAME = 2048            # VQVAE_PITCH_MAX_FRAME
+PITCH_COLUMNS = 8                 # VQVAE_PITCH_COLUMNS
+
 # elementwise op codes / profiler tags (mirror the header)
 MAX_STACK_GROUP = 24              # blocks per resstack call (MAXSEG in csrc/gemm_common.h)
 STORE_X_BF16, STORE_RES_BF16 = 2, 4
@@ -436,7 +456,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES, KMEANS_PROTOTYPES, OPTIM_PROTOTYPES,
                   SAMPLING_PROTOTYPES, GEN_SLOTS_PROTOTYPES, GEN_COND_PROTOTYPES, GEN_RNG_PROTOTYPES,
-                  CORPUS_PROTOTYPES, INGEST_PROTOTYPES, RAGGED_PROTOTYPES, METRICS_PROTOTYPES):
+                  CORPUS_PROTOTYPES, INGEST_PROTOTYPES, RAGGED_PROTOTYPES, METRICS_PROTOTYPES, PITCH_PROTOTYPES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)           # AttributeError if the symbol is missing
             fn.restype = res
@@ -480,6 +500,9 @@ def load():
     if lib.vqvae_metrics_abi_version() != METRICS_ABI_VERSION:
         raise ImportError('libvqvae_hip.so at %s has audio-metrics ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
                           % (LIB_PATH, lib.vqvae_metrics_abi_version(), METRICS_ABI_VERSION))
+    if lib.vqvae_pitch_abi_version() != PITCH_ABI_VERSION:
+        raise ImportError('libvqvae_hip.so at %s has pitch ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
+                          % (LIB_PATH, lib.vqvae_pitch_abi_version(), PITCH_ABI_VERSION))
     _lib = lib
     return lib
 
