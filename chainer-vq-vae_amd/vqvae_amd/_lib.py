@@ -1,8 +1,15 @@
-"""ctypes binding of libvqvae_hip.so (include/vqvae_hip.h).
+"""ctypes binding of libvqvae_hip.so: one HEADERS entry per header under include/.
+
+An entry holds the header's file name, the words its version error uses, the version this package binds and the
+prototype table; load() binds every table, then compares every version.  A Structure names the C typedef it mirrors
+in _c_name_.  An upper-case integer N of this module mirrors the macro VQVAE_N of the header whose stem is the
+longest prefix of N (KMEANS_BLOCK: vqvae_kmeans.h), or of vqvae_hip.h when no stem is one (EW_ADD, GEN_MAX_N);
+UNMIRRORED lists the few that mirror nothing public.  tests/test_host_abi.py holds all of this against the headers.
 
 There is no CPU fallback: if the shared library is missing, importing anything
 that needs it raises, and every compute entry point requires a gfx950 device.
 """
+import collections
 import ctypes as C
 import os
 
@@ -21,43 +28,51 @@ def ptr_array(arrays):
 
 
 class Conv1dDesc(C.Structure):
+    _c_name_ = 'vqvae_conv1d_desc'
     _fields_ = [(n, c_int) for n in
                 ('B', 'Cin', 'Tin', 'Cout', 'Tout', 'K', 'stride', 'pad', 'dil', 'relu')]
 
 
 class ResblockDesc(C.Structure):
+    _c_name_ = 'vqvae_resblock_desc'
     _fields_ = [(n, c_int) for n in ('B', 'T', 'Cr', 'Cd', 'Cs', 'Cc', 'K', 'dil', 'storage')]
 
 
 class ResblockParams(C.Structure):
+    _c_name_ = 'vqvae_resblock_params'
     _fields_ = [(n, P) for n in ('Wd', 'bd', 'Wc', 'bc', 'Wr', 'br', 'Ws', 'bs')]
 
 
 class ResblockCproj(C.Structure):
+    _c_name_ = 'vqvae_resblock_cproj'
     _fields_ = [('P', P), ('P_bstride', c_long), ('Tl', c_int), ('v0', P), ('w0', P), ('w1', P), ('P_has_bd', c_int), ('P_amax', P)]
 
 
 class ResblockAmax(C.Structure):
-    """vqvae_resblock_amax: device uint32 slots (float bit patterns of absolute maxima), matmul mode 3."""
+    """Device uint32 slots (float bit patterns of absolute maxima), matmul mode 3."""
+    _c_name_ = 'vqvae_resblock_amax'
     _fields_ = [(n, P) for n in ('x', 'res', 'g_res', 'g_skip', 'gh', 'gx', 'x_max', 'res_scale', 'gh_scale',
                                  'pb_part', 'pb_v0', 'pb_w0', 'pb_w1')] + [('pb_Tl', c_int)]
 
 
 class Conv1dAmax(C.Structure):
-    """vqvae_conv1d_amax"""
+    _c_name_ = 'vqvae_conv1d_amax'
     _fields_ = [(n, P) for n in ('x', 'gy', 'out', 'packed')]
 
 
 class ResblockGrads(C.Structure):
+    _c_name_ = 'vqvae_resblock_grads'
     _fields_ = [(n, P) for n in ('gWd', 'gbd', 'gWc', 'gbc', 'gWr', 'gbr', 'gWs', 'gbs')]
 
 
 class GenBlock(C.Structure):
+    _c_name_ = 'vqvae_gen_block'
     _fields_ = [(n, P) for n in ('conv_W', 'conv_b', 'cond_W', 'cond_b', 'res_W', 'res_b',
                                  'skip_W', 'skip_b', 'ring')] + [('dilation', c_int)]
 
 
 class GenDesc(C.Structure):
+    _c_name_ = 'vqvae_gen_desc'
     _fields_ = ([(n, c_int) for n in ('n', 'n_blocks', 'input_dim', 'residual', 'dilated', 'skip',
                                       'cond_dim', 'out_dim', 'sample_mode')]
                 + [('log_scale_min', c_float)]
@@ -71,51 +86,75 @@ class GenDesc(C.Structure):
 
 
 class GenSampling(C.Structure):
-    """vqvae_gen_sampling (include/vqvae_sampling.h): device arrays of n entries, NULL = neutral for every sequence."""
+    """Device arrays of n entries, NULL = neutral for every sequence."""
+    _c_name_ = 'vqvae_gen_sampling'
     _fields_ = [(n, P) for n in ('temperature', 'top_k', 'top_p')]
 
 
 class GenSlots(C.Structure):
-    """vqvae_gen_slots (include/vqvae_gen_slots.h): the slot table of lockstep generation with refill."""
+    """The slot table of lockstep generation with refill."""
+    _c_name_ = 'vqvae_gen_slots'
     _fields_ = [('n_seq', c_int), ('steps', P), ('queue', P), ('n_queue', c_int), ('next', P), ('slot_seq', P),
                 ('slot_t', P), ('live', P), ('started', P)]
 
 
 class GenLatentCond(C.Structure):
-    """vqvae_gen_latent_cond (include/vqvae_gen_cond.h): the latent-rate condition of lockstep generation."""
+    """The latent-rate condition of lockstep generation."""
+    _c_name_ = 'vqvae_gen_latent_cond'
     _fields_ = [('local', P), ('local_off', P), ('tl', P), ('global_vec', P), ('col_seq', P), ('column', P),
                 ('n_seq', c_int), ('Cl', c_int), ('G', c_int), ('upscale', c_int)]
 
 
 class GenRng(C.Structure):
-    """vqvae_gen_rng (include/vqvae_gen_rng.h): the seed and the device array of stream ids (NULL = the identity)."""
+    """The seed and the device array of stream ids (NULL = the identity)."""
+    _c_name_ = 'vqvae_gen_rng'
     _fields_ = [('seed', C.c_uint64), ('ids', P)]
 
 
 class Corpus(C.Structure):
-    """vqvae_corpus (include/vqvae_corpus.h): the device-resident corpus, or a view of it (view NULL = the identity)."""
+    """The device-resident corpus, or a view of it (view NULL = the identity)."""
+    _c_name_ = 'vqvae_corpus'
     _fields_ = [(n, P) for n in ('samples', 'offset', 'length', 'speaker', 'view')] + [('n_view', C.c_int32)]
 
 
 class RaggedConvDesc(C.Structure):
-    """vqvae_ragged_conv_desc (include/vqvae_ragged.h): one conv stage over a ragged batch."""
+    """One conv stage over a ragged batch."""
+    _c_name_ = 'vqvae_ragged_conv_desc'
     _fields_ = [(n, C.c_int32) for n in ('n', 'cin', 'cout', 'K', 'stride', 'pad', 'dil', 'relu', 'blocked_out')] + \
                [('ttot_out', C.c_int64), ('x_cstride', C.c_int64)]
 
 
 class MetricsDesc(C.Structure):
-    """vqvae_metrics_desc (include/vqvae_metrics.h): one STFT / log-mel / distance call over a ragged list."""
+    """One STFT / log-mel / distance call over a ragged list."""
+    _c_name_ = 'vqvae_metrics_desc'
     _fields_ = [(n, C.c_int32) for n in ('n', 'n_fft', 'hop', 'n_mels', 'n_mcep')] + [('floor', c_float), ('ftot', C.c_int64), ('stride', C.c_int64)]
 
 
 class PitchDesc(C.Structure):
-    """vqvae_pitch_desc (include/vqvae_pitch.h): one YIN / pair-statistics call over a ragged list."""
+    """One YIN / pair-statistics call over a ragged list."""
+    _c_name_ = 'vqvae_pitch_desc'
     _fields_ = [(n, C.c_int32) for n in ('n', 'sr', 'frame', 'hop')] + \
                [(n, C.c_double) for n in ('fmin', 'fmax', 'threshold', 'min_power')] + [('ftot', C.c_int64)]
 
 
-# name -> (restype, argtypes); this table IS the list of symbols the header declares
-PROTOTYPES = {
+class Header(collections.namedtuple('Header', 'file words version prototypes')):
+    """One header of include/: what the version error calls it, the version bound, name -> (restype, argtypes)."""
+
+    @property
+    def version_symbol(self):
+        stem = self.file[len('vqvae_'):-len('.h')]
+        return 'vqvae_abi_version' if stem == 'hip' else 'vqvae_%s_abi_version' % stem
+
+
+HEADERS = {}                      # file name -> Header, in load order
+
+
+def _header(file, words, version, prototypes):
+    HEADERS[file] = Header(file, words, version, prototypes)
+
+
+# each table IS the list of symbols its header declares
+_header('vqvae_hip.h', 'ABI', 5, {
     'vqvae_last_error_string': (c_char_p, []),
     'vqvae_abi_version': (c_int, []),
     'vqvae_device_count': (c_int, [C.POINTER(c_int)]),
@@ -262,47 +301,44 @@ PROTOTYPES = {
     'vqvae_graph_capture_end': (c_int, [P, C.POINTER(c_void_p)]),
     'vqvae_graph_launch': (c_int, [P, P]),
     'vqvae_graph_destroy': (c_int, [P]),
-}
+})
 
-# include/vqvae_codebook.h: codebook statistics and re-seeding, a table (and a version) of its own beside the ABI above
-CODEBOOK_PROTOTYPES = {
+# include/vqvae_codebook.h: codebook statistics and re-seeding
+_header('vqvae_codebook.h', 'codebook ABI', 1, {
     'vqvae_codebook_abi_version': (c_int, []),
     'vqvae_codebook_observe': (c_int, [P, P, c_int, c_int, c_int, c_int, c_float, C.c_uint64, P, P, P, P, P, P]),
     'vqvae_codebook_reseed': (c_int, [P, P, P, c_int, c_int, P, P, c_float, c_float, P, P, P]),
-}
-CODEBOOK_ABI_VERSION = 1          # vqvae_codebook_abi_version()
-CODEBOOK_STATS_WORDS = 8          # VQVAE_CODEBOOK_STATS_WORDS
-CODEBOOK_LDS_MAX_K = 16384        # VQVAE_CODEBOOK_LDS_MAX_K
+})
+CODEBOOK_STATS_WORDS = 8
+CODEBOOK_LDS_MAX_K = 16384
 
-# include/vqvae_vq_ema.h: EMA codebook updates, again a table and a version of their own
-VQ_EMA_PROTOTYPES = {
+# include/vqvae_vq_ema.h: EMA codebook updates
+_header('vqvae_vq_ema.h', 'EMA-codebook ABI', 1, {
     'vqvae_vq_ema_abi_version': (c_int, []),
     'vqvae_vq_ema_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'vqvae_vq_ema_accumulate': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
     'vqvae_vq_ema_apply': (c_int, [P, P, P, P, c_int, c_int, c_float, c_float, P]),
     'vqvae_vq_ema_reset': (c_int, [P, P, P, c_int, c_int, P, P]),
-}
-VQ_EMA_ABI_VERSION = 1            # vqvae_vq_ema_abi_version()
-VQ_EMA_PIECE = 512                # VQVAE_VQ_EMA_PIECE
-VQ_EMA_SMALL_MAX_N = 4096         # VQVAE_VQ_EMA_SMALL_MAX_N
-VQ_EMA_MAX_N = 1 << 24            # VQVAE_VQ_EMA_MAX_N
+})
+VQ_EMA_PIECE = 512
+VQ_EMA_SMALL_MAX_N = 4096
+VQ_EMA_MAX_N = 1 << 24
 
-# include/vqvae_kmeans.h: k-means initialisation of the codebook, a fourth table and version
-KMEANS_PROTOTYPES = {
+# include/vqvae_kmeans.h: k-means initialisation of the codebook
+_header('vqvae_kmeans.h', 'k-means ABI', 1, {
     'vqvae_kmeans_abi_version': (c_int, []),
     'vqvae_kmeans_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'vqvae_kmeans_collect': (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, P]),
     'vqvae_kmeans_seed': (c_int, [P, c_int, c_int, c_int, C.c_uint64, P, P, P, P, c_size_t, P]),
     'vqvae_kmeans_update': (c_int, [P, c_int, c_int, c_int, P, C.c_uint64, c_int, P, P, P]),
     'vqvae_kmeans_inertia': (c_int, [P, P, P, c_int, c_int, c_int, P, P, c_size_t, P]),
-}
-KMEANS_ABI_VERSION = 1            # vqvae_kmeans_abi_version()
-KMEANS_BLOCK = 256                # VQVAE_KMEANS_BLOCK
-KMEANS_MAX_N = 1 << 24            # VQVAE_KMEANS_MAX_N
-KMEANS_MAX_D = 4096               # VQVAE_KMEANS_MAX_D
+})
+KMEANS_BLOCK = 256
+KMEANS_MAX_N = 1 << 24
+KMEANS_MAX_D = 4096
 
-# include/vqvae_optim.h: optimizer hooks (gradient norms, clipping, the non-finite guard), a fifth table and version
-OPTIM_PROTOTYPES = {
+# include/vqvae_optim.h: optimizer hooks (gradient norms, clipping, the non-finite guard)
+_header('vqvae_optim.h', 'optimizer-hook ABI', 1, {
     'vqvae_optim_abi_version': (c_int, []),
     'vqvae_optim_plan_items': (c_int, [C.POINTER(C.c_int64), c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'vqvae_optim_workspace_bytes': (c_size_t, [c_int]),
@@ -310,39 +346,35 @@ OPTIM_PROTOTYPES = {
     'vqvae_optim_sumsq': (c_int, [P, c_size_t, P, c_int, P, c_int, P, P, c_int, c_int, c_double, c_int, P, P, c_size_t, P]),
     'vqvae_optim_adam_step_hooked': (c_int, [P, P, P, P, c_size_t, c_double, P, P, c_double, c_double, c_double, P,
                                              c_int, P]),
-}
-OPTIM_ABI_VERSION = 1             # vqvae_optim_abi_version()
-OPTIM_CHUNK = 4096                # VQVAE_OPTIM_CHUNK
-OPTIM_THREADS = 256               # VQVAE_OPTIM_THREADS
-OPTIM_STATE_HEADER = 64           # VQVAE_OPTIM_STATE_HEADER
-OPTIM_GUARD = 1                   # VQVAE_OPTIM_GUARD
+})
+OPTIM_CHUNK = 4096
+OPTIM_THREADS = 256
+OPTIM_STATE_HEADER = 64
+OPTIM_GUARD = 1
 
-# include/vqvae_sampling.h: sampling controls for generation (temperature, top-k, top-p, greedy), a sixth table and version
-SAMPLING_PROTOTYPES = {
+# include/vqvae_sampling.h: sampling controls for generation (temperature, top-k, top-p, greedy)
+_header('vqvae_sampling.h', 'sampling ABI', 1, {
     'vqvae_sampling_abi_version': (c_int, []),
     'vqvae_wavenet_gen_step_sampled': (c_int, [C.POINTER(GenDesc), C.POINTER(GenSampling), P]),
     'vqvae_sample_logits': (c_int, [P, c_int, c_int, c_int, c_float, P, c_int, C.POINTER(GenSampling), P, P, P]),
-}
-SAMPLING_ABI_VERSION = 1          # vqvae_sampling_abi_version()
-SAMPLING_MAX_CLASSES = 1024       # VQVAE_SAMPLING_MAX_CLASSES
+})
+SAMPLING_MAX_CLASSES = 1024
 
-# include/vqvae_gen_slots.h: lockstep generation with refill (slots, queue and scheduler on the device), a seventh table and version
-GEN_SLOTS_PROTOTYPES = {
+# include/vqvae_gen_slots.h: lockstep generation with refill (slots, queue and scheduler on the device)
+_header('vqvae_gen_slots.h', 'slot-generation ABI', 1, {
     'vqvae_gen_slots_abi_version': (c_int, []),
     'vqvae_gen_slots_init': (c_int, [C.POINTER(GenDesc), C.POINTER(GenSlots), P]),
     'vqvae_wavenet_gen_step_slots': (c_int, [C.POINTER(GenDesc), C.POINTER(GenSlots), C.POINTER(GenSampling), P]),
-}
-GEN_SLOTS_ABI_VERSION = 1         # vqvae_gen_slots_abi_version()
+})
 
-# include/vqvae_gen_cond.h: the condition column of a lockstep step from the latent-rate condition, an eighth table and version
-GEN_COND_PROTOTYPES = {
+# include/vqvae_gen_cond.h: the condition column of a lockstep step from the latent-rate condition
+_header('vqvae_gen_cond.h', 'latent-condition ABI', 1, {
     'vqvae_gen_cond_abi_version': (c_int, []),
     'vqvae_gen_cond_column': (c_int, [C.POINTER(GenLatentCond), C.POINTER(GenDesc), C.POINTER(GenSlots), P]),
-}
-GEN_COND_ABI_VERSION = 1          # vqvae_gen_cond_abi_version()
+})
 
-# include/vqvae_gen_rng.h: the uniforms of generation drawn on the device (Philox4x32-10), a ninth table and version
-GEN_RNG_PROTOTYPES = {
+# include/vqvae_gen_rng.h: the uniforms of generation drawn on the device (Philox4x32-10)
+_header('vqvae_gen_rng.h', 'device-uniforms ABI', 1, {
     'vqvae_gen_rng_abi_version': (c_int, []),
     'vqvae_gen_rng_fill': (c_int, [C.POINTER(GenRng), c_int, c_int, c_int, c_int, P, P]),
     'vqvae_sample_logits_rng': (c_int, [P, c_int, c_int, c_int, c_float, C.POINTER(GenRng), c_int, c_int,
@@ -350,70 +382,70 @@ GEN_RNG_PROTOTYPES = {
     'vqvae_wavenet_gen_step_rng': (c_int, [C.POINTER(GenDesc), C.POINTER(GenSampling), C.POINTER(GenRng), P]),
     'vqvae_wavenet_gen_step_slots_rng': (c_int, [C.POINTER(GenDesc), C.POINTER(GenSlots), C.POINTER(GenSampling),
                                                  C.POINTER(GenRng), P]),
-}
-GEN_RNG_ABI_VERSION = 1           # vqvae_gen_rng_abi_version()
+})
 
-# include/vqvae_corpus.h: minibatches drawn on the device from a corpus that lives there, a tenth table and version
-CORPUS_PROTOTYPES = {
+# include/vqvae_corpus.h: minibatches drawn on the device from a corpus that lives there
+_header('vqvae_corpus.h', 'resident-corpus ABI', 1, {
     'vqvae_corpus_abi_version': (c_int, []),
     'vqvae_corpus_draw': (c_int, [C.POINTER(Corpus), C.c_uint64, c_int, C.c_uint64, c_int, c_int, c_int, c_int, c_int, P, c_int,
                                   P, P, P, P, P, P, P]),
-}
-CORPUS_ABI_VERSION = 1            # vqvae_corpus_abi_version()
+})
 
-# include/vqvae_ingest.h: decode, resample, trim and normalise raw audio into a corpus's waveforms, an eleventh table and version
-INGEST_PROTOTYPES = {
+# include/vqvae_ingest.h: decode, resample, trim and normalise raw audio into a corpus's waveforms
+_header('vqvae_ingest.h', 'ingest ABI', 1, {
     'vqvae_ingest_abi_version': (c_int, []),
     'vqvae_ingest_workspace_bytes': (c_size_t, [c_int, c_int]),
     'vqvae_ingest_resample': (c_int, [P, c_int, c_int, P, P, c_int, c_int, P, c_int, c_int, c_int, P, P, c_int, P]),
     'vqvae_ingest_trim_bounds': (c_int, [P, P, P, c_int, c_int, c_double, P, c_size_t, P, P]),
     'vqvae_ingest_pack': (c_int, [P, P, P, P, c_int, c_int, P, P]),
-}
-INGEST_ABI_VERSION = 1            # vqvae_ingest_abi_version()
-INGEST_TILE = 1024                # VQVAE_INGEST_TILE
-INGEST_MAX_TAPS = 1 << 22         # VQVAE_INGEST_MAX_TAPS
-INGEST_MAX_WINDOW = 16384         # VQVAE_INGEST_MAX_WINDOW
+})
+INGEST_TILE = 1024
+INGEST_MAX_TAPS = 1 << 22
+INGEST_MAX_WINDOW = 16384
 
-# include/vqvae_ragged.h: the encoder's and ConditionEmbed's convs over a ragged batch and the two gathers, a twelfth table and version
-RAGGED_PROTOTYPES = {
+# include/vqvae_ragged.h: the encoder's and ConditionEmbed's convs over a ragged batch and the two gathers
+_header('vqvae_ragged.h', 'ragged-front-end ABI', 1, {
     'vqvae_ragged_abi_version': (c_int, []),
     'vqvae_ragged_conv_workspace_bytes': (c_size_t, [C.POINTER(RaggedConvDesc)]),
     'vqvae_ragged_conv_fwd': (c_int, [C.POINTER(RaggedConvDesc), P, P, P, P, P, P, P, P, c_size_t, P]),
     'vqvae_ragged_code_gather': (c_int, [P, P, C.c_int64, c_int, c_int, P, P]),
     'vqvae_ragged_speaker_gather': (c_int, [P, P, c_int, c_int, c_int, P, P]),
-}
-RAGGED_ABI_VERSION = 1            # vqvae_ragged_abi_version()
+})
 
-# include/vqvae_metrics.h: ragged STFT, log-mel and the per-utterance distances, a thirteenth table and version
-METRICS_PROTOTYPES = {
+# include/vqvae_metrics.h: ragged STFT, log-mel and the per-utterance distances
+_header('vqvae_metrics.h', 'audio-metrics ABI', 1, {
     'vqvae_metrics_abi_version': (c_int, []),
     'vqvae_metrics_stft_mel_workspace_bytes': (c_size_t, [C.POINTER(MetricsDesc)]),
     'vqvae_metrics_distances_workspace_bytes': (c_size_t, [C.POINTER(MetricsDesc)]),
     'vqvae_metrics_stft_mel': (c_int, [C.POINTER(MetricsDesc), P, P, P, P, P, P, P, P, P, c_size_t, P]),
     'vqvae_metrics_distances': (c_int, [C.POINTER(MetricsDesc), P, P, P, P, P, P, P, P, c_size_t, P]),
-}
-METRICS_ABI_VERSION = 1           # vqvae_metrics_abi_version()
-METRICS_TILE = 32                 # VQVAE_METRICS_TILE
-METRICS_THREADS = 256             # VQVAE_METRICS_THREADS
-METRICS_MAX_NFFT = 2048           # VQVAE_METRICS_MAX_NFFT
-METRICS_MAX_MELS = 128            # VQVAE_METRICS_MAX_MELS
+})
+METRICS_TILE = 32
+METRICS_THREADS = 256
+METRICS_MAX_NFFT = 2048
+METRICS_MAX_MELS = 128
 
-# include/vqvae_pitch.h: ragged YIN F0 and the per-pair pitch statistics, a fourteenth table and version
-PITCH_PROTOTYPES = {
+# include/vqvae_pitch.h: ragged YIN F0 and the per-pair pitch statistics
+_header('vqvae_pitch.h', 'pitch ABI', 1, {
     'vqvae_pitch_abi_version': (c_int, []),
     'vqvae_pitch_yin_workspace_bytes': (c_size_t, [C.POINTER(PitchDesc)]),
     'vqvae_pitch_compare_workspace_bytes': (c_size_t, [C.POINTER(PitchDesc)]),
     'vqvae_pitch_yin': (c_int, [C.POINTER(PitchDesc), P, P, P, P, P, P, c_size_t, P]),
     'vqvae_pitch_compare': (c_int, [C.POINTER(PitchDesc), P, P, P, P, P, c_size_t, P]),
-}
-PITCH_ABI_VERSION = 1             # vqvae_pitch_abi_version()
-PITCH_THREADS = 256               # VQVAE_PITCH_THREADS
-PITCH_MAX_TILE = 4                # VQVAE_PITCH_MAX_TILE
-PITCH_MAX_FRAME = 2048            # VQVAE_PITCH_MAX_FRAME
-PITCH_COLUMNS = 8                 # VQVAE_PITCH_COLUMNS
+})
+PITCH_THREADS = 256
+PITCH_MAX_TILE = 4
+PITCH_MAX_FRAME = 2048
+PITCH_COLUMNS = 8
 
-# elementwise op codes / profiler tags (mirror the header)
-MAX_STACK_GROUP = 24              # blocks per resstack call (MAXSEG in csrc/gemm_common.h)
+PROTOTYPES = HEADERS['vqvae_hip.h'].prototypes
+ABI_VERSION = HEADERS['vqvae_hip.h'].version
+MAX_STACK_GROUP = 24
+# upper-case integers that mirror no macro of a public header, and why
+UNMIRRORED = (('ABI_VERSION', "the version HEADERS['vqvae_hip.h'] binds, not a macro"),
+              ('MAX_STACK_GROUP', 'blocks per resstack call: MAXSEG of csrc/gemm_common.h, a private header'))
+
+# include/vqvae_hip.h: storage bits, elementwise op codes, profiler tags, sampling modes
 STORE_X_BF16, STORE_RES_BF16 = 2, 4
 STORE_GX_BF16, STORE_GRES_BF16 = 8, 16
 STORE_GH_BF16 = 1                 # vqvae_resblock_desc.storage bits (VQVAE_STORE_*)
@@ -437,9 +469,6 @@ class HipError(RuntimeError):
 _lib = None
 
 
-ABI_VERSION = 5        # include/vqvae_hip.h: vqvae_abi_version()
-
-
 def load():
     """Loads libvqvae_hip.so (once).  Raises loudly when it has not been built."""
     global _lib
@@ -454,55 +483,16 @@ def load():
     # Must be in the environment before the HSA runtime initialises (first HIP call).
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     lib = C.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, CODEBOOK_PROTOTYPES, VQ_EMA_PROTOTYPES, KMEANS_PROTOTYPES, OPTIM_PROTOTYPES,
-                  SAMPLING_PROTOTYPES, GEN_SLOTS_PROTOTYPES, GEN_COND_PROTOTYPES, GEN_RNG_PROTOTYPES,
-                  CORPUS_PROTOTYPES, INGEST_PROTOTYPES, RAGGED_PROTOTYPES, METRICS_PROTOTYPES, PITCH_PROTOTYPES):
-        for name, (res, args) in table.items():
+    for h in HEADERS.values():
+        for name, (res, args) in h.prototypes.items():
             fn = getattr(lib, name)           # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args
-    if lib.vqvae_abi_version() != ABI_VERSION:    # the ctypes structs below mirror ONE layout of include/vqvae_hip.h
-        raise ImportError('libvqvae_hip.so at %s has ABI %d, this package binds ABI %d: rebuild it (__graft_entry__.build())'
-                          % (LIB_PATH, lib.vqvae_abi_version(), ABI_VERSION))
-    if lib.vqvae_codebook_abi_version() != CODEBOOK_ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has codebook ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (LIB_PATH, lib.vqvae_codebook_abi_version(), CODEBOOK_ABI_VERSION))
-    if lib.vqvae_vq_ema_abi_version() != VQ_EMA_ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has EMA-codebook ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (LIB_PATH, lib.vqvae_vq_ema_abi_version(), VQ_EMA_ABI_VERSION))
-    if lib.vqvae_kmeans_abi_version() != KMEANS_ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has k-means ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (LIB_PATH, lib.vqvae_kmeans_abi_version(), KMEANS_ABI_VERSION))
-    if lib.vqvae_optim_abi_version() != OPTIM_ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has optimizer-hook ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (LIB_PATH, lib.vqvae_optim_abi_version(), OPTIM_ABI_VERSION))
-    if lib.vqvae_sampling_abi_version() != SAMPLING_ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has sampling ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (LIB_PATH, lib.vqvae_sampling_abi_version(), SAMPLING_ABI_VERSION))
-    if lib.vqvae_gen_slots_abi_version() != GEN_SLOTS_ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has slot-generation ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (LIB_PATH, lib.vqvae_gen_slots_abi_version(), GEN_SLOTS_ABI_VERSION))
-    if lib.vqvae_gen_cond_abi_version() != GEN_COND_ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has latent-condition ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (LIB_PATH, lib.vqvae_gen_cond_abi_version(), GEN_COND_ABI_VERSION))
-    if lib.vqvae_gen_rng_abi_version() != GEN_RNG_ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has device-uniforms ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (LIB_PATH, lib.vqvae_gen_rng_abi_version(), GEN_RNG_ABI_VERSION))
-    if lib.vqvae_corpus_abi_version() != CORPUS_ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has resident-corpus ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (LIB_PATH, lib.vqvae_corpus_abi_version(), CORPUS_ABI_VERSION))
-    if lib.vqvae_ingest_abi_version() != INGEST_ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has ingest ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (LIB_PATH, lib.vqvae_ingest_abi_version(), INGEST_ABI_VERSION))
-    if lib.vqvae_ragged_abi_version() != RAGGED_ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has ragged-front-end ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (LIB_PATH, lib.vqvae_ragged_abi_version(), RAGGED_ABI_VERSION))
-    if lib.vqvae_metrics_abi_version() != METRICS_ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has audio-metrics ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (LIB_PATH, lib.vqvae_metrics_abi_version(), METRICS_ABI_VERSION))
-    if lib.vqvae_pitch_abi_version() != PITCH_ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has pitch ABI %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (LIB_PATH, lib.vqvae_pitch_abi_version(), PITCH_ABI_VERSION))
+    for h in HEADERS.values():                # the ctypes structs above mirror ONE layout of each header
+        has = getattr(lib, h.version_symbol)()
+        if has != h.version:
+            raise ImportError('libvqvae_hip.so at %s has %s %d, this package binds %s%d: rebuild it (__graft_entry__.build())'
+                              % (LIB_PATH, h.words, has, 'ABI ' if h.file == 'vqvae_hip.h' else '', h.version))
     _lib = lib
     return lib
 

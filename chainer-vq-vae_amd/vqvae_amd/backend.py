@@ -619,3 +619,13 @@ def workspace(nbytes, slot='main'):
         ws = DeviceArray((int(nbytes * 1.25) // 4 + 64,), np.float32)
         _state['ws'][slot] = ws
     return ws
+
+
+def described_workspace(query, d, who):
+    """(pointer or None, bytes) of the scratch that the size query named `query` asks for the description `d`;
+    (size_t)-1 is the library refusing the description, a ValueError that names the caller `who`."""
+    need = getattr(_lib.load(), query)(C.byref(d))
+    if need == C.c_size_t(-1).value:
+        raise ValueError('%s: the library refuses this description' % who)
+    ws = workspace(need) if need else None
+    return (None if ws is None else ws.ptr), need

@@ -155,20 +155,12 @@ def _desc(cfg, n, ftot, stride):
     return d
 
 
-def _workspace(query, d, who):
-    need = getattr(_lib.load(), query)(C.byref(d))
-    if need == C.c_size_t(-1).value:
-        raise ValueError('%s: the library refuses this description' % who)
-    ws = backend.workspace(need) if need else None
-    return (None if ws is None else ws.ptr), need
-
-
 def _stft_mel(cfg, tabs, x_ptr, off_in, frames, log_mel_ptr, mag_ptr, stride, mel_ptr=None):
     """One launch over a run of utterances; returns the device frame_off table (kept by the caller while it is read)."""
     frame_off = ragged.offsets(frames, total=True)
     seg = backend.to_device(np.concatenate([np.ascontiguousarray(off_in, np.int64).reshape(-1), frame_off]))
     d = _desc(cfg, len(frames), frame_off[-1], stride)
-    ws, need = _workspace('vqvae_metrics_stft_mel_workspace_bytes', d, 'features_many')
+    ws, need = backend.described_workspace('vqvae_metrics_stft_mel_workspace_bytes', d, 'features_many')
     _lib.call('vqvae_metrics_stft_mel', C.byref(d), x_ptr, seg.ptr, seg.ptr + 8 * len(frames), tabs[0].ptr, tabs[1].ptr,
               log_mel_ptr, mag_ptr, mel_ptr, ws, need, _S())
     return seg
@@ -264,7 +256,7 @@ def compare_many(reference, test, cfg, chunk_bytes=1 << 30):
             seg = _stft_mel(cfg, tabs, x_ptr, off_in, fr, lm[side].ptr, mg[side].ptr, ftot)
             del keep
         d = _desc(cfg, stop - start, ftot, ftot)
-        ws, need = _workspace('vqvae_metrics_distances_workspace_bytes', d, 'compare_many')
+        ws, need = backend.described_workspace('vqvae_metrics_distances_workspace_bytes', d, 'compare_many')
         _lib.call('vqvae_metrics_distances', C.byref(d), lm[0].ptr, lm[1].ptr, mg[0].ptr, mg[1].ptr, tabs[2].ptr,
                   seg.ptr + 8 * (stop - start), out.ptr + 24 * start, ws, need, _S())
         del seg

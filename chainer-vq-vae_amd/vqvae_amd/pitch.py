@@ -99,21 +99,13 @@ def _desc(cfg, n, ftot):
     return d
 
 
-def _workspace(query, d, who):
-    need = getattr(_lib.load(), query)(C.byref(d))
-    if need == C.c_size_t(-1).value:
-        raise ValueError('%s: the library refuses this description' % who)
-    ws = backend.workspace(need) if need else None
-    return (None if ws is None else ws.ptr), need
-
-
 def _yin(cfg, x_ptr, off_in, frames, f0_ptr, ap_ptr, who):
     """One launch over a run of utterances; returns the device table (off_in, then frame_off), kept by the caller while it
     is read."""
     frame_off = ragged.offsets(frames, total=True)
     seg = backend.to_device(np.concatenate([np.ascontiguousarray(off_in, np.int64).reshape(-1), frame_off]))
     d = _desc(cfg, len(frames), frame_off[-1])
-    ws, need = _workspace('vqvae_pitch_yin_workspace_bytes', d, who)
+    ws, need = backend.described_workspace('vqvae_pitch_yin_workspace_bytes', d, who)
     _lib.call('vqvae_pitch_yin', C.byref(d), x_ptr, seg.ptr, seg.ptr + 8 * len(frames), f0_ptr, ap_ptr, ws, need, _S())
     return seg
 
@@ -198,7 +190,7 @@ def compare_pitch_many(reference, test, cfg, chunk_bytes=1 << 30):
             seg = _yin(cfg, x_ptr, off_in, fr, f0[side].ptr, None, 'compare_pitch_many')
             del keep
         d = _desc(cfg, stop - start, int(fr.sum()))
-        ws, need = _workspace('vqvae_pitch_compare_workspace_bytes', d, 'compare_pitch_many')
+        ws, need = backend.described_workspace('vqvae_pitch_compare_workspace_bytes', d, 'compare_pitch_many')
         _lib.call('vqvae_pitch_compare', C.byref(d), f0[0].ptr, f0[1].ptr, seg.ptr + 8 * (stop - start),
                   out.ptr + 8 * len(COLUMNS) * start, ws, need, _S())
         del seg

@@ -12,7 +12,6 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'chainer-vq-vae_amd'))
-HEADER = os.path.join(ROOT, 'include', 'vqvae_hip.h')
 
 
 @pytest.fixture(scope='module')
@@ -49,15 +48,10 @@ def test_lockstep_kernels_compile_without_scratch(lockstep_meta, record_property
 
 def test_header_limits_and_prototypes():
     from vqvae_amd import _lib
-    text = open(HEADER).read()
-    assert int(re.search(r'#define\s+VQVAE_GEN_MAX_LOCKSTEP\s+(\d+)', text).group(1)) == _lib.GEN_MAX_LOCKSTEP == 128
-    assert int(re.search(r'#define\s+VQVAE_GEN_MAX_N\s+(\d+)', text).group(1)) == _lib.GEN_MAX_N == 4
+    assert _lib.GEN_MAX_LOCKSTEP == 128 and _lib.GEN_MAX_N == 4          # against the header: tests/test_host_abi.py
     assert _lib.ABI_VERSION == 5                                        # no struct change, no new export
-    body = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(vqvae_\w+)\s*\(', body))
-    assert declared == set(_lib.PROTOTYPES), (declared ^ set(_lib.PROTOTYPES))
     # the feature adds no export: generation still has exactly these entry points
-    assert sorted(n for n in declared if 'wavenet_gen' in n) == [
+    assert sorted(n for n in _lib.PROTOTYPES if 'wavenet_gen' in n) == [
         'vqvae_wavenet_gen_run', 'vqvae_wavenet_gen_run_concurrency', 'vqvae_wavenet_gen_run_workspace_bytes',
         'vqvae_wavenet_gen_step']
 

@@ -15,7 +15,6 @@ from vqvae_amd import _lib
 from vqvae_amd.generation import plan_lockstep, plan_refill, refill_queue, refill_slots, run_lockstep_refill
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'vqvae_gen_slots.h')
 
 
 # ---- the scheduler's rule on the host -------------------------------------------------------------------------------
@@ -72,23 +71,10 @@ def test_plan_refill_between_the_lower_bound_and_sorted_groups():
 
 # ---- the header, the table, the library -----------------------------------------------------------------------------
 def test_header_exports_are_the_bound_table_and_versions_stand():
-    text = open(HEADER).read()
-    body = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(vqvae_\w+)\s*\(', body))
-    assert declared == set(_lib.GEN_SLOTS_PROTOTYPES) == {'vqvae_gen_slots_abi_version', 'vqvae_gen_slots_init',
-                                                          'vqvae_wavenet_gen_step_slots'}
-    lib = _lib.load()
-    for name in _lib.GEN_SLOTS_PROTOTYPES:
-        assert getattr(lib, name) is not None
-    assert lib.vqvae_gen_slots_abi_version() == _lib.GEN_SLOTS_ABI_VERSION == 1
-    assert lib.vqvae_abi_version() == _lib.ABI_VERSION == 5 and lib.vqvae_sampling_abi_version() == 1
-    assert not set(_lib.GEN_SLOTS_PROTOTYPES) & (set(_lib.PROTOTYPES) | set(_lib.SAMPLING_PROTOTYPES))
-    struct = re.search(r'typedef struct \{(.*?)\}\s*vqvae_gen_slots;', body, re.S).group(1)
-    assert [f[0] for f in _lib.GenSlots._fields_] == re.findall(r'(\w+);', struct)
-    kinds = ['int' if re.search(r'\bint\s+%s;' % f[0], struct) else 'ptr' for f in _lib.GenSlots._fields_]
-    assert kinds == ['int' if f[1] is C.c_int else 'ptr' for f in _lib.GenSlots._fields_]
-    makefile = open(os.path.join(ROOT, 'chainer-vq-vae_amd', 'csrc', 'Makefile')).read()
-    assert 'generate_slots.hip' in makefile and 'vqvae_gen_slots.h' in makefile and 'gen_lockstep_body.h' in makefile
+    """The header, the library, the versions and vqvae_gen_slots' layout: tests/test_host_abi.py, for every header."""
+    assert set(_lib.HEADERS['vqvae_gen_slots.h'].prototypes) == {'vqvae_gen_slots_abi_version', 'vqvae_gen_slots_init',
+                                                                 'vqvae_wavenet_gen_step_slots'}
+    assert 'generate_slots.hip' in open(os.path.join(ROOT, 'chainer-vq-vae_amd', 'csrc', 'Makefile')).read()
 
 
 def test_c_side_validation_needs_no_device():

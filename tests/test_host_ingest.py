@@ -421,35 +421,18 @@ NAMES = {'vqvae_ingest_abi_version', 'vqvae_ingest_workspace_bytes', 'vqvae_inge
 
 
 def test_header_exports_are_the_bound_table_and_versions_stand():
+    """The header, the library, the versions and _lib's constants: tests/test_host_abi.py, for every header."""
     text = open(HEADER).read()
-    body = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(vqvae_\w+)\s*\(', body))
-    assert declared == set(_lib.INGEST_PROTOTYPES) == NAMES
-    lib = _lib.load()
-    assert lib.vqvae_ingest_abi_version() == _lib.INGEST_ABI_VERSION == 1
-    assert lib.vqvae_abi_version() == _lib.ABI_VERSION == 5
-    for name in ('codebook', 'vq_ema', 'kmeans', 'optim', 'sampling', 'gen_slots', 'gen_cond', 'gen_rng', 'corpus'):
-        assert getattr(lib, 'vqvae_%s_abi_version' % name)() == 1, name
-    others = (_lib.PROTOTYPES, _lib.CODEBOOK_PROTOTYPES, _lib.VQ_EMA_PROTOTYPES, _lib.KMEANS_PROTOTYPES, _lib.OPTIM_PROTOTYPES,
-              _lib.SAMPLING_PROTOTYPES, _lib.GEN_SLOTS_PROTOTYPES, _lib.GEN_COND_PROTOTYPES, _lib.GEN_RNG_PROTOTYPES,
-              _lib.CORPUS_PROTOTYPES)
-    for table in others:
-        assert not NAMES & set(table)
-    for name, (_, args) in _lib.INGEST_PROTOTYPES.items():
-        proto = re.search(r'\b%s\((.*?)\);' % name, body, re.S).group(1)
-        assert len([a for a in proto.split(',') if a.strip() != 'void']) == len(args), name
-    for macro, value in (('VQVAE_INGEST_TILE', _lib.INGEST_TILE), ('VQVAE_INGEST_MAX_TAPS', _lib.INGEST_MAX_TAPS),
-                         ('VQVAE_INGEST_MAX_WINDOW', _lib.INGEST_MAX_WINDOW), ('VQVAE_INGEST_I16', G.FMT_I16),
-                         ('VQVAE_INGEST_F32', G.FMT_F32), ('VQVAE_INGEST_BAD_SAMPLE', G.BAD_SAMPLE),
+    assert set(_lib.HEADERS['vqvae_ingest.h'].prototypes) == NAMES
+    for macro, value in (('VQVAE_INGEST_I16', G.FMT_I16), ('VQVAE_INGEST_F32', G.FMT_F32), ('VQVAE_INGEST_BAD_SAMPLE', G.BAD_SAMPLE),
                          ('VQVAE_INGEST_ZERO_PEAK', G.ZERO_PEAK), ('VQVAE_INGEST_EMPTY', G.EMPTY)):
-        assert eval(re.search(r'#define %s\s+(\(?[\d <]+\)?)' % macro, body).group(1)) == value, macro
+        assert int(re.search(r'#define %s\s+(\d+)\s' % macro, text).group(1)) == value, macro
     assert _lib.INGEST_TILE == G.TILE == TILE
     for word in ('[resampy-recalled]', '[librosa-recalled]', 'No bit parity with librosa', '8.555504641634386', '14.769656459379492',
                  '0.9475937167399596'):
         assert word in ' '.join(text.replace('*', ' ').split()), word
     assert 'ingest' not in open(os.path.join(ROOT, 'include', 'vqvae_hip.h')).read()
-    makefile = open(os.path.join(CSRC, 'Makefile')).read()
-    assert 'ingest.hip' in makefile and 'ingest_rule.h ' in makefile and 'vqvae_ingest.h' in makefile
+    assert 'ingest.hip' in open(os.path.join(CSRC, 'Makefile')).read()
 
 
 def test_c_side_validation_needs_no_device():

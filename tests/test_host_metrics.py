@@ -2,7 +2,6 @@
 planner, every argument error (all raised before anything touches a device) and the exported symbols."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -153,31 +152,13 @@ def test_header_exports_are_the_bound_table():
     import vqvae_amd as V
     for name in ('MelConfig', 'RaggedFeatures', 'features_many', 'compare_many'):
         assert getattr(V, name) is getattr(metrics, name)
-    text = open(HEADER).read()
-    body = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(vqvae_\w+)\s*\(', body))
-    assert declared == set(_lib.METRICS_PROTOTYPES) == NAMES
-    lib = _lib.load()
-    for name in NAMES:
-        assert getattr(lib, name) is not None
-    assert lib.vqvae_metrics_abi_version() == _lib.METRICS_ABI_VERSION == 1
-    assert lib.vqvae_abi_version() == _lib.ABI_VERSION == 5 and lib.vqvae_ragged_abi_version() == 1
-    for table in (_lib.PROTOTYPES, _lib.CORPUS_PROTOTYPES, _lib.INGEST_PROTOTYPES, _lib.RAGGED_PROTOTYPES):
-        assert not NAMES & set(table)
-    struct = re.search(r'typedef struct \{(.*?)\}\s*vqvae_metrics_desc;', body, re.S).group(1)
-    fields = [f for decl in re.findall(r'(?:int\d+_t|float)\s+([\w, ]+);', struct) for f in re.split(r',\s*', decl)]
-    assert [f[0] for f in _lib.MetricsDesc._fields_] == fields
-    assert C.sizeof(_lib.MetricsDesc) == 40 and _lib.MetricsDesc.ftot.offset == 24
+    table = _lib.HEADERS['vqvae_metrics.h'].prototypes         # against the header and the library: tests/test_host_abi.py
+    assert set(table) == NAMES
     for name, n_args in (('vqvae_metrics_stft_mel', 12), ('vqvae_metrics_distances', 11)):
-        proto = re.search(r'int %s\((.*?)\);' % name, body, re.S).group(1)
-        assert len(proto.split(',')) == len(_lib.METRICS_PROTOTYPES[name][1]) == n_args
-    for macro, value in (('TILE', _lib.METRICS_TILE), ('THREADS', _lib.METRICS_THREADS), ('MAX_NFFT', _lib.METRICS_MAX_NFFT),
-                         ('MAX_MELS', _lib.METRICS_MAX_MELS)):
-        assert int(re.search(r'#define VQVAE_METRICS_%s (\d+)' % macro, text).group(1)) == value
-    assert repr(R.DB) in text and R.DB == 10.0 / np.log(10.0) and R.THREADS == _lib.METRICS_THREADS
+        assert len(table[name][1]) == n_args
+    assert repr(R.DB) in open(HEADER).read() and R.DB == 10.0 / np.log(10.0) and R.THREADS == _lib.METRICS_THREADS
     assert 'metrics' not in open(os.path.join(ROOT, 'include', 'vqvae_hip.h')).read()
-    makefile = open(os.path.join(CSRC, 'Makefile')).read()
-    assert 'audio_metrics.hip' in makefile and 'vqvae_metrics.h' in makefile
+    assert 'audio_metrics.hip' in open(os.path.join(CSRC, 'Makefile')).read()
 
 
 def test_c_side_validation_needs_no_device():

@@ -23,14 +23,8 @@ AWKWARD = [1, 7, CHUNK + 1, 0, CHUNK, 3 * CHUNK + 1, 3]
 
 
 def test_constants_mirror_the_header():
-    text = open(os.path.join(ROOT, 'include', 'vqvae_optim.h')).read()
-    for name, value in (('CHUNK', _lib.OPTIM_CHUNK), ('THREADS', _lib.OPTIM_THREADS),
-                        ('STATE_HEADER', _lib.OPTIM_STATE_HEADER), ('GUARD', _lib.OPTIM_GUARD)):
-        m = re.search(r'#define\s+VQVAE_OPTIM_%s\s+(\d+)' % name, text)
-        assert m and int(m.group(1)) == value, name
+    """_lib's constants against the header's macros: tests/test_host_abi.py; the restatement mirrors _lib."""
     assert (R.CHUNK, R.THREADS) == (_lib.OPTIM_CHUNK, _lib.OPTIM_THREADS)
-    for name in _lib.OPTIM_PROTOTYPES:
-        assert re.search(r'\b%s\s*\(' % name, text), name
 
 
 @pytest.mark.parametrize('sizes', [AWKWARD, [5], [CHUNK], [0, 0, 2], [2 * CHUNK, 1, 1, CHUNK - 1]])

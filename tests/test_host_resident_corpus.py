@@ -274,28 +274,13 @@ NAMES = {'vqvae_corpus_abi_version', 'vqvae_corpus_draw'}
 
 
 def test_header_exports_are_the_bound_table_and_versions_stand():
-    text = open(HEADER).read()
-    body = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(vqvae_\w+)\s*\(', body))
-    assert declared == set(_lib.CORPUS_PROTOTYPES) == NAMES
-    lib = _lib.load()
-    for name in _lib.CORPUS_PROTOTYPES:
-        assert getattr(lib, name) is not None
-    assert lib.vqvae_corpus_abi_version() == _lib.CORPUS_ABI_VERSION == 1
-    assert lib.vqvae_abi_version() == _lib.ABI_VERSION == 5 and lib.vqvae_gen_rng_abi_version() == 1
-    others = (_lib.PROTOTYPES, _lib.CODEBOOK_PROTOTYPES, _lib.VQ_EMA_PROTOTYPES, _lib.KMEANS_PROTOTYPES, _lib.OPTIM_PROTOTYPES,
-              _lib.SAMPLING_PROTOTYPES, _lib.GEN_SLOTS_PROTOTYPES, _lib.GEN_COND_PROTOTYPES, _lib.GEN_RNG_PROTOTYPES)
-    for table in others:
-        assert not NAMES & set(table)
-    struct = re.search(r'typedef struct \{(.*?)\}\s*vqvae_corpus;', body, re.S).group(1)
-    assert [f[0] for f in _lib.Corpus._fields_] == re.findall(r'(\w+);', struct) == ['samples', 'offset', 'length', 'speaker',
-                                                                                     'view', 'n_view']
-    assert _lib.Corpus._fields_[5][1] is C.c_int32 and C.sizeof(_lib.Corpus) == 48
-    proto = re.search(r'int vqvae_corpus_draw\((.*?)\);', body, re.S).group(1)
-    assert len(proto.split(',')) == len(_lib.CORPUS_PROTOTYPES['vqvae_corpus_draw'][1]) == 18
+    """The header, the library, the versions and vqvae_corpus' layout: tests/test_host_abi.py, for every header."""
+    table = _lib.HEADERS['vqvae_corpus.h'].prototypes
+    assert set(table) == NAMES and len(table['vqvae_corpus_draw'][1]) == 18
+    assert [f[0] for f in _lib.Corpus._fields_] == ['samples', 'offset', 'length', 'speaker', 'view', 'n_view']
+    assert _lib.Corpus._fields_[5][1] is C.c_int32
     assert 'corpus' not in open(os.path.join(ROOT, 'include', 'vqvae_hip.h')).read()
-    makefile = open(os.path.join(CSRC, 'Makefile')).read()
-    assert 'corpus.hip' in makefile and 'vqvae_corpus.h' in makefile and 'corpus_rule.h ' in makefile
+    assert 'corpus.hip' in open(os.path.join(CSRC, 'Makefile')).read()
 
 
 def test_c_side_validation_needs_no_device():

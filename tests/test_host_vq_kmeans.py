@@ -12,7 +12,7 @@ import pytest
 
 import vq_ema_ref as E
 import vq_kmeans_ref as R
-from test_host_vq_ema import _Upd, _exports, _meta
+from test_host_vq_ema import _Upd, _meta
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'chainer-vq-vae_amd', 'csrc')
@@ -21,31 +21,12 @@ NAMES = {'vqvae_kmeans_abi_version', 'vqvae_kmeans_workspace_bytes', 'vqvae_kmea
 
 
 def test_header_matches_its_prototype_table_and_the_library():
+    """The header, the library, the version and the macros: tests/test_host_abi.py, for every header."""
     from vqvae_amd import _lib
-    assert set(_exports('vqvae_kmeans.h')) == set(_lib.KMEANS_PROTOTYPES) == NAMES
-    lib = _lib.load()
-    for name, (res, args) in _lib.KMEANS_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-    assert lib.vqvae_kmeans_abi_version() == 1 == _lib.KMEANS_ABI_VERSION
-    header = open(os.path.join(ROOT, 'include', 'vqvae_kmeans.h')).read()
-    for macro, value in (('BLOCK', _lib.KMEANS_BLOCK), ('MAX_D', _lib.KMEANS_MAX_D)):
-        assert re.search(r'#define VQVAE_KMEANS_%s\s+%d\b' % (macro, value), header), macro
-    assert re.search(r'#define VQVAE_KMEANS_MAX_N\s+\(1 << 24\)', header) and _lib.KMEANS_MAX_N == 1 << 24 == _lib.VQ_EMA_MAX_N
+    assert set(_lib.HEADERS['vqvae_kmeans.h'].prototypes) == NAMES
+    assert _lib.KMEANS_MAX_N == 1 << 24 == _lib.VQ_EMA_MAX_N
     assert R.BLOCK == _lib.KMEANS_BLOCK
-    makefile = open(os.path.join(CSRC, 'Makefile')).read()
-    assert 'vq_kmeans.hip' in makefile and 'vqvae_kmeans.h' in makefile
-
-
-def test_the_three_existing_headers_are_untouched():
-    from vqvae_amd import _lib
-    old = _exports('vqvae_hip.h')
-    assert len(old) == 127 and set(old) == set(_lib.PROTOTYPES)
-    assert len(_exports('vqvae_codebook.h')) == 3 and set(_exports('vqvae_codebook.h')) == set(_lib.CODEBOOK_PROTOTYPES)
-    assert len(_exports('vqvae_vq_ema.h')) == 5 and set(_exports('vqvae_vq_ema.h')) == set(_lib.VQ_EMA_PROTOTYPES)
-    assert not (set(_lib.PROTOTYPES) | set(_lib.CODEBOOK_PROTOTYPES) | set(_lib.VQ_EMA_PROTOTYPES)) & NAMES
-    lib = _lib.load()
-    assert (lib.vqvae_abi_version(), lib.vqvae_codebook_abi_version(), lib.vqvae_vq_ema_abi_version()) == (5, 1, 1)
+    assert 'vq_kmeans.hip' in open(os.path.join(CSRC, 'Makefile')).read()
 
 
 def test_entry_points_reject_bad_arguments_without_a_device():
