@@ -19,5 +19,6 @@ from .ingest import (DeviceIngest, corpus_files, read_wav, resample_taps, write_
 from .frontend import (LatentCodes, condition_many, encode_many, frontend_many, plan_chunks)  # noqa: F401
 from .metrics import MelConfig, RaggedFeatures, compare_many, features_many  # noqa: F401
 from .pitch import PitchConfig, RaggedPitch, compare_pitch_many, pitch_many  # noqa: F401
+from .scoring import Scores, evaluate_many, score_many  # noqa: F401
 from .synthesis import synthesize, synthesize_many  # noqa: F401
 from .reporting import LogReport, PlotReport, PrintReport  # noqa: F401

@@ -124,6 +124,12 @@ class _Utterances(object):
         from .frontend import encode_corpus
         return encode_corpus(self, encoder, vq, chunk_bytes)
 
+    def score(self, wavenet, condition, chunk_bytes=1 << 30, per_sample=False, return_logits=False):
+        """The likelihood of these utterances under ``wavenet`` given ``condition`` (scoring.Scores): the samples are
+        binned in place from the corpus buffer; see scoring.score_many."""
+        from .scoring import score_many
+        return score_many(wavenet, condition, self, chunk_bytes, per_sample, return_logits)
+
 
 class ResidentCorpus(_Utterances):
     """``waves``: loaded, silence-trimmed waveforms (what inputs.crop_or_pad takes); ``speakers``: one int id each.
