@@ -20,5 +20,6 @@ from .frontend import (LatentCodes, condition_many, encode_many, frontend_many, 
 from .metrics import MelConfig, RaggedFeatures, compare_many, features_many  # noqa: F401
 from .pitch import PitchConfig, RaggedPitch, compare_pitch_many, pitch_many  # noqa: F401
 from .scoring import Scores, evaluate_many, score_many  # noqa: F401
+from .alignment import Alignment, align_many, compare_aligned_many  # noqa: F401
 from .synthesis import synthesize, synthesize_many  # noqa: F401
 from .reporting import LogReport, PlotReport, PrintReport  # noqa: F401
