@@ -399,6 +399,121 @@ extern "C" int vqvae_conv1d_pack(int n, const vqvae_conv1d_desc* descs, const fl
   return 0;
 }
 
+// The argument blocks of the three generic conv launches, from the desc and the pointers alone: what the entry points hand
+// launch_gemm / launch_wgrad, and what vqvae_conv1d_forms takes through the same dispatch without launching.
+// pk: the packed slab; f16: a float32x2 launch, with the operand's and the weights' maxima
+static void conv_fwd_args(GemmArgs& g, const vqvae_conv1d_desc* d, const ConvPlan& c, const float* x, const float* pk,
+                          const float* b, float* y, bool f16, const unsigned* xam, const unsigned* wam, unsigned* amax_out,
+                          const int32_t* skip_flag, void* ws, size_t ws_bytes) {
+  const int ldw = pad128(d->Cout), rp = slab_rows(d->Cin);
+  memset(&g, 0, sizeof(g));
+  g.nseg = d->K;
+  g.f16x2 = f16 ? 1 : 0;
+  for (int j = 0; j < d->K; ++j) {
+    Seg& sg = g.seg[j];
+    sg.x = x; sg.x_bstride = (long)d->Cin * d->Tin; sg.x_cstride = d->Tin; sg.cin = d->Cin; sg.Tin = d->Tin;
+    sg.tmul = d->stride; sg.toff = j * d->dil - d->pad; sg.tdiv = 1;
+    sg.w = pk + (size_t)j * rp * ldw; sg.ldw = ldw;
+    if (f16) { sg.amax = xam; sg.wamax = wam; }
+  }
+  g.M = d->Cout; g.Tout = d->Tout; g.B = d->B;
+  g.out[0].y = y; g.out[0].y_bstride = (long)d->Cout * d->Tout; g.out[0].rows = d->Cout;
+  g.out[0].bias = b; g.out[0].relu = d->relu;
+  g.out[0].amax_out = amax_out;
+  g.skip_flag = skip_flag;
+  if (c.partial_bytes[0] > 0 && c.partial[0] + c.partial_bytes[0] <= ws_bytes) g.partial = (float*)((char*)ws + c.partial[0]);
+}
+static void conv_bwd_data_args(GemmArgs& g, const vqvae_conv1d_desc* d, const ConvPlan& c, const float* pk, const float* gy,
+                               float* gx, int accumulate, bool f16, const unsigned* gam, const unsigned* wam,
+                               unsigned* amax_out, const float* x_relu, void* ws, size_t ws_bytes) {
+  const int ldw = pad128(d->Cin), rp = slab_rows(d->Cout);
+  memset(&g, 0, sizeof(g));
+  g.nseg = d->K;
+  g.f16x2 = f16 ? 1 : 0;
+  for (int j = 0; j < d->K; ++j) {
+    Seg& sg = g.seg[j];
+    sg.x = gy; sg.x_bstride = (long)d->Cout * d->Tout; sg.x_cstride = d->Tout; sg.cin = d->Cout; sg.Tin = d->Tout;
+    // t_out(gy) = (u + pad - j*dil) / stride
+    sg.tmul = 1; sg.toff = d->pad - j * d->dil; sg.tdiv = d->stride;
+    sg.w = pk + (size_t)j * rp * ldw; sg.ldw = ldw;
+    if (f16) { sg.amax = gam; sg.wamax = wam; }
+  }
+  g.M = d->Cin; g.Tout = d->Tin; g.B = d->B;
+  g.out[0].y = gx; g.out[0].y_bstride = (long)d->Cin * d->Tin; g.out[0].rows = d->Cin;
+  g.out[0].accumulate = accumulate;
+  g.out[0].amax_out = amax_out;
+  if (x_relu) { g.out[0].add = x_relu; g.out[0].add_bstride = (long)d->Cin * d->Tin; g.out[0].add_is_mask = 1; }
+  if (c.partial_bytes[1] > 0 && c.partial[1] + c.partial_bytes[1] <= ws_bytes) g.partial = (float*)((char*)ws + c.partial[1]);
+}
+// xe / xo: the even and the odd phase of x (phases); f16: a float32x2 launch, with both operands' maxima
+static void conv_bwd_weight_args(WgradArgs& w, const vqvae_conv1d_desc* d, const float* x, const float* gy, float* gW, float* gb,
+                                 int accumulate, bool phases, const float* xe, const float* xo, bool f16, const unsigned* xam,
+                                 const unsigned* gam, const int32_t* skip_flag) {
+  const int Tp = phase_pitch(d);
+  memset(&w, 0, sizeof(w));
+  w.gy = gy; w.gy_bstride = (long)d->Cout * d->Tout; w.M = d->Cout; w.Tout = d->Tout; w.B = d->B;
+  w.nseg = d->K;
+  for (int j = 0; j < d->K; ++j) {
+    WSeg& sg = w.seg[j];
+    const int e = j * d->dil - d->pad;
+    if (phases) {
+      const bool odd = (e & 1) != 0;
+      sg.x = odd ? xo : xe; sg.x_bstride = (long)d->Cin * Tp; sg.x_cstride = Tp; sg.cin = d->Cin;
+      sg.Tin = odd ? d->Tin / 2 : (d->Tin + 1) / 2;
+      sg.tmul = 1; sg.toff = odd ? (e - 1) >> 1 : e >> 1; sg.tdiv = 1;       // (arithmetic shifts: floor for negative e)
+    } else {
+      sg.x = x; sg.x_bstride = (long)d->Cin * d->Tin; sg.x_cstride = d->Tin; sg.cin = d->Cin; sg.Tin = d->Tin;
+      sg.tmul = d->stride; sg.toff = e; sg.tdiv = 1;
+    }
+    sg.gw = gW + j; sg.gw_co_stride = (long)d->Cin * d->K; sg.gw_ci_stride = d->K;
+  }
+  w.seg[0].gb = gb; w.accumulate = accumulate;
+  w.skip_flag = skip_flag;
+  if (f16) {
+    w.f16x2 = 1; w.amax_gy = gam;
+    for (int j = 0; j < d->K; ++j) w.seg[j].amax_x = xam;
+  }
+}
+// whether the weight-gradient launch runs float32x2: never over the phase split, never under a skip flag
+static bool conv_wgrad_f16x2(const vqvae_conv1d_desc* d, const ConvPlan& c, bool phases, const int32_t* skip_flag, size_t ws_bytes) {
+  return conv_f16x2(d) && !phases && d->stride == 1 && skip_flag == nullptr && ws_bytes >= c.total;
+}
+
+extern "C" int vqvae_conv1d_forms(const vqvae_conv1d_desc* d, int which) {
+  if (which < 0 || which > 2 || check_conv_desc(d) != 0) return -1;
+  const ConvPlan c = conv_plan(d);
+  // 16-byte aligned bases nobody dereferences, 2^40 apart; the workspace as vqvae_conv1d_workspace_bytes sizes it
+  auto base = [](int i) { return (char*)((uintptr_t)(i + 1) << 40); };
+  float* x = (float*)base(0); float* y = (float*)base(1); float* W = (float*)base(2); float* b = (float*)base(3);
+  char* ws = base(4);
+  const size_t ws_bytes = c.total;
+  unsigned* am = (unsigned*)(ws + c.amax);
+  int r = 0;
+  if (which == 2) {
+    const bool phases = c.phase_end && c.phase_end <= ws_bytes;
+    const bool f16 = conv_wgrad_f16x2(d, c, phases, nullptr, ws_bytes);
+    WgradArgs w;
+    conv_bwd_weight_args(w, d, x, y, W, b, 0, phases, (float*)(ws + c.phase_e), (float*)(ws + c.phase_o), f16, am, am + AMAX_SLOTS, nullptr);
+    WgradFormInfo o;
+    if (wgrad_form(w, c.wg, (float*)ws, o) != 0) return -1;
+    r = o.family | (o.np << VQVAE_CONV_FORM_NP_SHIFT) | (o.rows256 ? VQVAE_CONV_FORM_ROWS256 : 0) |
+        (phases ? VQVAE_CONV_FORM_PHASES : 0) | (o.nsplit > 1 ? VQVAE_CONV_FORM_SPLIT : 0);
+    for (int j = 0; j < w.nseg; ++j) if (w.seg[j].tmul != 1 || w.seg[j].tdiv != 1) r |= VQVAE_CONV_FORM_STRIDED;
+    return r;
+  }
+  const bool f16 = conv_f16x2(d);
+  GemmArgs g;
+  if (which == 0) conv_fwd_args(g, d, c, x, (float*)ws, b, y, f16, am, am + AMAX_SLOTS, nullptr, nullptr, ws, ws_bytes);
+  else conv_bwd_data_args(g, d, c, (float*)ws, y, x, 0, f16, am, am + AMAX_SLOTS, nullptr, nullptr, ws, ws_bytes);
+  GemmFormInfo o;
+  if (gemm_form_linear(g, o) != 0) return -1;
+  r = o.family | (o.np << VQVAE_CONV_FORM_NP_SHIFT);
+  if (o.family == VQVAE_CONV_GEMM_LIN128) return r;
+  return r | (o.rows256 ? VQVAE_CONV_FORM_ROWS256 : 0) | (o.nb == 2 ? VQVAE_CONV_FORM_WIDE : 0) | (o.tap2 ? VQVAE_CONV_FORM_TAP2 : 0) |
+         (o.lean ? VQVAE_CONV_FORM_LEAN : 0) | (o.halved ? VQVAE_CONV_FORM_HALVED : 0) | (o.ksplit > 1 ? VQVAE_CONV_FORM_SPLIT : 0) |
+         (o.strided ? VQVAE_CONV_FORM_STRIDED : 0);
+}
+
 static int conv1d_fwd_impl(const vqvae_conv1d_desc* d, const float* x, const float* W, const float* b, float* y,
                            void* ws, size_t ws_bytes, const int32_t* skip_flag, const vqvae_conv1d_amax* cam,
                            vqvae_stream_t s);
@@ -425,7 +540,7 @@ static int conv1d_fwd_impl(const vqvae_conv1d_desc* d, const float* x, const flo
   if (int e = check_conv_desc(d)) return e;
   VQ_REQUIRE(x && W && y && ws, "conv1d_fwd: null pointer");
   hipStream_t st = (hipStream_t)s;
-  const int ldw = pad128(d->Cout), rp = slab_rows(d->Cin);
+  const int ldw = pad128(d->Cout);
   const ConvPlan c = conv_plan(d);
   if (c.slab_bytes[0] > ws_bytes) { set_error("conv1d_fwd: workspace too small"); return VQVAE_E_WORKSPACE; }
   const void* pre = (cam && skip_flag == nullptr) ? cam->packed : nullptr;      // packed ahead (vqvae_conv1d_pack)
@@ -446,22 +561,8 @@ static int conv1d_fwd_impl(const vqvae_conv1d_desc* d, const float* x, const flo
     pa.job[0].amax = wam;
     if (int e = launch_pack(pa, st, f16 ? 3 : -1)) return e;
   }
-  GemmArgs g; memset(&g, 0, sizeof(g));
-  g.nseg = d->K;
-  g.f16x2 = f16 ? 1 : 0;
-  for (int j = 0; j < d->K; ++j) {
-    Seg& sg = g.seg[j];
-    sg.x = x; sg.x_bstride = (long)d->Cin * d->Tin; sg.x_cstride = d->Tin; sg.cin = d->Cin; sg.Tin = d->Tin;
-    sg.tmul = d->stride; sg.toff = j * d->dil - d->pad; sg.tdiv = 1;
-    sg.w = pk + (size_t)j * rp * ldw; sg.ldw = ldw;
-    if (f16) { sg.amax = xam; sg.wamax = wam; }
-  }
-  g.M = d->Cout; g.Tout = d->Tout; g.B = d->B;
-  g.out[0].y = y; g.out[0].y_bstride = (long)d->Cout * d->Tout; g.out[0].rows = d->Cout;
-  g.out[0].bias = b; g.out[0].relu = d->relu;
-  g.out[0].amax_out = cam ? cam->out : nullptr;
-  g.skip_flag = skip_flag;
-  if (c.partial_bytes[0] > 0 && c.partial[0] + c.partial_bytes[0] <= ws_bytes) g.partial = (float*)((char*)ws + c.partial[0]);
+  GemmArgs g;
+  conv_fwd_args(g, d, c, x, pk, b, y, f16, xam, wam, cam ? cam->out : nullptr, skip_flag, ws, ws_bytes);
   return launch_gemm<EPI_LINEAR>(g, VQVAE_PROF_CONV_FWD, st);
 }
 
@@ -488,7 +589,7 @@ static int conv1d_bwd_data_impl(const vqvae_conv1d_desc* d, const float* W, cons
   VQ_REQUIRE(!x_relu || !accumulate, "conv1d_bwd_data_relu: the ReLU mask applies to a freshly written gx (accumulate == 0)");
   VQ_REQUIRE(W && gy && gx && ws, "conv1d_bwd_data: null pointer");
   hipStream_t st = (hipStream_t)s;
-  const int ldw = pad128(d->Cin), rp = slab_rows(d->Cout);
+  const int ldw = pad128(d->Cin);
   const ConvPlan c = conv_plan(d);
   if (c.slab_bytes[1] > ws_bytes) { set_error("conv1d_bwd_data: workspace too small"); return VQVAE_E_WORKSPACE; }
   const void* pre = cam ? cam->packed : nullptr;      // packed ahead (vqvae_conv1d_pack, backward form)
@@ -509,23 +610,8 @@ static int conv1d_bwd_data_impl(const vqvae_conv1d_desc* d, const float* W, cons
     pa.job[0].amax = wam;
     if (int e = launch_pack(pa, st, f16 ? 3 : -1)) return e;
   }
-  GemmArgs g; memset(&g, 0, sizeof(g));
-  g.nseg = d->K;
-  g.f16x2 = f16 ? 1 : 0;
-  for (int j = 0; j < d->K; ++j) {
-    Seg& sg = g.seg[j];
-    sg.x = gy; sg.x_bstride = (long)d->Cout * d->Tout; sg.x_cstride = d->Tout; sg.cin = d->Cout; sg.Tin = d->Tout;
-    // t_out(gy) = (u + pad - j*dil) / stride
-    sg.tmul = 1; sg.toff = d->pad - j * d->dil; sg.tdiv = d->stride;
-    sg.w = pk + (size_t)j * rp * ldw; sg.ldw = ldw;
-    if (f16) { sg.amax = gam; sg.wamax = wam; }
-  }
-  g.M = d->Cin; g.Tout = d->Tin; g.B = d->B;
-  g.out[0].y = gx; g.out[0].y_bstride = (long)d->Cin * d->Tin; g.out[0].rows = d->Cin;
-  g.out[0].accumulate = accumulate;
-  g.out[0].amax_out = cam ? cam->out : nullptr;
-  if (x_relu) { g.out[0].add = x_relu; g.out[0].add_bstride = (long)d->Cin * d->Tin; g.out[0].add_is_mask = 1; }
-  if (c.partial_bytes[1] > 0 && c.partial[1] + c.partial_bytes[1] <= ws_bytes) g.partial = (float*)((char*)ws + c.partial[1]);
+  GemmArgs g;
+  conv_bwd_data_args(g, d, c, pk, gy, gx, accumulate, f16, gam, wam, cam ? cam->out : nullptr, x_relu, ws, ws_bytes);
   return launch_gemm<EPI_LINEAR>(g, VQVAE_PROF_CONV_BWD_DATA, st);
 }
 
@@ -557,9 +643,6 @@ static int conv1d_bwd_weight_impl(const vqvae_conv1d_desc* d, const float* x, co
   const ConvPlan c = conv_plan(d);
   const WgradPlan& p = c.wg;
   if (wgrad_bytes(p) > ws_bytes) { set_error("conv1d_bwd_weight: workspace too small"); return VQVAE_E_WORKSPACE; }
-  WgradArgs w; memset(&w, 0, sizeof(w));
-  w.gy = gy; w.gy_bstride = (long)d->Cout * d->Tout; w.M = d->Cout; w.Tout = d->Tout; w.B = d->B;
-  w.nseg = d->K;
   const bool phases = c.phase_end && c.phase_end <= ws_bytes;
   float* xe = nullptr;
   float* xo = nullptr;
@@ -573,26 +656,13 @@ static int conv1d_bwd_weight_impl(const vqvae_conv1d_desc* d, const float* x, co
     hipLaunchKernelGGL(phase_split_kernel, dim3((unsigned)nb), dim3(256), 0, st, x, rows, d->Tin, Tp, xe, xo, skip_flag);
     VQ_LAUNCH_CHECK();
   }
-  for (int j = 0; j < d->K; ++j) {
-    WSeg& sg = w.seg[j];
-    const int e = j * d->dil - d->pad;
-    if (phases) {
-      const bool odd = (e & 1) != 0;
-      sg.x = odd ? xo : xe; sg.x_bstride = (long)d->Cin * Tp; sg.x_cstride = Tp; sg.cin = d->Cin;
-      sg.Tin = odd ? d->Tin / 2 : (d->Tin + 1) / 2;
-      sg.tmul = 1; sg.toff = odd ? (e - 1) >> 1 : e >> 1; sg.tdiv = 1;       // (arithmetic shifts: floor for negative e)
-    } else {
-      sg.x = x; sg.x_bstride = (long)d->Cin * d->Tin; sg.x_cstride = d->Tin; sg.cin = d->Cin; sg.Tin = d->Tin;
-      sg.tmul = d->stride; sg.toff = e; sg.tdiv = 1;
-    }
-    sg.gw = gW + j; sg.gw_co_stride = (long)d->Cin * d->K; sg.gw_ci_stride = d->K;
-  }
-  w.seg[0].gb = gb; w.accumulate = accumulate;
-  w.skip_flag = skip_flag;
-  if (conv_f16x2(d) && !phases && d->stride == 1 && skip_flag == nullptr && ws_bytes >= c.total) {
+  const bool f16 = conv_wgrad_f16x2(d, c, phases, skip_flag, ws_bytes);
+  const unsigned* xam = nullptr;
+  const unsigned* gam = nullptr;
+  if (f16) {
     unsigned* am = (unsigned*)((char*)ws + c.amax);
-    const unsigned* xam = am;
-    const unsigned* gam = am + AMAX_SLOTS;
+    xam = am;
+    gam = am + AMAX_SLOTS;
     if (cam && cam->x) xam = cam->x;
     else {
       VQ_CHECK_HIP(hipMemsetAsync(am, 0, AMAX_SLOTS * sizeof(unsigned), st));
@@ -603,9 +673,9 @@ static int conv1d_bwd_weight_impl(const vqvae_conv1d_desc* d, const float* x, co
       VQ_CHECK_HIP(hipMemsetAsync(am + AMAX_SLOTS, 0, AMAX_SLOTS * sizeof(unsigned), st));
       if (int e = launch_absmax(gy, (long)d->B * d->Cout * d->Tout, am + AMAX_SLOTS, st)) return e;
     }
-    w.f16x2 = 1; w.amax_gy = gam;
-    for (int j = 0; j < d->K; ++j) w.seg[j].amax_x = xam;
   }
+  WgradArgs w;
+  conv_bwd_weight_args(w, d, x, gy, gW, gb, accumulate, phases, xe, xo, f16, xam, gam, skip_flag);
   return launch_wgrad(w, p, (float*)ws, VQVAE_PROF_CONV_WGRAD, st);
 }
 

@@ -1168,6 +1168,25 @@ int launch_gemm(GemmArgs& g, int tag, hipStream_t st) {
   return 0;
 }
 
+int gemm_form_linear(GemmArgs& g, GemmFormInfo& o) {
+  const int mode = g_matmul_dtype == 3 ? (g.f16x2 ? 3 : 2) : g_matmul_dtype;
+  const int nseg_in = g.nseg;
+  if (int e = prepare_gemm<EPI_LINEAR>(g, mode)) return e;
+  VQ_REQUIRE((long)g.ntile_m * g.ntile_n * g.B > 0, "conv_gemm: empty launch");
+  GemmForm f;
+  if (int e = select_gemm<EPI_LINEAR>(g, mode, f)) return e;
+  const TileTraits t = tile_traits<EPI_LINEAR>(g, mode);
+  o = GemmFormInfo{};
+  o.np = mode == 2 ? 3 : (mode == 3 ? 2 : mode);
+  if (f.family == GEMM_LIN128) { o.family = VQVAE_CONV_GEMM_LIN128; return 0; }
+  VQ_REQUIRE(f.family == GEMM_TILED || f.family == GEMM_FP32, "conv_gemm: a form of the packed chain");
+  o.family = f.family == GEMM_FP32 ? VQVAE_CONV_GEMM_FP32 : VQVAE_CONV_GEMM_TILED;
+  o.rows256 = f.WM == 4; o.nb = f.NB; o.tap2 = f.TAP2 ? 1 : 0; o.lean = t.lean ? 1 : 0;
+  o.halved = g.nseg != nseg_in; o.ksplit = g.ksplit;
+  for (int i = 0; i < g.nseg; ++i) o.strided = o.strided || g.seg[i].tmul != 1 || g.seg[i].tdiv != 1;
+  return 0;
+}
+
 template int launch_gemm<EPI_LINEAR>(GemmArgs&, int, hipStream_t);
 template int launch_gemm<EPI_GATE>(GemmArgs&, int, hipStream_t);
 template int launch_gemm<EPI_GATE_BWD>(GemmArgs&, int, hipStream_t);

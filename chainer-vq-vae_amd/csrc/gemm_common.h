@@ -1118,7 +1118,14 @@ int launch_gate_bwd_strip(const GemmArgs& g, int tag, hipStream_t st);
 // pre-split); select_gemm<EPI_LINEAR> asks _shape first
 bool lin_wide_shape(const GemmArgs& g);
 int launch_lin_wide(const GemmArgs& g, int tag, hipStream_t st);
+// the form prepare_gemm + select_gemm<EPI_LINEAR> choose for g under launch_gemm's mode (g is prepared as launch_gemm would
+// prepare it): no launch, no HIP call.  vqvae_conv1d_forms' half of the forward and backward-data GEMMs.
+struct GemmFormInfo { int family, rows256, nb, np, tap2, lean, halved, ksplit, strided; };      // family: VQVAE_CONV_GEMM_*
+int gemm_form_linear(GemmArgs& g, GemmFormInfo& o);
 // wgrad.hip
+// ... and prepare_wgrad + select_wgrad's for w under plan p
+struct WgradFormInfo { int family, rows256, np, nsplit; };      // family: VQVAE_CONV_WGRAD_*
+int wgrad_form(WgradArgs& w, const WgradPlan& p, float* ws, WgradFormInfo& o);
 WgradPlan plan_wgrad(int M, int B, int Tout, const int* cins, int nseg, bool wide = false);
 bool wgrad_dma_shape(int M, int Tout, const int* cins, int nseg);     // float32x2 with both operands pre-split: does this shape run on wgrad3_dma_kernel?
 int launch_wgrad(WgradArgs& w, const WgradPlan& p, float* ws, int tag, hipStream_t st);

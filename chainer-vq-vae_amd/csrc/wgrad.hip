@@ -1428,6 +1428,17 @@ int launch_wgrad(WgradArgs& w, const WgradPlan& p, float* ws, int tag, hipStream
   return 0;
 }
 
+int wgrad_form(WgradArgs& w, const WgradPlan& p, float* ws, WgradFormInfo& o) {
+  bool fast = false;
+  if (int e = prepare_wgrad(w, p, ws, fast)) return e;
+  WgradForm f;
+  if (int e = select_wgrad(w, p, fast, f)) return e;
+  VQ_REQUIRE(f.family != WG_DMA, "wgrad: a form of the packed chain");
+  o.family = f.family == WG_W3 ? VQVAE_CONV_WGRAD_W3 : (f.family == WG_W2 ? VQVAE_CONV_WGRAD_W2 : VQVAE_CONV_WGRAD_GENERIC);
+  o.rows256 = f.family != WG_GENERIC && f.WM == 4; o.np = f.NP; o.nsplit = p.nsplit;
+  return 0;
+}
+
 }  // namespace vq
 
 #ifdef VQ_PHASE_TIMING

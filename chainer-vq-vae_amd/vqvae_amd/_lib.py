@@ -194,6 +194,7 @@ _header('vqvae_hip.h', 'ABI', 5, {
     'vqvae_conv1d_bwd_data': (c_int, [C.POINTER(Conv1dDesc), P, P, P, c_int, P, c_size_t, P]),
     'vqvae_conv1d_bwd_weight': (c_int, [C.POINTER(Conv1dDesc), P, P, P, P, c_int, P, c_size_t, P]),
     'vqvae_conv1d_uses_f32x2': (c_int, [C.POINTER(Conv1dDesc)]),
+    'vqvae_conv1d_forms': (c_int, [C.POINTER(Conv1dDesc), c_int]),
     'vqvae_conv1d_packed_bytes': (c_size_t, [C.POINTER(Conv1dDesc), c_int]),
     'vqvae_conv1d_pack': (c_int, [c_int, C.POINTER(Conv1dDesc), C.POINTER(c_void_p), C.POINTER(c_int), C.POINTER(c_void_p), P]),
     'vqvae_conv1d_fwd_amax': (c_int, [C.POINTER(Conv1dDesc), P, P, P, P, P, c_size_t, C.POINTER(Conv1dAmax), P]),
@@ -457,6 +458,12 @@ EW_ADD, EW_SUB, EW_MUL, EW_AXPBY, EW_SCALE, EW_SQUARE, EW_RELU, EW_RELU_BWD, EW_
 PROF_RESBLOCK_GATE, PROF_RESBLOCK_OUT, PROF_RESBLOCK_BWD_GZ, PROF_RESBLOCK_BWD_GX, \
     PROF_RESBLOCK_BWD_GC, PROF_RESBLOCK_WGRAD, PROF_CONV_FWD, PROF_CONV_BWD_DATA, \
     PROF_CONV_WGRAD, PROF_VQ_NEAREST, PROF_RESSTACK_SKIP, PROF_WGRAD_DIL, PROF_WGRAD_RES_SKIP = range(1, 14)
+# vqvae_conv1d_forms: the bits of its word (VQVAE_CONV_FORM_*) and the family values (VQVAE_CONV_GEMM_* / _WGRAD_*)
+CONV_FORM_FAMILY, CONV_FORM_ROWS256, CONV_FORM_WIDE, CONV_FORM_NP, CONV_FORM_NP_SHIFT = 0x003, 0x004, 0x008, 0x030, 4
+CONV_FORM_TAP2, CONV_FORM_LEAN, CONV_FORM_HALVED, CONV_FORM_SPLIT, CONV_FORM_STRIDED, CONV_FORM_PHASES = \
+    0x040, 0x080, 0x100, 0x200, 0x400, 0x800
+CONV_GEMM_LIN128, CONV_GEMM_TILED, CONV_GEMM_FP32 = range(3)
+CONV_WGRAD_W3, CONV_WGRAD_W2, CONV_WGRAD_GENERIC = range(3)
 GEN_NONE, GEN_SOFTMAX, GEN_MOL = range(3)
 GEN_MAX_N = 4               # VQVAE_GEN_MAX_N: the persistent kernel and WaveNet.initialize
 GEN_MAX_LOCKSTEP = 128      # VQVAE_GEN_MAX_LOCKSTEP: vqvae_wavenet_gen_step

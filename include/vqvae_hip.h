@@ -174,6 +174,33 @@ size_t vqvae_conv1d_packed_bytes(const vqvae_conv1d_desc* d, int backward);
 int vqvae_conv1d_pack(int n, const vqvae_conv1d_desc* descs, const float* const* W, const int* backward,
                       void* const* packed, vqvae_stream_t s);
 int vqvae_conv1d_uses_f32x2(const vqvae_conv1d_desc* d);
+/* Which kernel form vqvae_conv1d_fwd (which = 0), vqvae_conv1d_bwd_data (1) or vqvae_conv1d_bwd_weight (2) launches for
+ * this desc under the current matmul dtype and f32x2 threshold, given a workspace of vqvae_conv1d_workspace_bytes, no
+ * skip flag and 16-byte aligned tensors: the entry point's own argument block taken through its own dispatch, without a
+ * launch and without device memory.  A word of VQVAE_CONV_FORM_* bits; -1 where the call would be refused (or which is
+ * none of 0, 1, 2).
+ *   which 0 / 1: FAMILY is VQVAE_CONV_GEMM_*; NP (pieces per operand: 3 = six bf16 products, 2 = three fp16 products,
+ *     1 = bf16 operands, 0 = fp32 MFMA) is set for every family, every other bit for the tiled families only.
+ *   which 2: FAMILY is VQVAE_CONV_WGRAD_*; NP (0 for WGRAD_W2 and for the generic kernel on fp32 operands), ROWS256
+ *     (WGRAD_W3 / _W2 only: the generic kernel has 128-row tiles alone), PHASES, SPLIT.                              */
+#define VQVAE_CONV_FORM_FAMILY 0x003    /* mask of the family value below */
+#define VQVAE_CONV_GEMM_LIN128 0        /*   lin128_stream_kernel (the 128 -> 256 channel 1x1, T % 64 == 0) */
+#define VQVAE_CONV_GEMM_TILED 1         /*   conv_gemm_x3_kernel */
+#define VQVAE_CONV_GEMM_FP32 2          /*   conv_gemm_kernel (matmul dtype 0) */
+#define VQVAE_CONV_WGRAD_W3 0           /*   wgrad3_kernel */
+#define VQVAE_CONV_WGRAD_W2 1           /*   wgrad2_kernel (matmul dtype 0) */
+#define VQVAE_CONV_WGRAD_GENERIC 2      /*   wgrad_kernel */
+#define VQVAE_CONV_FORM_ROWS256 0x004   /* 256-row tiles (absent: 128-row) */
+#define VQVAE_CONV_FORM_WIDE 0x008      /* 256-column tiles, NB = 2 */
+#define VQVAE_CONV_FORM_NP 0x030        /* mask of NP << VQVAE_CONV_FORM_NP_SHIFT */
+#define VQVAE_CONV_FORM_NP_SHIFT 4
+#define VQVAE_CONV_FORM_TAP2 0x040      /* the two-tap loop: two segments interleaved channel group by channel group */
+#define VQVAE_CONV_FORM_LEAN 0x080      /* ... on 256 x 128 tiles, two workgroups per CU */
+#define VQVAE_CONV_FORM_HALVED 0x100    /* a 1x1 conv presented as its lower and upper half of the channels */
+#define VQVAE_CONV_FORM_SPLIT 0x200     /* split-K (which 0 / 1) / more than one split of the (batch, time) axis (which 2) */
+#define VQVAE_CONV_FORM_STRIDED 0x400   /* a segment with tmul != 1 or tdiv != 1 */
+#define VQVAE_CONV_FORM_PHASES 0x800    /* which 2: x split into its even and odd phase first (stride-2 convs) */
+int vqvae_conv1d_forms(const vqvae_conv1d_desc* d, int which);
 int vqvae_conv1d_fwd_amax(const vqvae_conv1d_desc* d, const float* x, const float* W,
                           const float* b, float* y, void* ws, size_t ws_bytes,
                           const vqvae_conv1d_amax* amax, vqvae_stream_t s);

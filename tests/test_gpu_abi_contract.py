@@ -98,6 +98,7 @@ CONTRACTS = {
     'vqvae_conv1d_workspace_bytes': _row(init=_QUERY),
     'vqvae_conv1d_packed_bytes': _row(init=_QUERY),
     'vqvae_conv1d_uses_f32x2': _row(init=_QUERY),
+    'vqvae_conv1d_forms': _row(init=_QUERY),
     'vqvae_conv1d_fwd': _row(_CONV, init='ws: weight slab, split-K partial slabs (every slab element is stored before the reduce '
                                          'reads it: no memset, no atomics), operand maxima (memset by the entry point)'),
     'vqvae_conv1d_fwd_amax': _row(_CONV, maxima=['test_published_maximum_conv'], init='amax.out: zeroed by the caller'),

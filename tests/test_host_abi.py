@@ -15,7 +15,7 @@ FILES = list(_lib.HEADERS)
 BASE = 'vqvae_hip.h'
 
 # adding an export is a deliberate edit of this table
-EXPORT_COUNTS = {'vqvae_hip.h': 127, 'vqvae_codebook.h': 3, 'vqvae_vq_ema.h': 5, 'vqvae_kmeans.h': 6, 'vqvae_optim.h': 6,
+EXPORT_COUNTS = {'vqvae_hip.h': 128, 'vqvae_codebook.h': 3, 'vqvae_vq_ema.h': 5, 'vqvae_kmeans.h': 6, 'vqvae_optim.h': 6,
                  'vqvae_sampling.h': 3, 'vqvae_gen_slots.h': 3, 'vqvae_gen_cond.h': 2, 'vqvae_gen_rng.h': 5,
                  'vqvae_corpus.h': 2, 'vqvae_ingest.h': 5, 'vqvae_ragged.h': 5, 'vqvae_metrics.h': 5, 'vqvae_pitch.h': 5}
 
@@ -69,7 +69,7 @@ def test_the_registry_is_the_include_directory():
 
 def test_export_counts_are_pinned():
     assert {f: len(A.exports(f)) for f in FILES} == EXPORT_COUNTS
-    assert sum(EXPORT_COUNTS.values()) == 182
+    assert sum(EXPORT_COUNTS.values()) == 183
 
 
 def test_no_symbol_is_in_two_tables():
