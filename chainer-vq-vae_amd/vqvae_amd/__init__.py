@@ -21,5 +21,7 @@ from .metrics import MelConfig, RaggedFeatures, compare_many, features_many  # n
 from .pitch import PitchConfig, RaggedPitch, compare_pitch_many, pitch_many  # noqa: F401
 from .scoring import Scores, evaluate_many, score_many  # noqa: F401
 from .alignment import Alignment, align_many, compare_aligned_many  # noqa: F401
+from .codestats import (CodeComparison, CodeRuns, CodeStats, code_stats, collapse_many,  # noqa: F401
+                        compare_codes_many)
 from .synthesis import synthesize, synthesize_many  # noqa: F401
 from .reporting import LogReport, PlotReport, PrintReport  # noqa: F401

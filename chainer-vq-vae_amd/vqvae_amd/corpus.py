@@ -130,6 +130,12 @@ class _Utterances(object):
         from .scoring import score_many
         return score_many(wavenet, condition, self, chunk_bytes, per_sample, return_logits)
 
+    def code_stats(self, codes, **kw):
+        """Usage, speaker leakage and durations of these utterances' codes (``encode``'s result) with these utterances'
+        speaker ids as the groups (codestats.CodeStats); see codestats.code_stats for the keywords."""
+        from .codestats import code_stats
+        return code_stats(codes, speakers=self.speakers, **kw)
+
 
 class ResidentCorpus(_Utterances):
     """``waves``: loaded, silence-trimmed waveforms (what inputs.crop_or_pad takes); ``speakers``: one int id each.
