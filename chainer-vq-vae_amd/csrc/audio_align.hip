@@ -1,4 +1,4 @@
-// Dynamic time warping over mel-cepstra for a ragged list of utterance pairs (csrc/align_abi.h states the rule).
+// Dynamic time warping over mel-cepstra for a ragged list of utterance pairs (include/vqvae_align.h states the rule).
 //
 // align_cepstra_kernel: a thread per frame; the frame's n_mels log-mel values are read once per coefficient (coalesced
 //   along the frame axis, the dct row is the same address for the whole wave) and summed in float64, m ascending.
@@ -20,7 +20,7 @@
 // shorter side above max_short) is skipped: path_len 0, NaN scores, nothing else written.  Every address is formed in 64
 // bits; plain vector stores only.
 #include "common.h"
-#include "align_abi.h"
+#include "../../include/vqvae_align.h"
 
 namespace vq {
 

@@ -1,4 +1,4 @@
-// Statistics of the discrete codes of a ragged list of utterances (csrc/codes_abi.h states the rule).  Integer work only.
+// Statistics of the discrete codes of a ragged list of utterances (include/vqvae_codes.h states the rule).  Integer work only.
 //
 // codes_runs_kernel: one workgroup of 256 threads per utterance, passes of 256 positions.  A position flags a run start;
 //   one LDS scan per pass carries two things, the number of starts up to a position and the last start's position, with a
@@ -17,7 +17,7 @@
 // An utterance or pair whose table entries contradict the descriptor is skipped (the header says what is written then).
 // Every address is formed in 64 bits; plain vector stores and integer atomics only.
 #include "common.h"
-#include "codes_abi.h"
+#include "../../include/vqvae_codes.h"
 
 namespace vq {
 

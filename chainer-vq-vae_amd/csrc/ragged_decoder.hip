@@ -1,4 +1,4 @@
-// The teacher-forced decoder pass over a ragged list of utterances (csrc/ragged_decoder_abi.h, which states the rule):
+// The teacher-forced decoder pass over a ragged list of utterances (include/vqvae_ragged_decoder.h, which states the rule):
 // embed by index, the condition projected at the latent rate, per block a gate launch and a res / skip launch, the head
 // with the per-column log-sum-exp, and the per-utterance float64 reduce.
 //
@@ -26,7 +26,7 @@
 // Every address is formed in 64 bits.  Stores go to (row < rows of the output, column < ttot) only; plain vector stores.
 #include "gemm_common.h"
 #include "ragged_seg.h"
-#include "ragged_decoder_abi.h"
+#include "../../include/vqvae_ragged_decoder.h"
 
 namespace vq {
 
@@ -374,19 +374,19 @@ __global__ __launch_bounds__(RD_THREADS) void rd_gvec_kernel(const float* gv, co
 }
 
 // one workgroup per utterance: lane t adds elements t, t + 256, ... in ascending order, then s[k] += s[k + h], h = 128 .. 1
-__global__ __launch_bounds__(VQVAE_RDEC_REDUCE_LANES) void rd_reduce_kernel(const int64_t* off, const float* nll,
+__global__ __launch_bounds__(VQVAE_RAGGED_DECODER_REDUCE_LANES) void rd_reduce_kernel(const int64_t* off, const float* nll,
                                                                             const int32_t* hit, double* nll_sum,
                                                                             int64_t* hits) {
-  __shared__ double sd[VQVAE_RDEC_REDUCE_LANES];
-  __shared__ long long sh[VQVAE_RDEC_REDUCE_LANES];
+  __shared__ double sd[VQVAE_RAGGED_DECODER_REDUCE_LANES];
+  __shared__ long long sh[VQVAE_RAGGED_DECODER_REDUCE_LANES];
   const int i = blockIdx.x, t = threadIdx.x;
   const long long lo = (long long)off[i], hi = (long long)off[i + 1];
   double s = 0.0;
   long long h = 0;
-  for (long long j = lo + t; j < hi; j += VQVAE_RDEC_REDUCE_LANES) { s += (double)nll[j]; h += hit[j]; }
+  for (long long j = lo + t; j < hi; j += VQVAE_RAGGED_DECODER_REDUCE_LANES) { s += (double)nll[j]; h += hit[j]; }
   sd[t] = s; sh[t] = h;
   __syncthreads();
-  for (int w = VQVAE_RDEC_REDUCE_LANES / 2; w >= 1; w >>= 1) {
+  for (int w = VQVAE_RAGGED_DECODER_REDUCE_LANES / 2; w >= 1; w >>= 1) {
     if (t < w) { sd[t] += sd[t + w]; sh[t] += sh[t + w]; }
     __syncthreads();
   }
@@ -414,7 +414,7 @@ static int launch_rd_by_rows(const RdArgs& a, hipStream_t st) {
 }
 
 static bool rd_desc_ok(const vqvae_rdec_desc* d) {
-  return d && d->n >= 1 && d->R >= 1 && d->D >= 2 && d->D % 2 == 0 && d->S >= 1 && d->Q >= 1 && d->Q <= VQVAE_RDEC_MAX_CLASSES &&
+  return d && d->n >= 1 && d->R >= 1 && d->D >= 2 && d->D % 2 == 0 && d->S >= 1 && d->Q >= 1 && d->Q <= VQVAE_RAGGED_DECODER_MAX_CLASSES &&
          d->Cl >= 1 && d->G >= 0 && d->n_blocks >= 1 && d->upscale >= 1 && d->ttot >= 1 && d->tltot >= 1 &&
          d->ttot <= 0x7fffffffLL && d->tltot <= 0x7fffffffLL && (long long)d->n_blocks * d->D <= 0x7fffffffLL / (d->Cl + d->G) &&
          (long long)d->R * d->Q * 2 <= 0x7fffffffLL && (long long)d->D * d->R * 2 <= 0x7fffffffLL &&
@@ -439,7 +439,7 @@ using namespace vq;
   VQ_REQUIRE(d, who ": null descriptor");                                                                                       \
   VQ_REQUIRE(rd_desc_ok(d), who ": needs n, R, S, Cl, n_blocks, upscale, ttot, tltot >= 1, an even D >= 2, G >= 0, "             \
              "1 <= Q <= %d, ttot and tltot below 2^31 and weight tensors below 2^31 elements (got n %d, R %d, D %d, S %d, Q %d, Cl %d, G %d, n_blocks %d, " \
-             "upscale %d, ttot %lld, tltot %lld)", VQVAE_RDEC_MAX_CLASSES, (int)d->n, (int)d->R, (int)d->D, (int)d->S, (int)d->Q, \
+             "upscale %d, ttot %lld, tltot %lld)", VQVAE_RAGGED_DECODER_MAX_CLASSES, (int)d->n, (int)d->R, (int)d->D, (int)d->S, (int)d->Q, \
              (int)d->Cl, (int)d->G, (int)d->n_blocks, (int)d->upscale, (long long)d->ttot, (long long)d->tltot);                 \
   VQ_REQUIRE(g_matmul_dtype != 1, who ": matmul mode 1 (bf16 operands) is not supported by the ragged decoder; use mode 0, 2 or 3")
 
@@ -495,8 +495,8 @@ extern "C" int vqvae_rdec_gate(const vqvae_rdec_desc* d, const vqvae_rdec_tables
   VQ_REQUIRE(t && t->off && t->latoff && t->tl, "rdec_gate: null tables, off, latoff or tl");
   VQ_REQUIRE(x && Wd && P && g && z, "rdec_gate: null x, Wd, P, g or z");
   VQ_REQUIRE(block >= 0 && block < d->n_blocks, "rdec_gate: block %d of %d", block, (int)d->n_blocks);
-  VQ_REQUIRE(dilation >= 1 && dilation <= VQVAE_RDEC_MAX_DILATION, "rdec_gate: dilation must be in 1 .. %d (got %d)",
-             VQVAE_RDEC_MAX_DILATION, dilation);
+  VQ_REQUIRE(dilation >= 1 && dilation <= VQVAE_RAGGED_DECODER_MAX_DILATION, "rdec_gate: dilation must be in 1 .. %d (got %d)",
+             VQVAE_RAGGED_DECODER_MAX_DILATION, dilation);
   RdArgs a{};
   a.x = x; a.off = t->off; a.w0 = Wd; a.y0 = z;
   a.P = P + (long long)block * d->D * d->tltot;
@@ -557,7 +557,7 @@ extern "C" int vqvae_rdec_reduce(const vqvae_rdec_desc* d, const vqvae_rdec_tabl
   RD_COMMON("rdec_reduce");
   VQ_REQUIRE(t && t->off, "rdec_reduce: null tables or off");
   VQ_REQUIRE(nll && hit && nll_sum && hits, "rdec_reduce: null nll, hit, nll_sum or hits");
-  hipLaunchKernelGGL(rd_reduce_kernel, dim3((unsigned)d->n), dim3(VQVAE_RDEC_REDUCE_LANES), 0, (hipStream_t)stream, t->off, nll,
+  hipLaunchKernelGGL(rd_reduce_kernel, dim3((unsigned)d->n), dim3(VQVAE_RAGGED_DECODER_REDUCE_LANES), 0, (hipStream_t)stream, t->off, nll,
                      hit, nll_sum, hits);
   VQ_LAUNCH_CHECK();
   return 0;

@@ -137,6 +137,53 @@ class PitchDesc(C.Structure):
                [(n, C.c_double) for n in ('fmin', 'fmax', 'threshold', 'min_power')] + [('ftot', C.c_int64)]
 
 
+class RdecDesc(C.Structure):
+    """One chunk of the ragged decoder pass."""
+    _c_name_ = 'vqvae_rdec_desc'
+    _fields_ = [(n, C.c_int32) for n in ('n', 'R', 'D', 'S', 'Q', 'Cl', 'G', 'n_blocks', 'upscale', 'reserved')] + \
+               [('ttot', C.c_int64), ('tltot', C.c_int64)]
+
+
+class RdecTables(C.Structure):
+    """The device tables of one chunk of the ragged decoder pass."""
+    _c_name_ = 'vqvae_rdec_tables'
+    _fields_ = [(n, P) for n in ('off', 'qoff', 'latoff', 'tl')]
+
+
+class AlignDesc(C.Structure):
+    """One chunk of pairs to align."""
+    _c_name_ = 'vqvae_align_desc'
+    _fields_ = [(n, C.c_int32) for n in ('n', 'n_mels', 'n_mcep', 'max_short')] + \
+               [(n, C.c_int64) for n in ('fa_tot', 'fb_tot', 'stride_a', 'stride_b', 'cells', 'ptot')]
+
+
+class AlignTables(C.Structure):
+    """The device tables of one chunk of pairs to align."""
+    _c_name_ = 'vqvae_align_tables'
+    _fields_ = [(n, P) for n in ('off_a', 'off_b', 'cell_off', 'path_off')]
+
+
+class CodesRunsDesc(C.Structure):
+    _c_name_ = 'vqvae_codes_runs_desc'
+    _fields_ = [('n', C.c_int32), ('max_run', C.c_int32), ('total', C.c_int64)]
+
+
+class CodesHistDesc(C.Structure):
+    _c_name_ = 'vqvae_codes_hist_desc'
+    _fields_ = [(n, C.c_int32) for n in ('n', 'k', 'groups', 'bigrams', 'accumulate', 'reserved')] + [('total', C.c_int64)]
+
+
+class CodesPairDesc(C.Structure):
+    _c_name_ = 'vqvae_codes_pair_desc'
+    _fields_ = [('n', C.c_int32), ('max_short', C.c_int32), ('total_a', C.c_int64), ('total_b', C.c_int64)]
+
+
+class CodesPairTables(C.Structure):
+    """The device tables of the two sides of a list of code-string pairs."""
+    _c_name_ = 'vqvae_codes_pair_tables'
+    _fields_ = [(n, P) for n in ('start_a', 'len_a', 'start_b', 'len_b')]
+
+
 class Header(collections.namedtuple('Header', 'file words version prototypes')):
     """One header of include/: what the version error calls it, the version bound, name -> (restype, argtypes)."""
 
@@ -438,6 +485,53 @@ PITCH_THREADS = 256
 PITCH_MAX_TILE = 4
 PITCH_MAX_FRAME = 2048
 PITCH_COLUMNS = 8
+
+# include/vqvae_ragged_decoder.h: the teacher-forced decoder pass over a ragged list (held-out likelihood)
+_header('vqvae_ragged_decoder.h', 'ragged-decoder ABI', 1, {
+    'vqvae_ragged_decoder_abi_version': (c_int, []),
+    'vqvae_rdec_workspace_bytes': (c_size_t, [C.POINTER(RdecDesc)]),
+    'vqvae_rdec_embed': (c_int, [C.POINTER(RdecDesc), C.POINTER(RdecTables), P, P, P, P, P]),
+    'vqvae_rdec_cond_project': (c_int, [C.POINTER(RdecDesc), C.POINTER(RdecTables), P, P, P, P]),
+    'vqvae_rdec_cond_global': (c_int, [C.POINTER(RdecDesc), P, P, P, P, P]),
+    'vqvae_rdec_gate': (c_int, [C.POINTER(RdecDesc), C.POINTER(RdecTables), c_int, c_int, P, P, P, P, P, P]),
+    'vqvae_rdec_res_skip': (c_int, [C.POINTER(RdecDesc), P, P, P, P, P, P, P, P, c_int, P]),
+    'vqvae_rdec_head': (c_int, [C.POINTER(RdecDesc), C.POINTER(RdecTables), P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
+    'vqvae_rdec_reduce': (c_int, [C.POINTER(RdecDesc), C.POINTER(RdecTables), P, P, P, P, P]),
+})
+RAGGED_DECODER_MAX_CLASSES = 512
+RAGGED_DECODER_MAX_DILATION = 512
+RAGGED_DECODER_REDUCE_LANES = 256
+
+# include/vqvae_align.h: dynamic time warping over mel-cepstra for a ragged list of utterance pairs
+_header('vqvae_align.h', 'alignment ABI', 1, {
+    'vqvae_align_abi_version': (c_int, []),
+    'vqvae_align_cepstra_workspace_bytes': (c_size_t, [C.POINTER(AlignDesc)]),
+    'vqvae_align_dtw_workspace_bytes': (c_size_t, [C.POINTER(AlignDesc)]),
+    'vqvae_align_path_workspace_bytes': (c_size_t, [C.POINTER(AlignDesc)]),
+    'vqvae_align_cepstra': (c_int, [C.POINTER(AlignDesc), c_int, P, P, P, P, c_size_t, P]),
+    'vqvae_align_dtw': (c_int, [C.POINTER(AlignDesc), C.POINTER(AlignTables), P, P, P, P, P, P, c_size_t, P]),
+    'vqvae_align_path': (c_int, [C.POINTER(AlignDesc), C.POINTER(AlignTables), P, P, P, P, P, P, P, P, P, c_size_t, P]),
+})
+ALIGN_MAX_SHORT = 3072
+ALIGN_MAX_MELS = 128
+ALIGN_THREADS = 256
+ALIGN_REDUCE_LANES = 256
+
+# include/vqvae_codes.h: runs, per-speaker counts and the edit distance of the discrete codes of a ragged list
+_header('vqvae_codes.h', 'code-statistics ABI', 1, {
+    'vqvae_codes_abi_version': (c_int, []),
+    'vqvae_codes_runs_workspace_bytes': (c_size_t, [C.POINTER(CodesRunsDesc)]),
+    'vqvae_codes_hist_workspace_bytes': (c_size_t, [C.POINTER(CodesHistDesc)]),
+    'vqvae_codes_agree_workspace_bytes': (c_size_t, [C.POINTER(CodesPairDesc)]),
+    'vqvae_codes_edit_workspace_bytes': (c_size_t, [C.POINTER(CodesPairDesc)]),
+    'vqvae_codes_runs': (c_int, [C.POINTER(CodesRunsDesc), P, P, P, P, P, P, P, P, c_size_t, P]),
+    'vqvae_codes_hist': (c_int, [C.POINTER(CodesHistDesc), P, P, P, P, P, P, P, P, c_size_t, P]),
+    'vqvae_codes_agree': (c_int, [C.POINTER(CodesPairDesc), C.POINTER(CodesPairTables), P, P, P, P, c_size_t, P]),
+    'vqvae_codes_edit': (c_int, [C.POINTER(CodesPairDesc), C.POINTER(CodesPairTables), P, P, P, P, P, c_size_t, P]),
+})
+CODES_MAX_SHORT = 6143
+CODES_THREADS = 256
+CODES_MAX_BIGRAM_K = 4096
 
 PROTOTYPES = HEADERS['vqvae_hip.h'].prototypes
 ABI_VERSION = HEADERS['vqvae_hip.h'].version

@@ -1,5 +1,5 @@
 """Time-aligned metrics on the device: dynamic time warping over mel-cepstra for a ragged list of utterance pairs
-(csrc/align_abi.h states the rule, csrc/audio_align.hip runs it).
+(include/vqvae_align.h states the rule, csrc/audio_align.hip runs it).
 
     fa = features_many(targets, cfg)                   # the target speaker's own recordings of the sentences
     fb = features_many(converted, cfg)                 # the converted utterances: other lengths, other timing
@@ -15,9 +15,6 @@ MCD-DTW; NO parity with any toolkit is claimed.
 
 Everything is float64 in one written order, so a pair's results are the same bits alone, in any list, at any position and
 for any ``chunk_bytes``; tests/alignment_ref.py restates the rule in NumPy and the device is held to every bit of it.
-
-The entry points are declared in csrc/align_abi.h, which is not under include/, so they are bound here (table,
-Structures, version check) and not in _lib.HEADERS, as scoring.py binds its header.
 """
 import ctypes as C
 
@@ -28,68 +25,11 @@ from .backend import DeviceArray
 from .metrics import MelConfig, RaggedFeatures, _frames, features_many, tables
 
 _S = backend.stream
-MAX_SHORT = 3072                   # VQVAE_ALIGN_MAX_SHORT: min(Fa, Fb) of a pair
-MAX_MELS = 128                     # VQVAE_ALIGN_MAX_MELS
-THREADS = 256                      # VQVAE_ALIGN_THREADS
-REDUCE_LANES = 256                 # VQVAE_ALIGN_REDUCE_LANES
+MAX_SHORT = _lib.ALIGN_MAX_SHORT   # min(Fa, Fb) of a pair
+MAX_MELS = _lib.ALIGN_MAX_MELS
+THREADS = _lib.ALIGN_THREADS
+REDUCE_LANES = _lib.ALIGN_REDUCE_LANES
 MAX_CELLS = 1 << 31                # the direction table of ONE pair
-
-HEADER = 'align_abi.h'             # under csrc/
-ABI_WORDS = 'alignment ABI'
-ABI_VERSION = 1
-P = _lib.P
-
-
-class AlignDesc(C.Structure):
-    """One chunk of pairs."""
-    _c_name_ = 'vqvae_align_desc'
-    _fields_ = [(n, C.c_int32) for n in ('n', 'n_mels', 'n_mcep', 'max_short')] + \
-               [(n, C.c_int64) for n in ('fa_tot', 'fb_tot', 'stride_a', 'stride_b', 'cells', 'ptot')]
-
-
-class AlignTables(C.Structure):
-    """The device tables of one chunk."""
-    _c_name_ = 'vqvae_align_tables'
-    _fields_ = [(n, P) for n in ('off_a', 'off_b', 'cell_off', 'path_off')]
-
-
-_D, _T = C.POINTER(AlignDesc), C.POINTER(AlignTables)
-# the table IS the list of symbols csrc/align_abi.h declares (tests/test_host_alignment.py)
-PROTOTYPES = {
-    'vqvae_align_abi_version': (C.c_int, []),
-    'vqvae_align_cepstra_workspace_bytes': (C.c_size_t, [_D]),
-    'vqvae_align_dtw_workspace_bytes': (C.c_size_t, [_D]),
-    'vqvae_align_path_workspace_bytes': (C.c_size_t, [_D]),
-    'vqvae_align_cepstra': (C.c_int, [_D, C.c_int, P, P, P, P, C.c_size_t, P]),
-    'vqvae_align_dtw': (C.c_int, [_D, _T, P, P, P, P, P, P, C.c_size_t, P]),
-    'vqvae_align_path': (C.c_int, [_D, _T, P, P, P, P, P, P, P, P, P, C.c_size_t, P]),
-}
-STRUCTS = (AlignDesc, AlignTables)
-
-_bound = None
-
-
-def load():
-    """libvqvae_hip.so with this header's entry points bound (once); another version of the header is an ImportError."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    lib = _lib.load()
-    for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(lib, name)               # AttributeError if the symbol is missing
-        fn.restype = res
-        fn.argtypes = args
-    has = lib.vqvae_align_abi_version()
-    if has != ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has %s %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (_lib.LIB_PATH, ABI_WORDS, has, ABI_VERSION))
-    _bound = lib
-    return lib
-
-
-def call(name, *args):
-    """Calls an int-returning entry point of the header and raises _lib.HipError on failure."""
-    _lib.check(getattr(load(), name)(*args), name)
 
 
 # --------------------------------------------------------------------------- #
@@ -172,16 +112,17 @@ class _Tables(object):
         self.cell_off, self.path_off = ragged.offsets(fa * fb, total=True), ragged.offsets(fa + fb - 1, total=True)
         self.dev = backend.to_device(np.concatenate([self.off_a, self.off_b, self.cell_off, self.path_off]))
         p, step = self.dev.ptr, 8 * (n + 1)
-        self.c = AlignTables(p, p + step, p + 2 * step, p + 3 * step)
+        self.c = _lib.AlignTables(p, p + step, p + 2 * step, p + 3 * step)
 
 
 def _desc(cfg, fa, fb, stride_a, stride_b):
-    return AlignDesc(len(fa), cfg.n_mels, cfg.n_mcep, int(np.minimum(fa, fb).max()), int(fa.sum()), int(fb.sum()),
-                     int(stride_a), int(stride_b), int((fa * fb).sum()), int((fa + fb - 1).sum()))
+    return _lib.AlignDesc(len(fa), cfg.n_mels, cfg.n_mcep, int(np.minimum(fa, fb).max()), int(fa.sum()), int(fb.sum()),
+                          int(stride_a), int(stride_b), int((fa * fb).sum()), int((fa + fb - 1).sum()))
 
 
 def _workspace(query, d, who):
-    need = getattr(load(), query)(C.byref(d))
+    """The bytes a size query asks for; align_many sizes ONE scratch from three of them, so nothing is allocated here."""
+    need = getattr(_lib.load(), query)(C.byref(d))
     if need == C.c_size_t(-1).value:
         raise ValueError('%s: the library refuses this description' % who)
     return need
@@ -233,14 +174,14 @@ def align_many(feats_a, feats_b, paths=True, chunk_bytes=1 << 30):
         need_d = _workspace('vqvae_align_dtw_workspace_bytes', d, who)
         need_p = _workspace('vqvae_align_path_workspace_bytes', d, who) if not paths else 0
         ws = backend.workspace(max(need_c, need_d + need_p, 256))       # the direction table, then the path scratch
-        call('vqvae_align_cepstra', db, 0, la, dct.ptr, ca.ptr, ws.ptr, need_c, _S())
-        call('vqvae_align_cepstra', db, 1, lb, dct.ptr, cb.ptr, ws.ptr, need_c, _S())
-        call('vqvae_align_dtw', db, tc, ca.ptr, cb.ptr, cost.ptr + 8 * start, klen.ptr + 4 * start, diag.ptr + 4 * start,
-             ws.ptr, need_d, _S())
+        _lib.call('vqvae_align_cepstra', db, 0, la, dct.ptr, ca.ptr, ws.ptr, need_c, _S())
+        _lib.call('vqvae_align_cepstra', db, 1, lb, dct.ptr, cb.ptr, ws.ptr, need_c, _S())
+        _lib.call('vqvae_align_dtw', db, tc, ca.ptr, cb.ptr, cost.ptr + 8 * start, klen.ptr + 4 * start, diag.ptr + 4 * start,
+                  ws.ptr, need_d, _S())
         at = 4 * int(path_off[start])
-        call('vqvae_align_path', db, tc, ws.ptr, cost.ptr + 8 * start, klen.ptr + 4 * start, la, lb,
-             None if ia is None else ia.ptr + at, None if ib is None else ib.ptr + at, scores.ptr + 16 * start,
-             ws.ptr + need_d, need_p, _S())
+        _lib.call('vqvae_align_path', db, tc, ws.ptr, cost.ptr + 8 * start, klen.ptr + 4 * start, la, lb,
+                  None if ia is None else ia.ptr + at, None if ib is None else ib.ptr + at, scores.ptr + 16 * start,
+                  ws.ptr + need_d, need_p, _S())
         del ta
     sc = scores.get()
     return Alignment(sc[:, 0].copy(), sc[:, 1].copy(), cost.get(), klen.get().astype(np.int64), diag.get().astype(np.int64),

@@ -1,5 +1,5 @@
 """Statistics of the discrete codes on the device: speaker leakage, usage, durations and the edit distance of two code
-strings for a ragged list of utterances (csrc/codes_abi.h states the rule, csrc/code_stats.hip runs it).
+strings for a ragged list of utterances (include/vqvae_codes.h states the rule, csrc/code_stats.hip runs it).
 
     codes = corpus.encode(encoder, vq)                         # frontend.LatentCodes
     st = code_stats(codes, speakers, n_speakers)               # CodeStats: mi_bits, perplexity, js_bits, run_hist, ...
@@ -16,9 +16,6 @@ string -- or a converted utterance, encoded again, the codes it was made from --
 The device counts; everything it does is integer arithmetic, so the tables and distances are the same bits for any list
 order and launch shape, and tests/codestats_ref.py restates them in NumPy.  The derived figures are float64 NumPy over the
 count tables, on the host (``figures``).
-
-The entry points are declared in csrc/codes_abi.h, which is not under include/, so they are bound here (table,
-Structures, version check) and not in _lib.HEADERS, as alignment.py binds its header.
 """
 import ctypes as C
 
@@ -29,83 +26,9 @@ from .backend import DeviceArray
 from .frontend import LatentCodes
 
 _S = backend.stream
-MAX_SHORT = 6143                   # VQVAE_CODES_MAX_SHORT: min(La, Lb) of a pair
-THREADS = 256                      # VQVAE_CODES_THREADS
-MAX_BIGRAM_K = 4096                # VQVAE_CODES_MAX_BIGRAM_K
-
-HEADER = 'codes_abi.h'             # under csrc/
-ABI_WORDS = 'code-statistics ABI'
-ABI_VERSION = 1
-P = _lib.P
-
-
-class RunsDesc(C.Structure):
-    _c_name_ = 'vqvae_codes_runs_desc'
-    _fields_ = [('n', C.c_int32), ('max_run', C.c_int32), ('total', C.c_int64)]
-
-
-class HistDesc(C.Structure):
-    _c_name_ = 'vqvae_codes_hist_desc'
-    _fields_ = [(n, C.c_int32) for n in ('n', 'k', 'groups', 'bigrams', 'accumulate', 'reserved')] + [('total', C.c_int64)]
-
-
-class PairDesc(C.Structure):
-    _c_name_ = 'vqvae_codes_pair_desc'
-    _fields_ = [('n', C.c_int32), ('max_short', C.c_int32), ('total_a', C.c_int64), ('total_b', C.c_int64)]
-
-
-class PairTables(C.Structure):
-    """The device tables of the two sides."""
-    _c_name_ = 'vqvae_codes_pair_tables'
-    _fields_ = [(n, P) for n in ('start_a', 'len_a', 'start_b', 'len_b')]
-
-
-_R, _H, _D, _T = C.POINTER(RunsDesc), C.POINTER(HistDesc), C.POINTER(PairDesc), C.POINTER(PairTables)
-# the table IS the list of symbols csrc/codes_abi.h declares (tests/test_host_codestats.py)
-PROTOTYPES = {
-    'vqvae_codes_abi_version': (C.c_int, []),
-    'vqvae_codes_runs_workspace_bytes': (C.c_size_t, [_R]),
-    'vqvae_codes_hist_workspace_bytes': (C.c_size_t, [_H]),
-    'vqvae_codes_agree_workspace_bytes': (C.c_size_t, [_D]),
-    'vqvae_codes_edit_workspace_bytes': (C.c_size_t, [_D]),
-    'vqvae_codes_runs': (C.c_int, [_R, P, P, P, P, P, P, P, P, C.c_size_t, P]),
-    'vqvae_codes_hist': (C.c_int, [_H, P, P, P, P, P, P, P, P, C.c_size_t, P]),
-    'vqvae_codes_agree': (C.c_int, [_D, _T, P, P, P, P, C.c_size_t, P]),
-    'vqvae_codes_edit': (C.c_int, [_D, _T, P, P, P, P, P, C.c_size_t, P]),
-}
-STRUCTS = (RunsDesc, HistDesc, PairDesc, PairTables)
-
-_bound = None
-
-
-def load():
-    """libvqvae_hip.so with this header's entry points bound (once); another version of the header is an ImportError."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    lib = _lib.load()
-    for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(lib, name)               # AttributeError if the symbol is missing
-        fn.restype = res
-        fn.argtypes = args
-    has = lib.vqvae_codes_abi_version()
-    if has != ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has %s %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (_lib.LIB_PATH, ABI_WORDS, has, ABI_VERSION))
-    _bound = lib
-    return lib
-
-
-def call(name, *args):
-    """Calls an int-returning entry point of the header and raises _lib.HipError on failure."""
-    _lib.check(getattr(load(), name)(*args), name)
-
-
-def _workspace(query, d, who):
-    need = getattr(load(), query)(C.byref(d))
-    if need == C.c_size_t(-1).value:
-        raise ValueError('%s: the library refuses this description' % who)
-    return (backend.workspace(need).ptr if need else None), need
+MAX_SHORT = _lib.CODES_MAX_SHORT   # min(La, Lb) of a pair
+THREADS = _lib.CODES_THREADS
+MAX_BIGRAM_K = _lib.CODES_MAX_BIGRAM_K
 
 
 # --------------------------------------------------------------------------- #
@@ -264,10 +187,10 @@ def collapse_many(codes, max_run=64):
     start, length = tables[1]
     u, dur = DeviceArray((total,), np.int32), DeviceArray((total,), np.int32)
     m, hist = DeviceArray((N,), np.int32), None if max_run is None else DeviceArray((int(max_run),), np.int64)
-    d = RunsDesc(N, 1 if max_run is None else int(max_run), total)
-    ws, need = _workspace('vqvae_codes_runs_workspace_bytes', d, who)
-    call('vqvae_codes_runs', C.byref(d), codes.indices.ptr, start, length, u.ptr, dur.ptr, m.ptr,
-         None if hist is None else hist.ptr, ws, need, _S())
+    d = _lib.CodesRunsDesc(N, 1 if max_run is None else int(max_run), total)
+    ws, need = backend.described_workspace('vqvae_codes_runs_workspace_bytes', d, who)
+    _lib.call('vqvae_codes_runs', C.byref(d), codes.indices.ptr, start, length, u.ptr, dur.ptr, m.ptr,
+              None if hist is None else hist.ptr, ws, need, _S())
     return CodeRuns(codes.tl, codes.offsets, codes.k, u, dur, m, hist, tables)
 
 
@@ -290,10 +213,10 @@ class CodeStats(object):
 
 
 def _count(who, buf, total, start, length, group, N, k, G, uni, big, invalid, accumulate=False):
-    d = HistDesc(N, k, G, int(big is not None), int(bool(accumulate)), 0, total)
-    ws, need = _workspace('vqvae_codes_hist_workspace_bytes', d, who)
-    call('vqvae_codes_hist', C.byref(d), buf.ptr, start, length, group, uni.ptr, None if big is None else big.ptr,
-         invalid.ptr, ws, need, _S())
+    d = _lib.CodesHistDesc(N, k, G, int(big is not None), int(bool(accumulate)), 0, total)
+    ws, need = backend.described_workspace('vqvae_codes_hist_workspace_bytes', d, who)
+    _lib.call('vqvae_codes_hist', C.byref(d), buf.ptr, start, length, group, uni.ptr, None if big is None else big.ptr,
+              invalid.ptr, ws, need, _S())
 
 
 def code_stats(codes, speakers=None, n_speakers=None, bigrams=True, collapsed=False, max_run=64, permutations=0, seed=0):
@@ -385,20 +308,20 @@ def compare_codes_many(codes_a, codes_b, collapse=True):
         raise ValueError('%s: side a has k = %d and side b k = %d: not codes of one codebook' % (who, codes_a.k, codes_b.k))
     la, lb = check_pairs(codes_a.tl, codes_b.tl, who)
     N = len(la)
-    d = PairDesc(N, int(np.minimum(la, lb).max()), int(codes_a.offsets[-1]), int(codes_b.offsets[-1]))
+    d = _lib.CodesPairDesc(N, int(np.minimum(la, lb).max()), int(codes_a.offsets[-1]), int(codes_b.offsets[-1]))
     keep, (sa, sb, na, nb) = _upload(codes_a.offsets[:-1].astype(np.int64), codes_b.offsets[:-1].astype(np.int64),
                                      codes_a.tl.astype(np.int32), codes_b.tl.astype(np.int32))
     out = DeviceArray((3, N), np.int32)                      # agree, dist, subs
-    raw = PairTables(sa, na, sb, nb)
-    ws, need = _workspace('vqvae_codes_agree_workspace_bytes', d, who)
-    call('vqvae_codes_agree', C.byref(d), C.byref(raw), codes_a.indices.ptr, codes_b.indices.ptr, out.ptr, ws, need, _S())
+    raw = _lib.CodesPairTables(sa, na, sb, nb)
+    ws, need = backend.described_workspace('vqvae_codes_agree_workspace_bytes', d, who)
+    _lib.call('vqvae_codes_agree', C.byref(d), C.byref(raw), codes_a.indices.ptr, codes_b.indices.ptr, out.ptr, ws, need, _S())
     if collapse:
         ra, rb = collapse_many(codes_a, None), collapse_many(codes_b, None)
-        t, a, b = PairTables(sa, ra.m.ptr, sb, rb.m.ptr), ra.u, rb.u
+        t, a, b = _lib.CodesPairTables(sa, ra.m.ptr, sb, rb.m.ptr), ra.u, rb.u
     else:
         t, a, b = raw, codes_a.indices, codes_b.indices
-    ws, need = _workspace('vqvae_codes_edit_workspace_bytes', d, who)
-    call('vqvae_codes_edit', C.byref(d), C.byref(t), a.ptr, b.ptr, out.ptr + 4 * N, out.ptr + 8 * N, ws, need, _S())
+    ws, need = backend.described_workspace('vqvae_codes_edit_workspace_bytes', d, who)
+    _lib.call('vqvae_codes_edit', C.byref(d), C.byref(t), a.ptr, b.ptr, out.ptr + 4 * N, out.ptr + 8 * N, ws, need, _S())
     got = out.get().astype(np.int64)
     len_a, len_b = (ra.lengths, rb.lengths) if collapse else (la.copy(), lb.copy())
     del keep

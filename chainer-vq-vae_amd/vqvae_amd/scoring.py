@@ -1,5 +1,5 @@
 """Held-out likelihood on the device: the teacher-forced decoder pass over a ragged list of utterances
-(csrc/ragged_decoder_abi.h states the rule, csrc/ragged_decoder.hip runs it).
+(include/vqvae_ragged_decoder.h states the rule, csrc/ragged_decoder.hip runs it).
 
     cond = frontend_many(encoder, vq, condition_embed, waves, speakers)
     s = score_many(model.decoder.ema, cond, waves)                 # Scores: nll, count, hits, bits_per_sample, total()
@@ -11,8 +11,7 @@ j is class q[j], the target q[j + 1], the condition column j of the dense tensor
 with no padding and every tap stays inside its own utterance, so a position's NLL is the same bits alone, in any list,
 at any position and for any ``chunk_bytes``.  The per-utterance sums are float64 in one written order.
 
-The entry points are declared in csrc/ragged_decoder_abi.h, which is not under include/ yet, so they are bound here
-(table, Structures, version check) and not in _lib.HEADERS.  Everything runs with dropout off under no_backprop_mode.
+Everything runs with dropout off under no_backprop_mode.
 """
 import ctypes as C
 import math
@@ -25,68 +24,9 @@ from .backend import DeviceArray
 _S = backend.stream
 _CAP = 1 << 31                     # elements of one ragged activation stay below this
 MAX_LOGIT_COLUMNS = 1 << 16        # return_logits: at most this many positions in one call (Q floats each, copied to the host)
-REDUCE_LANES = 256                 # VQVAE_RDEC_REDUCE_LANES: the lanes of the per-utterance reduce
-MAX_CLASSES = 512                  # VQVAE_RDEC_MAX_CLASSES
-MAX_DILATION = 512                 # VQVAE_RDEC_MAX_DILATION
-
-HEADER = 'ragged_decoder_abi.h'    # under csrc/
-ABI_WORDS = 'ragged-decoder ABI'
-ABI_VERSION = 1
-P = _lib.P
-
-
-class RdecDesc(C.Structure):
-    """One chunk of the ragged decoder pass."""
-    _c_name_ = 'vqvae_rdec_desc'
-    _fields_ = [(n, C.c_int32) for n in ('n', 'R', 'D', 'S', 'Q', 'Cl', 'G', 'n_blocks', 'upscale', 'reserved')] + \
-               [('ttot', C.c_int64), ('tltot', C.c_int64)]
-
-
-class RdecTables(C.Structure):
-    """The device tables of one chunk."""
-    _c_name_ = 'vqvae_rdec_tables'
-    _fields_ = [(n, P) for n in ('off', 'qoff', 'latoff', 'tl')]
-
-
-_D, _T = C.POINTER(RdecDesc), C.POINTER(RdecTables)
-# the table IS the list of symbols csrc/ragged_decoder_abi.h declares (tests/test_host_scoring.py)
-PROTOTYPES = {
-    'vqvae_ragged_decoder_abi_version': (C.c_int, []),
-    'vqvae_rdec_workspace_bytes': (C.c_size_t, [_D]),
-    'vqvae_rdec_embed': (C.c_int, [_D, _T, P, P, P, P, P]),
-    'vqvae_rdec_cond_project': (C.c_int, [_D, _T, P, P, P, P]),
-    'vqvae_rdec_cond_global': (C.c_int, [_D, P, P, P, P, P]),
-    'vqvae_rdec_gate': (C.c_int, [_D, _T, C.c_int, C.c_int, P, P, P, P, P, P]),
-    'vqvae_rdec_res_skip': (C.c_int, [_D, P, P, P, P, P, P, P, P, C.c_int, P]),
-    'vqvae_rdec_head': (C.c_int, [_D, _T, P, P, P, P, P, P, P, P, P, P, C.c_size_t, P]),
-    'vqvae_rdec_reduce': (C.c_int, [_D, _T, P, P, P, P, P]),
-}
-STRUCTS = (RdecDesc, RdecTables)
-
-_bound = None
-
-
-def load():
-    """libvqvae_hip.so with this header's entry points bound (once); another version of the header is an ImportError."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    lib = _lib.load()
-    for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(lib, name)               # AttributeError if the symbol is missing
-        fn.restype = res
-        fn.argtypes = args
-    has = lib.vqvae_ragged_decoder_abi_version()
-    if has != ABI_VERSION:
-        raise ImportError('libvqvae_hip.so at %s has %s %d, this package binds %d: rebuild it (__graft_entry__.build())'
-                          % (_lib.LIB_PATH, ABI_WORDS, has, ABI_VERSION))
-    _bound = lib
-    return lib
-
-
-def call(name, *args):
-    """Calls an int-returning entry point of the header and raises _lib.HipError on failure."""
-    _lib.check(getattr(load(), name)(*args), name)
+REDUCE_LANES = _lib.RAGGED_DECODER_REDUCE_LANES       # the lanes of the per-utterance reduce
+MAX_CLASSES = _lib.RAGGED_DECODER_MAX_CLASSES
+MAX_DILATION = _lib.RAGGED_DECODER_MAX_DILATION
 
 
 # --------------------------------------------------------------------------- #
@@ -348,12 +288,12 @@ class _Tables(object):
         raw = np.concatenate([i64.view(np.uint8), np.ascontiguousarray(tl, np.int32).view(np.uint8)])
         self.dev = backend.to_device(raw)
         p = self.dev.ptr
-        self.c = RdecTables(p, p + 8 * (n + 1), p + 8 * (2 * n + 1), p + 8 * (3 * n + 2))
+        self.c = _lib.RdecTables(p, p + 8 * (n + 1), p + 8 * (2 * n + 1), p + 8 * (3 * n + 2))
         self.ttot, self.tltot, self.off = int(off[-1]), int(latoff[-1]), off
 
 
 def _desc(dims, cond, n, ttot, tltot):
-    return RdecDesc(n, dims['R'], dims['D'], dims['S'], dims['Q'], cond.Cl, cond.G, dims['n_blocks'], cond.upscale, 0, ttot, tltot)
+    return _lib.RdecDesc(n, dims['R'], dims['D'], dims['S'], dims['Q'], cond.Cl, cond.G, dims['n_blocks'], cond.upscale, 0, ttot, tltot)
 
 
 def _run_chunk(d, tb, m, cp, cond, lat0, u0, q, bufs, nll_ptr, sum_ptr, hits_ptr, logits):
@@ -365,22 +305,22 @@ def _run_chunk(d, tb, m, cp, cond, lat0, u0, q, bufs, nll_ptr, sum_ptr, hits_ptr
     hit = bufs.get('hit', T, np.int32)
     Pl = bufs.get('P', d.n_blocks * d.D * d.tltot)
     g = bufs.get('g', d.n * d.n_blocks * d.D)
-    call('vqvae_rdec_embed', db, tc, q.ptr, m['We'].ptr, None if m['be'] is None else m['be'].ptr, x.ptr, _S())
-    call('vqvae_rdec_cond_project', db, tc, cond.local.ptr + 4 * cond.Cl * lat0, cp.Wc_all.ptr, Pl.ptr, _S())
-    call('vqvae_rdec_cond_global', db, None if cond.G == 0 else cond.global_vec.ptr + 4 * cond.G * u0, cp.Wc_all.ptr,
-         cp.bc_all.ptr, g.ptr, _S())
+    _lib.call('vqvae_rdec_embed', db, tc, q.ptr, m['We'].ptr, None if m['be'] is None else m['be'].ptr, x.ptr, _S())
+    _lib.call('vqvae_rdec_cond_project', db, tc, cond.local.ptr + 4 * cond.Cl * lat0, cp.Wc_all.ptr, Pl.ptr, _S())
+    _lib.call('vqvae_rdec_cond_global', db, None if cond.G == 0 else cond.global_vec.ptr + 4 * cond.G * u0, cp.Wc_all.ptr,
+              cp.bc_all.ptr, g.ptr, _S())
     nb = d.n_blocks
     for b, (prm, dil) in enumerate(zip(m['blocks'], m['dils'])):
         Wd, _, _, _, Wr, br, Ws, bs = prm
-        call('vqvae_rdec_gate', db, tc, b, dil, x.ptr, Wd.ptr, Pl.ptr, g.ptr, z.ptr, _S())
+        _lib.call('vqvae_rdec_gate', db, tc, b, dil, x.ptr, Wd.ptr, Pl.ptr, g.ptr, z.ptr, _S())
         last = b == nb - 1                       # the last block's residual output is not computed
-        call('vqvae_rdec_res_skip', db, z.ptr, None if last else Wr.ptr, None if last else br.ptr, Ws.ptr, bs.ptr,
-             None if last else x.ptr, None if last else x.ptr, skip.ptr, 1 if b else 0, _S())
-    need = load().vqvae_rdec_workspace_bytes(db)
+        _lib.call('vqvae_rdec_res_skip', db, z.ptr, None if last else Wr.ptr, None if last else br.ptr, Ws.ptr, bs.ptr,
+                  None if last else x.ptr, None if last else x.ptr, skip.ptr, 1 if b else 0, _S())
+    need = _lib.load().vqvae_rdec_workspace_bytes(db)
     ws = backend.workspace(need)
-    call('vqvae_rdec_head', db, tc, q.ptr, skip.ptr, m['W1'].ptr, m['b1'].ptr, m['W2'].ptr, m['b2'].ptr, nll_ptr, hit.ptr,
-         None if logits is None else logits.ptr, ws.ptr, need, _S())
-    call('vqvae_rdec_reduce', db, tc, nll_ptr, hit.ptr, sum_ptr, hits_ptr, _S())
+    _lib.call('vqvae_rdec_head', db, tc, q.ptr, skip.ptr, m['W1'].ptr, m['b1'].ptr, m['W2'].ptr, m['b2'].ptr, nll_ptr, hit.ptr,
+              None if logits is None else logits.ptr, ws.ptr, need, _S())
+    _lib.call('vqvae_rdec_reduce', db, tc, nll_ptr, hit.ptr, sum_ptr, hits_ptr, _S())
 
 
 # --------------------------------------------------------------------------- #

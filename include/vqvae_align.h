@@ -1,5 +1,5 @@
 /*
- * align_abi.h -- dynamic time warping over mel-cepstra for a RAGGED list of utterance pairs
+ * vqvae_align.h -- dynamic time warping over mel-cepstra for a RAGGED list of utterance pairs
  * (csrc/audio_align.hip, part of libvqvae_hip.so): the device side of vqvae_amd.alignment (align_many,
  * compare_aligned_many): mel-cepstral distortion along the warping path (MCD-DTW), the log-mel distance along it, and
  * the path itself.
@@ -7,8 +7,8 @@
  * The entry points are additive and follow the conventions of include/vqvae_hip.h and the add-on headers: raw
  * device pointers, asynchronous on the given stream, 0 / hipError_t / VQVAE_E_INVALID return codes with
  * vqvae_last_error_string(), arguments validated before anything is launched, writes only inside the outputs
- * and the queried workspace, every address formed in 64 bits.  The header lives beside its source and is bound by
- * vqvae_amd/alignment.py itself, as csrc/ragged_decoder_abi.h is by scoring.py.
+ * and the queried workspace, every address formed in 64 bits.  The header is an entry of the header table of
+ * vqvae_amd/_lib.py like every other.
  *
  * The rule (normative).  Everything is float64, one rounding per operation, no contraction.  Pair i aligns the Fa
  * frames of side a with the Fb frames of side b; nothing is cut to a common length.
@@ -44,10 +44,10 @@
  *      start(k) = first(k) for k <= L, else S * L - first(S + L - 1 - k),
  *      first(n) = n (n + 1) / 2 for n <= S, else S (S + 1) / 2 + (n - S) S.
  */
-#ifndef VQVAE_ALIGN_ABI_H_
-#define VQVAE_ALIGN_ABI_H_
+#ifndef VQVAE_ALIGN_H_
+#define VQVAE_ALIGN_H_
 
-#include "../../include/vqvae_hip.h"
+#include "vqvae_hip.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -109,4 +109,4 @@ int vqvae_align_path(const vqvae_align_desc* d, const vqvae_align_tables* t, con
 #ifdef __cplusplus
 }
 #endif
-#endif  /* VQVAE_ALIGN_ABI_H_ */
+#endif  /* VQVAE_ALIGN_H_ */

@@ -1,5 +1,5 @@
 /*
- * codes_abi.h -- statistics of the discrete codes of a RAGGED list of utterances (csrc/code_stats.hip, part of
+ * vqvae_codes.h -- statistics of the discrete codes of a RAGGED list of utterances (csrc/code_stats.hip, part of
  * libvqvae_hip.so): the device side of vqvae_amd.codestats (code_stats, collapse_many, compare_codes_many): runs of equal
  * codes, unigram counts per speaker and bigram counts, and per pair of utterances the frame agreement and the edit
  * distance of the two code strings.
@@ -7,8 +7,8 @@
  * The entry points are additive and follow the conventions of include/vqvae_hip.h and the add-on headers: raw
  * device pointers, asynchronous on the given stream, 0 / hipError_t / VQVAE_E_INVALID return codes with
  * vqvae_last_error_string(), arguments validated before anything is launched, writes only inside the outputs
- * and the queried workspace, every address formed in 64 bits.  The header lives beside its source and is bound by
- * vqvae_amd/codestats.py itself, as csrc/align_abi.h is by alignment.py.
+ * and the queried workspace, every address formed in 64 bits.  The header is an entry of the header table of
+ * vqvae_amd/_lib.py like every other.
  *
  * The rule (normative).  Everything is integer arithmetic: integer atomics are exact and order-free, so every launch
  * shape gives the same tables, and a pair's or an utterance's results are the same bits alone, in any list and at any
@@ -31,7 +31,7 @@
  *   4. Edit distance, unit costs, on the (La + 1) x (Lb + 1) matrix.  D(i, 0) = i, D(0, j) = j, S = 0 on both borders.
  *      Inside, with ne = (a[i-1] != b[j-1]), the candidates are taken in the order
  *          D(i-1, j-1) + ne   [diagonal],   D(i-1, j) + 1   [step along a],   D(i, j-1) + 1   [step along b];
- *      a later candidate replaces an earlier one only when it is strictly smaller (<): the tie order of align_abi.h.
+ *      a later candidate replaces an earlier one only when it is strictly smaller (<): the tie order of vqvae_align.h.
  *      Every cell carries S, the substitutions on its chosen path: the diagonal gives S_prev + ne, the other two steps
  *      S_prev.  dist = D(La, Lb), subs = S(La, Lb).  The host derives dels = (dist - subs + La - Lb) / 2,
  *      ins = (dist - subs - La + Lb) / 2 and matches = La - dels - subs.
@@ -46,10 +46,10 @@
  * within the 144 KiB (147456 bytes) that VQVAE_ALIGN_MAX_SHORT asks of the 160 KiB of a compute unit: 24 s of audio at
  * the default stride of 64 samples per code at 16 kHz on the SHORTER side.  The longer side is free (below 2^30).
  */
-#ifndef VQVAE_CODES_ABI_H_
-#define VQVAE_CODES_ABI_H_
+#ifndef VQVAE_CODES_H_
+#define VQVAE_CODES_H_
 
-#include "../../include/vqvae_hip.h"
+#include "vqvae_hip.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -121,4 +121,4 @@ int vqvae_codes_edit(const vqvae_codes_pair_desc* d, const vqvae_codes_pair_tabl
 #ifdef __cplusplus
 }
 #endif
-#endif  /* VQVAE_CODES_ABI_H_ */
+#endif  /* VQVAE_CODES_H_ */

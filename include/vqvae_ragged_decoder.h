@@ -1,14 +1,14 @@
 /*
- * ragged_decoder_abi.h -- the teacher-forced decoder pass over a RAGGED list of utterances
+ * vqvae_ragged_decoder.h -- the teacher-forced decoder pass over a RAGGED list of utterances
  * (csrc/ragged_decoder.hip, part of libvqvae_hip.so): the device side of vqvae_amd.scoring (score_many,
  * evaluate_many): per-sample negative log-likelihood of held-out speech, per-utterance sums.
  *
  * The entry points are additive and follow the conventions of include/vqvae_hip.h and the add-on headers: raw
  * device pointers, asynchronous on the given stream, 0 / hipError_t / VQVAE_E_INVALID return codes with
  * vqvae_last_error_string(), arguments validated before anything is launched, writes only inside the outputs
- * and the queried workspace, every address formed in 64 bits.  Forward only, dropout off.  The header lives
- * beside its source for now and is bound by vqvae_amd/scoring.py itself; moving it into include/ is a later,
- * deliberate edit of the header table of vqvae_amd/_lib.py.
+ * and the queried workspace, every address formed in 64 bits.  Forward only, dropout off.  The header is an entry
+ * of the header table of vqvae_amd/_lib.py like every other; its macros carry the file's stem, its functions and
+ * typedefs the shorter vqvae_rdec_.
  *
  * The rule (normative).  Utterance i has L_i samples with classes q (int32, in [0, Q)), tl_i latent frames and
  * T_i = upscale * tl_i.
@@ -47,25 +47,25 @@
  * vqvae_rdec_reduce sums in float64 in one written order: lane t of 256 adds the utterance's elements t, t + 256,
  * ... in ascending order, then the 256 partial sums are folded pairwise, s[k] += s[k + h] for h = 128, 64 .. 1.
  */
-#ifndef VQVAE_RAGGED_DECODER_ABI_H_
-#define VQVAE_RAGGED_DECODER_ABI_H_
+#ifndef VQVAE_RAGGED_DECODER_H_
+#define VQVAE_RAGGED_DECODER_H_
 
-#include "../../include/vqvae_hip.h"
+#include "vqvae_hip.h"
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define VQVAE_RDEC_MAX_CLASSES 512   /* Q: the head keeps a column tile's logits in LDS */
-#define VQVAE_RDEC_MAX_DILATION 512
-#define VQVAE_RDEC_REDUCE_LANES 256
+#define VQVAE_RAGGED_DECODER_MAX_CLASSES 512   /* Q: the head keeps a column tile's logits in LDS */
+#define VQVAE_RAGGED_DECODER_MAX_DILATION 512
+#define VQVAE_RAGGED_DECODER_REDUCE_LANES 256
 
 /* 1; independent of the other versions */
 int vqvae_ragged_decoder_abi_version(void);
 
 typedef struct {
   int32_t n;            /* utterances of this call, >= 1 */
-  int32_t R, D, S, Q;   /* residual, dilated (even), skip channels; classes, 1 .. VQVAE_RDEC_MAX_CLASSES */
+  int32_t R, D, S, Q;   /* residual, dilated (even), skip channels; classes, 1 .. VQVAE_RAGGED_DECODER_MAX_CLASSES */
   int32_t Cl, G;        /* local / global condition channels, Cl >= 1, G >= 0 */
   int32_t n_blocks;     /* residual blocks, >= 1 */
   int32_t upscale;      /* samples per latent frame, >= 1 */
@@ -101,7 +101,7 @@ int vqvae_rdec_cond_project(const vqvae_rdec_desc* d, const vqvae_rdec_tables* t
 int vqvae_rdec_cond_global(const vqvae_rdec_desc* d, const float* global_vec, const float* Wc_all,
                            const float* bias_all, float* g, vqvae_stream_t stream);
 
-/* Block `block` (0 <= block < n_blocks) with dilation 1 .. VQVAE_RDEC_MAX_DILATION: the two-tap dilated GEMM with the
+/* Block `block` (0 <= block < n_blocks) with dilation 1 .. VQVAE_RAGGED_DECODER_MAX_DILATION: the two-tap dilated GEMM with the
  * gate in its epilogue, z (D / 2, ttot); h never reaches memory.  x (R, ttot), Wd (D, R, 2), P and g as written by the
  * two calls above (whole arrays: the block's rows are picked here). */
 int vqvae_rdec_gate(const vqvae_rdec_desc* d, const vqvae_rdec_tables* t, int block, int dilation, const float* x,
@@ -128,4 +128,4 @@ int vqvae_rdec_reduce(const vqvae_rdec_desc* d, const vqvae_rdec_tables* t, cons
 #ifdef __cplusplus
 }
 #endif
-#endif  /* VQVAE_RAGGED_DECODER_ABI_H_ */
+#endif  /* VQVAE_RAGGED_DECODER_H_ */

@@ -1,4 +1,4 @@
-"""The rule of csrc/align_abi.h restated in float64 NumPy, twice: ``dtw_loops`` is a plain double loop over the cells,
+"""The rule of include/vqvae_align.h restated in float64 NumPy, twice: ``dtw_loops`` is a plain double loop over the cells,
 ``dtw_diagonals`` the same recurrence an anti-diagonal at a time (what the larger shapes are checked with).  Both return
 (cost, K, diagonal_steps, ia, ib).  ``cepstra`` and ``local_cost`` are steps 1 and 2, ``path_mae`` the along-path reduce
 with the header's lane order, ``align`` the whole of a pair from its two float32 log-mel blocks.

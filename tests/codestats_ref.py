@@ -1,4 +1,4 @@
-"""The rule of csrc/codes_abi.h restated in NumPy: ``runs`` and ``run_hist``; the counts twice, ``counts_loops`` by plain
+"""The rule of include/vqvae_codes.h restated in NumPy: ``runs`` and ``run_hist``; the counts twice, ``counts_loops`` by plain
 loops over the positions and ``counts_add_at`` by np.add.at; the edit distance twice, ``edit_loops`` cell by cell over the
 whole (La + 1) x (Lb + 1) matrix and ``edit_diagonals`` an anti-diagonal at a time keeping three diagonals only (what the
 larger shapes are checked with); ``agreement``; and the derived figures of vqvae_amd.codestats.figures written again from

@@ -1,4 +1,4 @@
-"""The rule of csrc/ragged_decoder_abi.h restated per utterance in float64 NumPy, on the oracle's own functions: the dense
+"""The rule of include/vqvae_ragged_decoder.h restated per utterance in float64 NumPy, on the oracle's own functions: the dense
 condition of cond_embed_fwd (align-corners up-sampling of the local block, the speaker vector broadcast), wavenet_fwd
 over the one-hot input and softmax_xent_fwd.  Nothing here restates a kernel: no tiles, no splits, no latent-rate
 projection.  The reduce's order IS restated, exactly (reduce_order), because the device promises those bits.
@@ -55,7 +55,7 @@ def score_utterance(dec, q, local, gvec, n_loop, n_layer, upscale=64, dtype=np.f
 
 
 def reduce_order(values, lanes=LANES):
-    """The device reduce's order (csrc/ragged_decoder_abi.h): lane t adds elements t, t + lanes, ... in ascending order
+    """The device reduce's order (include/vqvae_ragged_decoder.h): lane t adds elements t, t + lanes, ... in ascending order
     (float64, or int64 for integers), then s[k] += s[k + h] for h = lanes / 2, lanes / 4 .. 1."""
     v = np.asarray(values).reshape(-1)
     acc = np.float64 if v.dtype.kind == 'f' else np.int64

@@ -1,4 +1,4 @@
-"""Time alignment on the device (vqvae_amd.alignment, csrc/align_abi.h, csrc/audio_align.hip) against the NumPy
+"""Time alignment on the device (vqvae_amd.alignment, include/vqvae_align.h, csrc/audio_align.hip) against the NumPy
 restatement of the rule (tests/alignment_ref.py): every score, the path length, the diagonal count and the whole path
 equal it in EVERY bit, in every arrangement of the list; answers known by construction; red zones round every output and
 round exactly-sized, poisoned workspaces of the three entry points.
@@ -15,7 +15,7 @@ import pytest
 
 import alignment_ref as R
 import zoned as Z
-from vqvae_amd import alignment, metrics
+from vqvae_amd import _lib, alignment, metrics
 from vqvae_amd.corpus import ResidentCorpus
 from vqvae_amd.metrics import MelConfig
 
@@ -247,11 +247,11 @@ def _chunk(case):
 
 
 def _tables(b):
-    return alignment.AlignTables(b.off_a.ptr, b.off_b.ptr, b.cell_off.ptr, b.path_off.ptr)
+    return _lib.AlignTables(b.off_a.ptr, b.off_b.ptr, b.cell_off.ptr, b.path_off.ptr)
 
 
 def _need(query, d):
-    need = getattr(alignment.load(), query)(C.byref(d))
+    need = getattr(_lib.load(), query)(C.byref(d))
     assert need != C.c_size_t(-1).value
     return need
 
@@ -264,7 +264,7 @@ def test_cepstra_write_inside_their_output(case, gpu):
         specs = dict(lm=Z.In(lm), dct=Z.In(case.dct), c=Z.Out((lm.shape[1], CFG.n_mcep), np.float64), ws=Z.Ws(256))
 
         def run(b):
-            alignment.call('vqvae_align_cepstra', C.byref(d), side, b.lm.ptr, b.dct.ptr, b.c.ptr, b.ws.ptr, need, gpu.stream())
+            _lib.call('vqvae_align_cepstra', C.byref(d), side, b.lm.ptr, b.dct.ptr, b.c.ptr, b.ws.ptr, need, gpu.stream())
 
         out = Z.run_contract(gpu, run, specs)['c']
         assert np.array_equal(_bits(out), _bits(R.cepstra(lm, case.dct))), side
@@ -281,8 +281,8 @@ def test_dtw_and_path_write_inside_their_outputs_and_workspaces(case, gpu):
                  ws=Z.Out((need,), np.uint8, valid=np.arange(need) < int((fa * fb).sum())))
     def run(b):
         t = _tables(b)
-        alignment.call('vqvae_align_dtw', C.byref(d), C.byref(t), b.ca.ptr, b.cb.ptr, b.cost.ptr, b.klen.ptr, b.diag.ptr,
-                       b.ws.ptr, need, gpu.stream())
+        _lib.call('vqvae_align_dtw', C.byref(d), C.byref(t), b.ca.ptr, b.cb.ptr, b.cost.ptr, b.klen.ptr, b.diag.ptr,
+                  b.ws.ptr, need, gpu.stream())
 
     out = Z.run_contract(gpu, run, specs)                   # the direction table: an output here, every cell written, the same from zeros and poison
     for k, i in enumerate(ZONED):
@@ -305,8 +305,8 @@ def test_dtw_and_path_write_inside_their_outputs_and_workspaces(case, gpu):
 
         def run_path(b):
             t = _tables(b)
-            alignment.call('vqvae_align_path', C.byref(d), C.byref(t), b.dirs.ptr, b.cost.ptr, b.klen.ptr, b.la.ptr, b.lb.ptr,
-                           b.ia.ptr if paths else None, b.ib.ptr if paths else None, b.scores.ptr, b.ws.ptr, need_p, gpu.stream())
+            _lib.call('vqvae_align_path', C.byref(d), C.byref(t), b.dirs.ptr, b.cost.ptr, b.klen.ptr, b.la.ptr, b.lb.ptr,
+                      b.ia.ptr if paths else None, b.ib.ptr if paths else None, b.scores.ptr, b.ws.ptr, need_p, gpu.stream())
 
         got = Z.run_contract(gpu, run_path, specs)
         for k, i in enumerate(ZONED):
@@ -321,7 +321,7 @@ def test_dtw_and_path_write_inside_their_outputs_and_workspaces(case, gpu):
 def test_a_bad_descriptor_is_refused_without_a_launch(case, gpu):
     fa, fb, la, lb, good, off = _chunk(case)
     n = len(fa)
-    lib = alignment.load()
+    lib = _lib.load()
     need = _need('vqvae_align_dtw_workspace_bytes', good)
     bufs = dict(cost=Z.ZonedArray(gpu, shape=(n,), dtype=np.float64, name='cost'), klen=Z.ZonedArray(gpu, shape=(n,), dtype=np.int32, name='klen'),
                 diag=Z.ZonedArray(gpu, shape=(n,), dtype=np.int32, name='diag'), ws=Z.ZonedArray(gpu, shape=(need,), dtype=np.uint8, name='ws'),
@@ -329,7 +329,7 @@ def test_a_bad_descriptor_is_refused_without_a_launch(case, gpu):
     ins = dict((k, gpu.to_device(v)) for k, v in (('off_a', off[0]), ('off_b', off[1]), ('cell_off', off[2]), ('path_off', off[3]),
                                                  ('ca', R.cepstra(la, case.dct)), ('cb', R.cepstra(lb, case.dct)), ('la', la), ('lb', lb),
                                                  ('dct', case.dct)))
-    t = alignment.AlignTables(ins['off_a'].ptr, ins['off_b'].ptr, ins['cell_off'].ptr, ins['path_off'].ptr)
+    t = _lib.AlignTables(ins['off_a'].ptr, ins['off_b'].ptr, ins['cell_off'].ptr, ins['path_off'].ptr)
     st = gpu.stream()
 
     need_p = _need('vqvae_align_path_workspace_bytes', good)

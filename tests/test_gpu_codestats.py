@@ -1,4 +1,4 @@
-"""Code statistics on the device (vqvae_amd.codestats, csrc/codes_abi.h, csrc/code_stats.hip) against the NumPy restatement
+"""Code statistics on the device (vqvae_amd.codestats, include/vqvae_codes.h, csrc/code_stats.hip) against the NumPy restatement
 of the rule (tests/codestats_ref.py).  Everything the device does here is integer arithmetic, so EVERY comparison is an
 equality: runs, count tables, agreement, edit distance and substitutions, in every arrangement of the list; answers known
 by construction; red zones round every output of the four entry points.
@@ -14,7 +14,7 @@ import pytest
 
 import codestats_ref as R
 import zoned as Z
-from vqvae_amd import codestats
+from vqvae_amd import _lib, codestats
 from vqvae_amd.frontend import LatentCodes
 
 pytestmark = pytest.mark.gpu
@@ -302,7 +302,7 @@ def test_accumulate_adds_and_its_absence_clears(gpu):
 
 # ---- red zones --------------------------------------------------------------------------------------------------------------
 def _need(query, d):
-    need = getattr(codestats.load(), query)(C.byref(d))
+    need = getattr(_lib.load(), query)(C.byref(d))
     assert need == 0
     return need
 
@@ -323,14 +323,14 @@ def test_every_entry_point_writes_inside_its_outputs(gpu):
     written = np.zeros(total, bool)
     for o, w in zip(start, want):
         written[int(o):int(o) + len(w[0])] = True
-    d = codestats.RunsDesc(N, 4, total)
+    d = _lib.CodesRunsDesc(N, 4, total)
     need = _need('vqvae_codes_runs_workspace_bytes', d)
     specs = dict(codes=Z.In(flat), start=Z.In(start), len=Z.In(tl), u=Z.Out((total,), np.int32, valid=written),
                  dur=Z.Out((total,), np.int32, valid=written), m=Z.Out((N,), np.int32), hist=Z.Out((4,), np.int64), ws=Z.Ws(256))
 
     def run_runs(b):
-        codestats.call('vqvae_codes_runs', C.byref(d), b.codes.ptr, b.start.ptr, b.len.ptr, b.u.ptr, b.dur.ptr, b.m.ptr,
-                       b.hist.ptr, b.ws.ptr, need, st())
+        _lib.call('vqvae_codes_runs', C.byref(d), b.codes.ptr, b.start.ptr, b.len.ptr, b.u.ptr, b.dur.ptr, b.m.ptr,
+                  b.hist.ptr, b.ws.ptr, need, st())
 
     out = Z.run_contract(gpu, run_runs, specs)
     assert out['m'].tolist() == [len(w[0]) for w in want] and np.array_equal(out['hist'], R.run_hist([w[1] for w in want], 4))
@@ -340,7 +340,7 @@ def test_every_entry_point_writes_inside_its_outputs(gpu):
     # counts, with and without the nullable table
     groups = np.array([0, 1, 1, 0, 1], np.int32)
     for bigrams in (1, 0):
-        dh = codestats.HistDesc(N, k, 2, bigrams, 0, 0, total)
+        dh = _lib.CodesHistDesc(N, k, 2, bigrams, 0, 0, total)
         need = _need('vqvae_codes_hist_workspace_bytes', dh)
         specs = dict(codes=Z.In(flat), start=Z.In(start), len=Z.In(tl), group=Z.In(groups), uni=Z.Out((2, k), np.int64),
                      invalid=Z.Out((1,), np.int64), ws=Z.Ws(256))
@@ -348,26 +348,26 @@ def test_every_entry_point_writes_inside_its_outputs(gpu):
             specs['big'] = Z.Out((k, k), np.int64)
 
         def run_hist(b):
-            codestats.call('vqvae_codes_hist', C.byref(dh), b.codes.ptr, b.start.ptr, b.len.ptr, b.group.ptr, b.uni.ptr,
-                           b.big.ptr if bigrams else None, b.invalid.ptr, b.ws.ptr, need, st())
+            _lib.call('vqvae_codes_hist', C.byref(dh), b.codes.ptr, b.start.ptr, b.len.ptr, b.group.ptr, b.uni.ptr,
+                      b.big.ptr if bigrams else None, b.invalid.ptr, b.ws.ptr, need, st())
 
         out = Z.run_contract(gpu, run_hist, specs)
         wu, wb, wi = R.counts_loops(utts, groups, k, 2)
         assert np.array_equal(out['uni'], wu) and out['invalid'][0] == wi == 0 and (not bigrams or np.array_equal(out['big'], wb))
 
     # the two pair entry points
-    dp = codestats.PairDesc(N, int(np.minimum(tl, tlb).max()), total, totalb)
+    dp = _lib.CodesPairDesc(N, int(np.minimum(tl, tlb).max()), total, totalb)
     specs = dict(a=Z.In(flat), b=Z.In(flatb), sa=Z.In(start), na=Z.In(tl), sb=Z.In(startb), nb=Z.In(tlb), ws=Z.Ws(256))
 
     def run_agree(b):
-        t = codestats.PairTables(b.sa.ptr, b.na.ptr, b.sb.ptr, b.nb.ptr)
-        codestats.call('vqvae_codes_agree', C.byref(dp), C.byref(t), b.a.ptr, b.b.ptr, b.agree.ptr, b.ws.ptr,
-                       _need('vqvae_codes_agree_workspace_bytes', dp), st())
+        t = _lib.CodesPairTables(b.sa.ptr, b.na.ptr, b.sb.ptr, b.nb.ptr)
+        _lib.call('vqvae_codes_agree', C.byref(dp), C.byref(t), b.a.ptr, b.b.ptr, b.agree.ptr, b.ws.ptr,
+                  _need('vqvae_codes_agree_workspace_bytes', dp), st())
 
     def run_edit(b):
-        t = codestats.PairTables(b.sa.ptr, b.na.ptr, b.sb.ptr, b.nb.ptr)
-        codestats.call('vqvae_codes_edit', C.byref(dp), C.byref(t), b.a.ptr, b.b.ptr, b.dist.ptr, b.subs.ptr, b.ws.ptr,
-                       _need('vqvae_codes_edit_workspace_bytes', dp), st())
+        t = _lib.CodesPairTables(b.sa.ptr, b.na.ptr, b.sb.ptr, b.nb.ptr)
+        _lib.call('vqvae_codes_edit', C.byref(dp), C.byref(t), b.a.ptr, b.b.ptr, b.dist.ptr, b.subs.ptr, b.ws.ptr,
+                  _need('vqvae_codes_edit_workspace_bytes', dp), st())
 
     out = Z.run_contract(gpu, run_agree, dict(specs, agree=Z.Out((N,), np.int32)))
     assert out['agree'].tolist() == [R.agreement(x, y)[0] for x, y in zip(utts, other)]
@@ -389,34 +389,34 @@ def test_contradicting_tables_are_skipped_on_the_device(gpu):
         keep2, (sg, ng) = codestats._upload(start, tl)
         m, hist = gpu.DeviceArray((N,), np.int32), gpu.DeviceArray((4,), np.int64)
         u, dur = gpu.DeviceArray((total,), np.int32), gpu.DeviceArray((total,), np.int32)
-        d = codestats.RunsDesc(N, 4, total)
-        codestats.call('vqvae_codes_runs', C.byref(d), flat.ptr, sp, np_, u.ptr, dur.ptr, m.ptr, hist.ptr, None, 0, gpu.stream())
+        d = _lib.CodesRunsDesc(N, 4, total)
+        _lib.call('vqvae_codes_runs', C.byref(d), flat.ptr, sp, np_, u.ptr, dur.ptr, m.ptr, hist.ptr, None, 0, gpu.stream())
         want = [0 if i == skipped else len(R.runs(x)[0]) for i, x in enumerate(utts)]
         assert m.get().tolist() == want and hist.get().sum() == sum(want)
         out = gpu.DeviceArray((2, N), np.int32)
-        dp = codestats.PairDesc(N, 40, total, total)
-        t = codestats.PairTables(sp, np_, sg, ng)
-        codestats.call('vqvae_codes_edit', C.byref(dp), C.byref(t), flat.ptr, flat.ptr, out.ptr, out.ptr + 4 * N, None, 0, gpu.stream())
+        dp = _lib.CodesPairDesc(N, 40, total, total)
+        t = _lib.CodesPairTables(sp, np_, sg, ng)
+        _lib.call('vqvae_codes_edit', C.byref(dp), C.byref(t), flat.ptr, flat.ptr, out.ptr, out.ptr + 4 * N, None, 0, gpu.stream())
         assert out.get().tolist() == [[-1 if i == skipped else 0 for i in range(N)], [0, 0, 0]]
-        codestats.call('vqvae_codes_agree', C.byref(dp), C.byref(t), flat.ptr, flat.ptr, out.ptr, None, 0, gpu.stream())
+        _lib.call('vqvae_codes_agree', C.byref(dp), C.byref(t), flat.ptr, flat.ptr, out.ptr, None, 0, gpu.stream())
         assert out.get()[0].tolist() == [-1 if i == skipped else int(tl[i]) for i in range(N)]
-    short = codestats.PairDesc(N, 25, total, total)                                 # a shorter side above max_short: skipped
+    short = _lib.CodesPairDesc(N, 25, total, total)                                 # a shorter side above max_short: skipped
     keep, (sg, ng) = codestats._upload(start, tl)
     out = gpu.DeviceArray((2, N), np.int32)
-    t = codestats.PairTables(sg, ng, sg, ng)
-    codestats.call('vqvae_codes_edit', C.byref(short), C.byref(t), flat.ptr, flat.ptr, out.ptr, out.ptr + 4 * N, None, 0, gpu.stream())
+    t = _lib.CodesPairTables(sg, ng, sg, ng)
+    _lib.call('vqvae_codes_edit', C.byref(short), C.byref(t), flat.ptr, flat.ptr, out.ptr, out.ptr + 4 * N, None, 0, gpu.stream())
     assert out.get()[0].tolist() == [0, -1, -1]
 
 
 def test_a_bad_descriptor_is_refused_without_a_launch(gpu):
-    lib = codestats.load()
+    lib = _lib.load()
     N, k, total = 2, 4, 10
     bufs = dict((n, Z.ZonedArray(gpu, shape=s, dtype=t, name=n)) for n, s, t in (
         ('u', (total,), np.int32), ('dur', (total,), np.int32), ('m', (N,), np.int32), ('hist', (4,), np.int64),
         ('uni', (1, k), np.int64), ('big', (k, k), np.int64), ('invalid', (1,), np.int64), ('dist', (N,), np.int32), ('subs', (N,), np.int32)))
     flat = gpu.to_device(_string(total, k, 1))
     keep, (s, n_, g) = codestats._upload(np.array([0, 4], np.int64), np.array([4, 6], np.int32), np.zeros(N, np.int32))
-    tabs = codestats.PairTables(s, n_, s, n_)
+    tabs = _lib.CodesPairTables(s, n_, s, n_)
     st = gpu.stream()
 
     def runs(d, m=bufs['m'].ptr):
@@ -437,27 +437,27 @@ def test_a_bad_descriptor_is_refused_without_a_launch(gpu):
         assert rc != 0 and who in msg and words in msg, (who, rc, msg, words)
 
     for field, value, words in (('n', 0, 'n must be at least 1'), ('max_run', 0, 'max_run must be at least 1'), ('total', 1, 'total must be at least n')):
-        d = codestats.RunsDesc(N, 4, total)
+        d = _lib.CodesRunsDesc(N, 4, total)
         setattr(d, field, value)
         refused(runs(d), words)
     for field, value, words in (('n', 0, 'n must be at least 1'), ('k', 0, 'k and groups'), ('groups', 0, 'k and groups'), ('bigrams', 2, 'must be 0 or 1'),
                                 ('accumulate', 2, 'must be 0 or 1'), ('reserved', 1, 'reserved 0'), ('k', 4097, 'bigrams need k of at most 4096'),
                                 ('total', 1, 'total must be at least n')):
-        d = codestats.HistDesc(N, k, 1, 1, 0, 0, total)
+        d = _lib.CodesHistDesc(N, k, 1, 1, 0, 0, total)
         setattr(d, field, value)
         refused(hist(d), words)
     for field, value, words in (('n', 0, 'n must be at least 1'), ('max_short', 0, 'max_short must be in'),
                                 ('max_short', codestats.MAX_SHORT + 1, 'max_short must be in'), ('total_b', 1, 'total_a and total_b')):
         for entry in (agree, edit):
-            d = codestats.PairDesc(N, 6, total, total)
+            d = _lib.CodesPairDesc(N, 6, total, total)
             setattr(d, field, value)
             refused(entry(d), words)
-    refused(runs(codestats.RunsDesc(N, 4, total), m=None), 'null codes')
-    refused(hist(codestats.HistDesc(N, k, 1, 1, 0, 0, total), big=None), 'big must be given')
-    refused(hist(codestats.HistDesc(N, k, 1, 0, 0, 0, total)), 'big must be given')
-    refused(agree(codestats.PairDesc(N, 6, total, total), t=None), 'null tables')
-    refused(edit(codestats.PairDesc(N, 6, total, total), t=None), 'null tables')
-    refused(edit(codestats.PairDesc(N, 6, total, total), subs=None), 'null a, b, dist or subs')
+    refused(runs(_lib.CodesRunsDesc(N, 4, total), m=None), 'null codes')
+    refused(hist(_lib.CodesHistDesc(N, k, 1, 1, 0, 0, total), big=None), 'big must be given')
+    refused(hist(_lib.CodesHistDesc(N, k, 1, 0, 0, 0, total)), 'big must be given')
+    refused(agree(_lib.CodesPairDesc(N, 6, total, total), t=None), 'null tables')
+    refused(edit(_lib.CodesPairDesc(N, 6, total, total), t=None), 'null tables')
+    refused(edit(_lib.CodesPairDesc(N, 6, total, total), subs=None), 'null a, b, dist or subs')
     gpu.synchronize()
     for name, z in bufs.items():                            # nothing ran: every payload still holds its poison, every zone its pattern
         z.check()

@@ -1,4 +1,4 @@
-"""Held-out likelihood on the device (vqvae_amd.scoring, csrc/ragged_decoder_abi.h, csrc/ragged_decoder.hip).
+"""Held-out likelihood on the device (vqvae_amd.scoring, include/vqvae_ragged_decoder.h, csrc/ragged_decoder.hip).
 
 1. Composition independence as BIT equality of per-sample NLL, nll, count and hits: alone / reversed / beside replaced
    neighbours / three chunks against one / a ResidentCorpus read in place / evaluate_many against its two halves.
@@ -207,7 +207,7 @@ class Geo(object):
     """One chunk's geometry and its tables for direct calls."""
 
     def __init__(self, Rr, D, S, Cl, G, Q, nb, tl):
-        from vqvae_amd import scoring
+        from vqvae_amd import _lib
         self.R, self.D, self.S, self.Cl, self.G, self.Q, self.nb, self.tl = Rr, D, S, Cl, G, Q, nb, np.asarray(tl, np.int32)
         self.L = np.asarray(lengths_for(tl), np.int64)
         self.n = np.minimum(UP * self.tl.astype(np.int64), self.L - 1)
@@ -215,12 +215,12 @@ class Geo(object):
         self.qoff = np.concatenate([[0], np.cumsum(self.L)[:-1]]).astype(np.int64)
         self.latoff = np.concatenate([[0], np.cumsum(self.tl)]).astype(np.int64)
         self.T, self.TL = int(self.off[-1]), int(self.latoff[-1])
-        self.desc = scoring.RdecDesc(len(tl), Rr, D, S, Q, Cl, G, nb, UP, 0, self.T, self.TL)
+        self.desc = _lib.RdecDesc(len(tl), Rr, D, S, Q, Cl, G, nb, UP, 0, self.T, self.TL)
         self.specs = dict(off=In(self.off), qoff=In(self.qoff), latoff=In(self.latoff), tl=In(self.tl))
 
     def tables(self, b):
-        from vqvae_amd import scoring
-        return C.byref(scoring.RdecTables(b.off.ptr, b.qoff.ptr, b.latoff.ptr, b.tl.ptr))
+        from vqvae_amd import _lib
+        return C.byref(_lib.RdecTables(b.off.ptr, b.qoff.ptr, b.latoff.ptr, b.tl.ptr))
 
     def seg(self, i):
         return slice(int(self.off[i]), int(self.off[i + 1]))
@@ -252,7 +252,7 @@ def _c(a, dt):
 
 @pytest.mark.parametrize('geo', ['g40', 'g512'])
 def test_every_entry_point_alone(gpu, matmul_mode, geo):
-    from vqvae_amd import scoring
+    from vqvae_amd import _lib
     g = Geo(*GEOS[geo])
     rs = np.random.RandomState(3)
     Ch, M, Cc = g.D // 2, g.nb * g.D, g.Cl + g.G
@@ -264,7 +264,7 @@ def test_every_entry_point_alone(gpu, matmul_mode, geo):
 
     # embed
     We, be = f32(g.R, g.Q, 2), f32(g.R)
-    out = run_contract(gpu, lambda b: scoring.call('vqvae_rdec_embed', d, g.tables(b), b.q.ptr, b.W.ptr, b.b.ptr, b.x.ptr, S_()),
+    out = run_contract(gpu, lambda b: _lib.call('vqvae_rdec_embed', d, g.tables(b), b.q.ptr, b.W.ptr, b.b.ptr, b.x.ptr, S_()),
                        dict(g.specs, q=In(q, index_range=(0, g.Q)), W=In(We), b=In(be), x=Out((g.R, g.T))))
 
     def embed_ref(dt):
@@ -279,11 +279,11 @@ def test_every_entry_point_alone(gpu, matmul_mode, geo):
     Wc_all, bias_all, gv = f32(M, Cc) / np.float32(np.sqrt(Cc)), f32(M), f32(len(g.tl), g.G)
     local = [np.maximum(f32(g.Cl, int(t)), 0) for t in g.tl]
     local_flat = np.concatenate([a.reshape(-1) for a in local])
-    out = run_contract(gpu, lambda b: scoring.call('vqvae_rdec_cond_project', d, g.tables(b), b.local.ptr, b.W.ptr, b.P.ptr, S_()),
+    out = run_contract(gpu, lambda b: _lib.call('vqvae_rdec_cond_project', d, g.tables(b), b.local.ptr, b.W.ptr, b.P.ptr, S_()),
                        dict(g.specs, local=In(local_flat), W=In(Wc_all), P=Out((M, g.TL))))
     Pdev = out['P']
     judge('cond_project', Pdev, lambda dt: np.concatenate([np.matmul(_c(Wc_all[:, :g.Cl], dt), _c(a, dt)) for a in local], axis=1))
-    out = run_contract(gpu, lambda b: scoring.call('vqvae_rdec_cond_global', d, b.gv.ptr, b.W.ptr, b.bias.ptr, b.g.ptr, S_()),
+    out = run_contract(gpu, lambda b: _lib.call('vqvae_rdec_cond_global', d, b.gv.ptr, b.W.ptr, b.bias.ptr, b.g.ptr, S_()),
                        dict(gv=In(gv), W=In(Wc_all), bias=In(bias_all), g=Out((len(g.tl), M))))
     gdev = out['g']
     judge('cond_global', gdev, lambda dt: np.matmul(_c(gv, dt), _c(Wc_all[:, g.Cl:], dt).T) + _c(bias_all, dt)[None],
@@ -292,8 +292,8 @@ def test_every_entry_point_alone(gpu, matmul_mode, geo):
     # gate: block 1 of 2, a dilation longer than the shortest utterance, over the P and g the device wrote
     x, Wd = f32(g.R, g.T), f32(g.D, g.R, 2) / np.float32(np.sqrt(2 * g.R))
     for dil in (1, 128):
-        out = run_contract(gpu, lambda b: scoring.call('vqvae_rdec_gate', d, g.tables(b), 1, dil, b.x.ptr, b.Wd.ptr, b.P.ptr, b.g.ptr,
-                                                       b.z.ptr, S_()),
+        out = run_contract(gpu, lambda b: _lib.call('vqvae_rdec_gate', d, g.tables(b), 1, dil, b.x.ptr, b.Wd.ptr, b.P.ptr, b.g.ptr,
+                                                    b.z.ptr, S_()),
                            dict(g.specs, x=In(x), Wd=In(Wd), P=In(Pdev), g=In(gdev), z=Out((Ch, g.T))))
 
         def gate_h(dt, dil=dil):
@@ -320,8 +320,8 @@ def test_every_entry_point_alone(gpu, matmul_mode, geo):
     for acc, last in ((0, False), (1, False), (1, True)):
         specs = dict(z=In(z), Wr=In(Wr), br=In(br), Ws=In(Ws_), bs=In(bs), x=In(x), xo=Out((g.R, g.T), valid=np.full((g.R, g.T), not last)),
                      skip=Out(init=skip0) if acc else Out((g.S, g.T)))
-        out = run_contract(gpu, lambda b: scoring.call('vqvae_rdec_res_skip', d, b.z.ptr, None if last else b.Wr.ptr, None if last else b.br.ptr,
-                                                       b.Ws.ptr, b.bs.ptr, None if last else b.x.ptr, None if last else b.xo.ptr, b.skip.ptr, acc, S_()), specs)
+        out = run_contract(gpu, lambda b: _lib.call('vqvae_rdec_res_skip', d, b.z.ptr, None if last else b.Wr.ptr, None if last else b.br.ptr,
+                                                    b.Ws.ptr, b.bs.ptr, None if last else b.x.ptr, None if last else b.xo.ptr, b.skip.ptr, acc, S_()), specs)
         if not last:
             judge('res (accumulate %d)' % acc, out['xo'], lambda dt: np.matmul(_c(Wr, dt), _c(z, dt)) + _c(br, dt)[:, None] + _c(x, dt))
         judge('skip (accumulate %d, last %d)' % (acc, last), out['skip'],
@@ -329,7 +329,7 @@ def test_every_entry_point_alone(gpu, matmul_mode, geo):
 
     # head, with and without the logits, and the reduce over what it wrote
     W1, b1, W2, b2 = f32(g.S, g.S) / np.float32(np.sqrt(g.S)), f32(g.S), 3 * f32(g.Q, g.S) / np.float32(np.sqrt(g.S)), f32(g.Q)
-    need = scoring.load().vqvae_rdec_workspace_bytes(d)
+    need = _lib.load().vqvae_rdec_workspace_bytes(d)
     assert need == -(-4 * g.S * g.T // 256) * 256
     tgt = np.concatenate([qi[1:n + 1] for qi, n in zip(qs, g.n)])
 
@@ -347,7 +347,7 @@ def test_every_entry_point_alone(gpu, matmul_mode, geo):
                      nll=Out((g.T,)), hit=Out((g.T,), np.int32), ws=Ws(need))
         if with_logits:
             specs['logits'] = Out((g.Q, g.T))
-        outs[with_logits] = run_contract(gpu, lambda b: scoring.call(
+        outs[with_logits] = run_contract(gpu, lambda b: _lib.call(
             'vqvae_rdec_head', d, g.tables(b), b.q.ptr, b.skip.ptr, b.W1.ptr, b.b1.ptr, b.W2.ptr, b.b2.ptr, b.nll.ptr, b.hit.ptr,
             b.logits.ptr if with_logits else None, b.ws.ptr, need, S_()), specs)
     out = outs[True]
@@ -358,7 +358,7 @@ def test_every_entry_point_alone(gpu, matmul_mode, geo):
     assert np.array_equal(out['hit'], (np.argmax(y, axis=0) == tgt).astype(np.int32)), 'hit is not the arg-max (lowest index) of the logits'
     H.assert_close(out['nll'], nll_ref(np.float64), TOL, 'head nll')
 
-    red = run_contract(gpu, lambda b: scoring.call('vqvae_rdec_reduce', d, g.tables(b), b.nll.ptr, b.hit.ptr, b.s.ptr, b.h.ptr, S_()),
+    red = run_contract(gpu, lambda b: _lib.call('vqvae_rdec_reduce', d, g.tables(b), b.nll.ptr, b.hit.ptr, b.s.ptr, b.h.ptr, S_()),
                        dict(g.specs, nll=In(out['nll']), hit=In(out['hit']), s=Out((len(g.tl),), np.float64), h=Out((len(g.tl),), np.int64)))
     for i in range(len(g.tl)):
         want = R.reduce_order(out['nll'][g.seg(i)])
@@ -369,18 +369,18 @@ def test_every_entry_point_alone(gpu, matmul_mode, geo):
 
 def test_the_reduce_follows_its_written_order_on_long_utterances(gpu):
     """Bits, on lengths around the lane count and values whose float64 sum depends on the order."""
-    from vqvae_amd import scoring
+    from vqvae_amd import _lib
     n = np.array([1, 255, 256, 257, 1000, 513], np.int64)
     off = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
     rs = np.random.RandomState(9)
     nll = (rs.standard_normal(int(off[-1])) * 10.0 ** rs.randint(-6, 6, int(off[-1]))).astype(np.float32)
     hit = rs.randint(0, 2, int(off[-1])).astype(np.int32)
-    desc = scoring.RdecDesc(len(n), 8, 8, 8, 8, 8, 0, 1, 64, 0, int(off[-1]), len(n))
+    desc = _lib.RdecDesc(len(n), 8, 8, 8, 8, 8, 0, 1, 64, 0, int(off[-1]), len(n))
     keep = gpu.to_device(off)
-    tb = scoring.RdecTables(keep.ptr, None, None, None)
+    tb = _lib.RdecTables(keep.ptr, None, None, None)
     s, h = gpu.DeviceArray((len(n),), np.float64), gpu.DeviceArray((len(n),), np.int64)
     nll_dev, hit_dev = gpu.to_device(nll), gpu.to_device(hit)
-    scoring.call('vqvae_rdec_reduce', C.byref(desc), C.byref(tb), nll_dev.ptr, hit_dev.ptr, s.ptr, h.ptr, gpu.stream())
+    _lib.call('vqvae_rdec_reduce', C.byref(desc), C.byref(tb), nll_dev.ptr, hit_dev.ptr, s.ptr, h.ptr, gpu.stream())
     s, h = s.get(), h.get()
     for i in range(len(n)):
         seg = slice(int(off[i]), int(off[i + 1]))

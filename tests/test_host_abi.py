@@ -17,7 +17,8 @@ BASE = 'vqvae_hip.h'
 # adding an export is a deliberate edit of this table
 EXPORT_COUNTS = {'vqvae_hip.h': 128, 'vqvae_codebook.h': 3, 'vqvae_vq_ema.h': 5, 'vqvae_kmeans.h': 6, 'vqvae_optim.h': 6,
                  'vqvae_sampling.h': 3, 'vqvae_gen_slots.h': 3, 'vqvae_gen_cond.h': 2, 'vqvae_gen_rng.h': 5,
-                 'vqvae_corpus.h': 2, 'vqvae_ingest.h': 5, 'vqvae_ragged.h': 5, 'vqvae_metrics.h': 5, 'vqvae_pitch.h': 5}
+                 'vqvae_corpus.h': 2, 'vqvae_ingest.h': 5, 'vqvae_ragged.h': 5, 'vqvae_metrics.h': 5, 'vqvae_pitch.h': 5,
+                 'vqvae_ragged_decoder.h': 9, 'vqvae_align.h': 7, 'vqvae_codes.h': 9}
 
 # what load() calls each header when its version is not the bound one
 VERSION_WORDS = {'vqvae_hip.h': 'ABI', 'vqvae_codebook.h': 'codebook ABI', 'vqvae_vq_ema.h': 'EMA-codebook ABI',
@@ -25,7 +26,9 @@ VERSION_WORDS = {'vqvae_hip.h': 'ABI', 'vqvae_codebook.h': 'codebook ABI', 'vqva
                  'vqvae_gen_slots.h': 'slot-generation ABI', 'vqvae_gen_cond.h': 'latent-condition ABI',
                  'vqvae_gen_rng.h': 'device-uniforms ABI', 'vqvae_corpus.h': 'resident-corpus ABI',
                  'vqvae_ingest.h': 'ingest ABI', 'vqvae_ragged.h': 'ragged-front-end ABI',
-                 'vqvae_metrics.h': 'audio-metrics ABI', 'vqvae_pitch.h': 'pitch ABI'}
+                 'vqvae_metrics.h': 'audio-metrics ABI', 'vqvae_pitch.h': 'pitch ABI',
+                 'vqvae_ragged_decoder.h': 'ragged-decoder ABI', 'vqvae_align.h': 'alignment ABI',
+                 'vqvae_codes.h': 'code-statistics ABI'}
 
 # typedef'd structs of the headers that _lib mirrors with no Structure, and where they are read instead
 READ_ELSEWHERE = {'vqvae_ingest_bounds': 'vqvae_amd/ingest.py reads the array back as four int32 words per utterance'}
@@ -69,7 +72,7 @@ def test_the_registry_is_the_include_directory():
 
 def test_export_counts_are_pinned():
     assert {f: len(A.exports(f)) for f in FILES} == EXPORT_COUNTS
-    assert sum(EXPORT_COUNTS.values()) == 183
+    assert sum(EXPORT_COUNTS.values()) == 208
 
 
 def test_no_symbol_is_in_two_tables():
@@ -133,7 +136,7 @@ def test_every_integer_constant_has_exactly_one_home():
 def test_struct_layouts_are_the_compiler_s(compiled):
     declared = {name: fields for f in FILES for name, fields in A.structs(f).items()}
     mirrored = {cls._c_name_: cls for cls in _structures()}
-    assert len(mirrored) == len(_structures()) == 17
+    assert len(mirrored) == len(_structures()) == 25
     assert set(declared) == set(mirrored) | set(READ_ELSEWHERE) and not set(mirrored) & set(READ_ELSEWHERE)
     for t, cls in mirrored.items():
         assert [f for f, _ in cls._fields_] == declared[t], t

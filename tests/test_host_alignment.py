@@ -1,11 +1,11 @@
-"""CPU checks of time alignment (vqvae_amd.alignment, csrc/align_abi.h): the two NumPy restatements of the rule against
-each other and against answers known by construction, the host side of the rule (chunk plan, refusals), and the binding
-of the header that alignment.py carries itself -- the declared functions, parameter counts, struct layouts as a C99
-compiler sees them, the version error, and the source's place in the Makefile."""
+"""CPU checks of time alignment (vqvae_amd.alignment, include/vqvae_align.h): the two NumPy restatements of the rule
+against each other and against answers known by construction, the host side of the rule (chunk plan, refusals), and what
+is this header's own in the registry of vqvae_amd/_lib.py -- its literal names, structs and limits, the workspace
+queries and the source's place in the Makefile; the table against the header text, the library and the compiler's layout
+is tests/test_host_abi.py."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,7 +13,7 @@ import pytest
 import abi_headers as A
 import alignment_ref as R
 
-HEADER = os.path.join(A.CSRC, 'align_abi.h')
+HEADER = 'vqvae_align.h'
 SHAPES = [(1, 1), (1, 7), (7, 1), (2, 2), (5, 9), (9, 5), (64, 64), (63, 65), (40, 33)]
 N_MELS, N_MCEP = 12, 5
 
@@ -203,83 +203,38 @@ def test_every_refusal_names_its_reason():
         al.utterance(1)
 
 
-# ---- the header alignment.py binds itself --------------------------------------------------------------------------------------
-def _code():
-    text = open(HEADER).read()
-    return re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', text, flags=re.S))
+# ---- the header, the table -----------------------------------------------------------------------------------------------------
+NAMES = {'vqvae_align_abi_version', 'vqvae_align_cepstra_workspace_bytes', 'vqvae_align_dtw_workspace_bytes',
+         'vqvae_align_path_workspace_bytes', 'vqvae_align_cepstra', 'vqvae_align_dtw', 'vqvae_align_path'}
 
 
-def test_declared_functions_equal_the_bound_table():
+def test_the_header_is_in_the_registry_and_alignment_binds_nothing():
     from vqvae_amd import _lib, alignment
-    declared = sorted(set(re.findall(r'\b(vqvae_[a-z0-9_]+)\s*\(', _code())))
-    assert declared == sorted(alignment.PROTOTYPES) and len(declared) == 7
-    for name, (res, args) in alignment.PROTOTYPES.items():
-        found = re.findall(r'\b%s\s*\(([^()]*)\)\s*;' % name, _code())
-        assert len(found) == 1, name
-        params = found[0].strip()
-        assert (0 if params == 'void' else len(params.split(','))) == len(args), (name, params)
-    lib = alignment.load()
-    for name, (res, args) in alignment.PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-    assert lib.vqvae_align_abi_version() == alignment.ABI_VERSION == 1
-    # nothing was added to _lib's tables or namespace: the header is not under include/
-    assert not any(n in h.prototypes for n in alignment.PROTOTYPES for h in _lib.HEADERS.values())
-    assert alignment.HEADER not in os.listdir(A.INCLUDE) and not hasattr(_lib, 'AlignDesc')
-
-
-def test_struct_layouts_and_macros_are_the_compiler_s(tmp_path):
-    from vqvae_amd import _lib, alignment
-    declared = {}
-    for body, name in re.findall(r'typedef\s+struct[^{;]*\{([^}]*)\}\s*(\w+)\s*;', _code()):
-        declared[name] = [re.findall(r'\w+', declarator)[-1] for declaration in body.split(';') if declaration.strip()
-                          for declarator in declaration.split(',')]
-    mirrored = {cls._c_name_: cls for cls in alignment.STRUCTS}
-    assert set(declared) == set(mirrored) == {'vqvae_align_desc', 'vqvae_align_tables'}
-    lines = []
-    for t, cls in mirrored.items():
-        assert [f for f, _ in cls._fields_] == declared[t], t
-        lines.append('printf("%s %%d\\n", (int)sizeof(%s));' % (t, t))
-        for f, _ in cls._fields_:
-            lines.append('printf("%s.%s %%d %%d\\n", (int)offsetof(%s, %s), (int)sizeof(((%s*)0)->%s));' % (t, f, t, f, t, f))
-    macros = {'VQVAE_ALIGN_MAX_SHORT': alignment.MAX_SHORT, 'VQVAE_ALIGN_MAX_MELS': alignment.MAX_MELS,
-              'VQVAE_ALIGN_THREADS': alignment.THREADS, 'VQVAE_ALIGN_REDUCE_LANES': alignment.REDUCE_LANES}
-    assert sorted(m for m in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(VQVAE_\w+)', _code(), flags=re.M) if not m.endswith('_H_')) == sorted(macros)
-    lines += ['printf("%s %%d\\n", (int)(%s));' % (m, m) for m in macros]
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % HEADER, 'int main(void) {'] + lines + ['return 0; }', '']
-    c, exe = str(tmp_path / 'align.c'), str(tmp_path / 'align')
-    open(c, 'w').write('\n'.join(src))
-    subprocess.check_call([A.host_cc(), '-std=c99', '-o', exe, c])                # one C99 program, as abi_headers.run_c99
-    out = {ln.split()[0]: [int(v) for v in ln.split()[1:]] for ln in subprocess.check_output([exe], universal_newlines=True).splitlines()}
-    for t, cls in mirrored.items():
-        assert out[t] == [C.sizeof(cls)], t
-        for f, _ in cls._fields_:
-            d = getattr(cls, f)
-            assert out['%s.%s' % (t, f)] == [d.offset, d.size], (t, f)
-    for m, v in macros.items():
-        assert out[m] == [v], m
-    assert R.LANES == alignment.REDUCE_LANES and alignment.MAX_MELS == _lib.METRICS_MAX_MELS
-
-
-def test_a_bumped_bound_version_is_the_exact_import_error(monkeypatch):
-    from vqvae_amd import _lib, alignment
-    monkeypatch.setattr(alignment, '_bound', None)
-    monkeypatch.setattr(alignment, 'ABI_VERSION', 2)
-    with pytest.raises(ImportError) as e:
-        alignment.load()
-    assert str(e.value) == 'libvqvae_hip.so at %s has alignment ABI 1, this package binds 2: rebuild it (__graft_entry__.build())' % _lib.LIB_PATH
-    assert alignment._bound is None
+    h = _lib.HEADERS[HEADER]                                   # against the header and the library: tests/test_host_abi.py
+    assert set(h.prototypes) == NAMES and len(NAMES) == 7 and h.words == 'alignment ABI' and h.version == 1
+    assert HEADER in os.listdir(A.INCLUDE) and not any('abi_version' in open(os.path.join(A.CSRC, f)).read() for f in os.listdir(A.CSRC) if f.endswith('.h'))
+    assert set(A.structs(HEADER)) == {'vqvae_align_desc', 'vqvae_align_tables'}
+    assert (_lib.AlignDesc._c_name_, _lib.AlignTables._c_name_) == ('vqvae_align_desc', 'vqvae_align_tables')
+    assert [f for f, _ in _lib.AlignDesc._fields_] == ['n', 'n_mels', 'n_mcep', 'max_short', 'fa_tot', 'fb_tot', 'stride_a', 'stride_b',
+                                                       'cells', 'ptot']
+    assert [f for f, _ in _lib.AlignTables._fields_] == ['off_a', 'off_b', 'cell_off', 'path_off']
+    assert sorted(A.macros(HEADER)) == ['VQVAE_ALIGN_MAX_MELS', 'VQVAE_ALIGN_MAX_SHORT', 'VQVAE_ALIGN_REDUCE_LANES', 'VQVAE_ALIGN_THREADS']
+    assert (_lib.ALIGN_MAX_SHORT, _lib.ALIGN_MAX_MELS, _lib.ALIGN_THREADS, _lib.ALIGN_REDUCE_LANES) == (3072, 128, 256, 256)
+    assert (alignment.MAX_SHORT, alignment.MAX_MELS, alignment.THREADS, alignment.REDUCE_LANES) == (3072, 128, 256, 256)
+    assert R.LANES == alignment.REDUCE_LANES and _lib.ALIGN_MAX_MELS == _lib.METRICS_MAX_MELS
+    for name in ('HEADER', 'ABI_WORDS', 'ABI_VERSION', 'PROTOTYPES', 'STRUCTS', '_bound', 'load', 'call', 'AlignDesc', 'AlignTables'):
+        assert not hasattr(alignment, name), name
 
 
 def test_the_source_is_built_and_depends_on_its_header():
     srcs = re.search(r'^SRCS\s*:?=\s*(.*)$', A.make_database(), flags=re.M).group(1).split()
     assert 'audio_align.hip' in srcs
-    assert 'align_abi.h' in [os.path.basename(p) for p in A.object_rule_prerequisites()]
+    assert HEADER in [os.path.basename(p) for p in A.object_rule_prerequisites()]
 
 
 def test_the_workspace_queries_refuse_what_the_entry_points_refuse():
-    from vqvae_amd import alignment
-    lib = alignment.load()
+    from vqvae_amd import _lib, alignment
+    lib = _lib.load()
     fa, fb = np.array([5, 9], np.int64), np.array([7, 3], np.int64)
     good = alignment._desc(_cfg(), fa, fb, 14, 10)
     assert (good.max_short, good.cells, good.ptot) == (5, 35 + 27, 11 + 11)

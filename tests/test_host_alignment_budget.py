@@ -14,7 +14,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, 'chainer-vq-vae_amd', 'csrc', 'audio_align.hip')
-HEADER = os.path.join(ROOT, 'chainer-vq-vae_amd', 'csrc', 'align_abi.h')
+HEADER = os.path.join(ROOT, 'include', 'vqvae_align.h')
 
 
 @pytest.fixture(scope='module')

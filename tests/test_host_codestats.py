@@ -1,12 +1,11 @@
-"""CPU checks of the code statistics (vqvae_amd.codestats, csrc/codes_abi.h): the two NumPy restatements of the edit
+"""CPU checks of the code statistics (vqvae_amd.codestats, include/vqvae_codes.h): the two NumPy restatements of the edit
 distance and of the counts against each other and against answers known by construction, the derived figures against
-closed forms and against their restatement, every refusal, and the binding of the header that codestats.py carries itself
--- the declared functions, parameter counts, struct layouts as a C99 compiler sees them, the version error, the source's
-place in the Makefile and the workspace queries."""
+closed forms and against their restatement, every refusal, and what is this header's own in the registry of
+vqvae_amd/_lib.py -- its literal names, structs and limits, the workspace queries and the source's place in the
+Makefile; the table against the header text, the library and the compiler's layout is tests/test_host_abi.py."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,7 +13,7 @@ import pytest
 import abi_headers as A
 import codestats_ref as R
 
-HEADER = os.path.join(A.CSRC, 'codes_abi.h')
+HEADER = 'vqvae_codes.h'
 SHAPES = [(1, 1), (1, 7), (7, 1), (2, 2), (5, 9), (9, 5), (63, 65), (64, 64), (40, 33)]
 ALPHABETS = [2, 3, 128]
 
@@ -183,92 +182,49 @@ def test_the_comparison_derives_the_rest():
     assert all(getattr(c, n).dtype == np.int64 for n in ('distance', 'subs', 'ins', 'dels', 'matches', 'len_a', 'len_b', 'agree', 'overlap'))
 
 
-# ---- the header codestats.py binds itself ------------------------------------------------------------------------------------------
-def _code():
-    text = open(HEADER).read()
-    return re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', text, flags=re.S))
+# ---- the header, the table -----------------------------------------------------------------------------------------------------
+NAMES = {'vqvae_codes_abi_version', 'vqvae_codes_runs_workspace_bytes', 'vqvae_codes_hist_workspace_bytes',
+         'vqvae_codes_agree_workspace_bytes', 'vqvae_codes_edit_workspace_bytes', 'vqvae_codes_runs', 'vqvae_codes_hist',
+         'vqvae_codes_agree', 'vqvae_codes_edit'}
 
 
-def test_declared_functions_equal_the_bound_table():
+def test_the_header_is_in_the_registry_and_codestats_binds_nothing():
     from vqvae_amd import _lib, codestats
-    declared = sorted(set(re.findall(r'\b(vqvae_[a-z0-9_]+)\s*\(', _code())))
-    assert declared == sorted(codestats.PROTOTYPES) and len(declared) == 9
-    for name, (res, args) in codestats.PROTOTYPES.items():
-        found = re.findall(r'\b%s\s*\(([^()]*)\)\s*;' % name, _code())
-        assert len(found) == 1, name
-        params = found[0].strip()
-        assert (0 if params == 'void' else len(params.split(','))) == len(args), (name, params)
-    lib = codestats.load()
-    for name, (res, args) in codestats.PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-    assert lib.vqvae_codes_abi_version() == codestats.ABI_VERSION == 1
-    # nothing was added to _lib's tables or namespace: the header is not under include/
-    assert not any(n in h.prototypes for n in codestats.PROTOTYPES for h in _lib.HEADERS.values())
-    assert codestats.HEADER not in os.listdir(A.INCLUDE) and not hasattr(_lib, 'PairDesc')
-    assert codestats.ABI_WORDS == 'code-statistics ABI'
-
-
-def test_struct_layouts_and_macros_are_the_compiler_s(tmp_path):
-    from vqvae_amd import codestats
-    declared = {}
-    for body, name in re.findall(r'typedef\s+struct[^{;]*\{([^}]*)\}\s*(\w+)\s*;', _code()):
-        declared[name] = [re.findall(r'\w+', declarator)[-1] for declaration in body.split(';') if declaration.strip()
-                          for declarator in declaration.split(',')]
-    mirrored = {cls._c_name_: cls for cls in codestats.STRUCTS}
-    assert set(declared) == set(mirrored) == {'vqvae_codes_runs_desc', 'vqvae_codes_hist_desc', 'vqvae_codes_pair_desc',
-                                              'vqvae_codes_pair_tables'}
-    lines = []
-    for t, cls in mirrored.items():
-        assert [f for f, _ in cls._fields_] == declared[t], t
-        lines.append('printf("%s %%d\\n", (int)sizeof(%s));' % (t, t))
-        for f, _ in cls._fields_:
-            lines.append('printf("%s.%s %%d %%d\\n", (int)offsetof(%s, %s), (int)sizeof(((%s*)0)->%s));' % (t, f, t, f, t, f))
-    macros = {'VQVAE_CODES_MAX_SHORT': codestats.MAX_SHORT, 'VQVAE_CODES_THREADS': codestats.THREADS,
-              'VQVAE_CODES_MAX_BIGRAM_K': codestats.MAX_BIGRAM_K}
-    assert sorted(m for m in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(VQVAE_\w+)', _code(), flags=re.M) if not m.endswith('_H_')) == sorted(macros)
-    lines += ['printf("%s %%d\\n", (int)(%s));' % (m, m) for m in macros]
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % HEADER, 'int main(void) {'] + lines + ['return 0; }', '']
-    c, exe = str(tmp_path / 'codes.c'), str(tmp_path / 'codes')
-    open(c, 'w').write('\n'.join(src))
-    subprocess.check_call([A.host_cc(), '-std=c99', '-o', exe, c])                # one C99 program, as abi_headers.run_c99
-    out = {ln.split()[0]: [int(v) for v in ln.split()[1:]] for ln in subprocess.check_output([exe], universal_newlines=True).splitlines()}
-    for t, cls in mirrored.items():
-        assert out[t] == [C.sizeof(cls)], t
-        for f, _ in cls._fields_:
-            d = getattr(cls, f)
-            assert out['%s.%s' % (t, f)] == [d.offset, d.size], (t, f)
-    for m, v in macros.items():
-        assert out[m] == [v], m
-
-
-def test_a_bumped_bound_version_is_the_exact_import_error(monkeypatch):
-    from vqvae_amd import _lib, codestats
-    monkeypatch.setattr(codestats, '_bound', None)
-    monkeypatch.setattr(codestats, 'ABI_VERSION', 2)
-    with pytest.raises(ImportError) as e:
-        codestats.load()
-    assert str(e.value) == 'libvqvae_hip.so at %s has code-statistics ABI 1, this package binds 2: rebuild it (__graft_entry__.build())' % _lib.LIB_PATH
-    assert codestats._bound is None
+    h = _lib.HEADERS[HEADER]                                   # against the header and the library: tests/test_host_abi.py
+    assert set(h.prototypes) == NAMES and len(NAMES) == 9 and h.words == 'code-statistics ABI' and h.version == 1
+    assert HEADER in os.listdir(A.INCLUDE) and not any('abi_version' in open(os.path.join(A.CSRC, f)).read() for f in os.listdir(A.CSRC) if f.endswith('.h'))
+    mirrored = {'vqvae_codes_runs_desc': (_lib.CodesRunsDesc, ['n', 'max_run', 'total']),
+                'vqvae_codes_hist_desc': (_lib.CodesHistDesc, ['n', 'k', 'groups', 'bigrams', 'accumulate', 'reserved', 'total']),
+                'vqvae_codes_pair_desc': (_lib.CodesPairDesc, ['n', 'max_short', 'total_a', 'total_b']),
+                'vqvae_codes_pair_tables': (_lib.CodesPairTables, ['start_a', 'len_a', 'start_b', 'len_b'])}
+    assert set(A.structs(HEADER)) == set(mirrored)
+    for c_name, (cls, fields) in mirrored.items():
+        assert cls._c_name_ == c_name and [f for f, _ in cls._fields_] == fields, c_name
+    assert sorted(A.macros(HEADER)) == ['VQVAE_CODES_MAX_BIGRAM_K', 'VQVAE_CODES_MAX_SHORT', 'VQVAE_CODES_THREADS']
+    assert (_lib.CODES_MAX_SHORT, _lib.CODES_THREADS, _lib.CODES_MAX_BIGRAM_K) == (6143, 256, 4096)
+    assert (codestats.MAX_SHORT, codestats.THREADS, codestats.MAX_BIGRAM_K) == (6143, 256, 4096)
+    for name in ('HEADER', 'ABI_WORDS', 'ABI_VERSION', 'PROTOTYPES', 'STRUCTS', '_bound', 'load', 'call', '_workspace',
+                 'RunsDesc', 'HistDesc', 'PairDesc', 'PairTables'):
+        assert not hasattr(codestats, name), name
 
 
 def test_the_source_is_built_and_depends_on_its_header():
     srcs = re.search(r'^SRCS\s*:?=\s*(.*)$', A.make_database(), flags=re.M).group(1).split()
     assert 'code_stats.hip' in srcs
-    assert 'codes_abi.h' in [os.path.basename(p) for p in A.object_rule_prerequisites()]
+    assert HEADER in [os.path.basename(p) for p in A.object_rule_prerequisites()]
 
 
 def test_the_workspace_queries_refuse_what_the_entry_points_refuse():
-    from vqvae_amd import codestats
-    lib = codestats.load()
+    from vqvae_amd import _lib, codestats
+    lib = _lib.load()
     refused = C.c_size_t(-1).value
-    cases = (('vqvae_codes_runs_workspace_bytes', lambda: codestats.RunsDesc(3, 64, 10),
+    cases = (('vqvae_codes_runs_workspace_bytes', lambda: _lib.CodesRunsDesc(3, 64, 10),
               (('n', 0), ('max_run', 0), ('total', 2))),
-             ('vqvae_codes_hist_workspace_bytes', lambda: codestats.HistDesc(3, 4096, 2, 1, 0, 0, 10),
+             ('vqvae_codes_hist_workspace_bytes', lambda: _lib.CodesHistDesc(3, 4096, 2, 1, 0, 0, 10),
               (('n', 0), ('k', 0), ('k', 4097), ('groups', 0), ('bigrams', 2), ('accumulate', -1), ('reserved', 1), ('total', 2))),
-             ('vqvae_codes_agree_workspace_bytes', lambda: codestats.PairDesc(3, codestats.MAX_SHORT, 10, 3),
+             ('vqvae_codes_agree_workspace_bytes', lambda: _lib.CodesPairDesc(3, codestats.MAX_SHORT, 10, 3),
               (('n', 0), ('max_short', 0), ('max_short', codestats.MAX_SHORT + 1), ('total_a', 2), ('total_b', 0))),
-             ('vqvae_codes_edit_workspace_bytes', lambda: codestats.PairDesc(3, 1, 3, 10),
+             ('vqvae_codes_edit_workspace_bytes', lambda: _lib.CodesPairDesc(3, 1, 3, 10),
               (('n', 0), ('max_short', 0), ('max_short', codestats.MAX_SHORT + 1), ('total_a', 2), ('total_b', 0))))
     for query, good, bad in cases:
         assert getattr(lib, query)(C.byref(good())) == 0, query            # none of them keeps anything outside its outputs
@@ -277,7 +233,7 @@ def test_the_workspace_queries_refuse_what_the_entry_points_refuse():
             d = good()
             setattr(d, field, value)
             assert getattr(lib, query)(C.byref(d)) == refused, (query, field, value)
-    unigrams = codestats.HistDesc(3, 8192, 2, 0, 1, 0, 10)                  # k above the bigram bound without bigrams
+    unigrams = _lib.CodesHistDesc(3, 8192, 2, 0, 1, 0, 10)                  # k above the bigram bound without bigrams
     assert lib.vqvae_codes_hist_workspace_bytes(C.byref(unigrams)) == 0
 
 

@@ -17,7 +17,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, 'chainer-vq-vae_amd', 'csrc', 'code_stats.hip')
-HEADER = os.path.join(ROOT, 'chainer-vq-vae_amd', 'csrc', 'codes_abi.h')
+HEADER = os.path.join(ROOT, 'include', 'vqvae_codes.h')
 GRANULE = 8
 MEASURED = {'codes_runs_kernel': (33, 2 * 256 * 4), 'codes_hist_kernel': (14, 0), 'codes_agree_kernel': (19, 256 * 4),
             'codes_edit_kernel': (19, 0)}                    # registers, bytes of static LDS

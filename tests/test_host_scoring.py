@@ -1,11 +1,9 @@
-"""CPU checks of held-out scoring (vqvae_amd.scoring, csrc/ragged_decoder_abi.h): the float64 restatement against the
-oracle, the host side of the rule (positions, chunk plan, refusals), and the binding of the header that scoring.py
-carries itself -- the declared functions, parameter counts, struct layouts as a C99 compiler sees them, the version
-error, and the source's place in the Makefile."""
-import ctypes as C
+"""CPU checks of held-out scoring (vqvae_amd.scoring, include/vqvae_ragged_decoder.h): the float64 restatement against
+the oracle, the host side of the rule (positions, chunk plan, refusals), and what is this header's own in the registry of
+vqvae_amd/_lib.py -- its literal names, structs and limits and the source's place in the Makefile; the table against the
+header text, the library and the compiler's layout is tests/test_host_abi.py."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,7 +13,7 @@ import helpers as H
 import scoring_ref as R
 import vqvae_oracle as O
 
-HEADER = os.path.join(A.CSRC, 'ragged_decoder_abi.h')
+HEADER = 'vqvae_ragged_decoder.h'
 TL = [1, 3, 2, 1, 5, 2]
 L = [64 * t if i % 2 == 0 else 64 * t + 1 + i for i, t in enumerate(TL)]
 
@@ -134,78 +132,32 @@ def test_every_refusal_names_its_reason():
     assert scoring.MAX_LOGIT_COLUMNS == 1 << 16
 
 
-# ---- the header scoring.py binds itself ----------------------------------------------------------------------------------------
-def _code():
-    text = open(HEADER).read()
-    return re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', text, flags=re.S))
+# ---- the header, the table -----------------------------------------------------------------------------------------------------
+NAMES = {'vqvae_ragged_decoder_abi_version', 'vqvae_rdec_workspace_bytes', 'vqvae_rdec_embed', 'vqvae_rdec_cond_project',
+         'vqvae_rdec_cond_global', 'vqvae_rdec_gate', 'vqvae_rdec_res_skip', 'vqvae_rdec_head', 'vqvae_rdec_reduce'}
 
 
-def test_declared_functions_equal_the_bound_table():
+def test_the_header_is_in_the_registry_and_scoring_binds_nothing():
     from vqvae_amd import _lib, scoring
-    declared = sorted(set(re.findall(r'\b(vqvae_[a-z0-9_]+)\s*\(', _code())))
-    assert declared == sorted(scoring.PROTOTYPES) and len(declared) == 9
-    for name, (res, args) in scoring.PROTOTYPES.items():
-        found = re.findall(r'\b%s\s*\(([^()]*)\)\s*;' % name, _code())
-        assert len(found) == 1, name
-        params = found[0].strip()
-        assert (0 if params == 'void' else len(params.split(','))) == len(args), (name, params)
-    lib = scoring.load()
-    for name, (res, args) in scoring.PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-    assert lib.vqvae_ragged_decoder_abi_version() == scoring.ABI_VERSION == 1
-    # nothing was added to _lib's tables or namespace: the header is not under include/ yet
-    assert not any(n in h.prototypes for n in scoring.PROTOTYPES for h in _lib.HEADERS.values())
-    assert scoring.HEADER not in os.listdir(A.INCLUDE) and not hasattr(_lib, 'RdecDesc')
-
-
-def test_struct_layouts_and_macros_are_the_compiler_s(tmp_path):
-    from vqvae_amd import scoring
-    declared = {}
-    for body, name in re.findall(r'typedef\s+struct[^{;]*\{([^}]*)\}\s*(\w+)\s*;', _code()):
-        declared[name] = [re.findall(r'\w+', declarator)[-1] for declaration in body.split(';') if declaration.strip()
-                          for declarator in declaration.split(',')]
-    mirrored = {cls._c_name_: cls for cls in scoring.STRUCTS}
-    assert set(declared) == set(mirrored) == {'vqvae_rdec_desc', 'vqvae_rdec_tables'}
-    lines = []
-    for t, cls in mirrored.items():
-        assert [f for f, _ in cls._fields_] == declared[t], t
-        lines.append('printf("%s %%d\\n", (int)sizeof(%s));' % (t, t))
-        for f, _ in cls._fields_:
-            lines.append('printf("%s.%s %%d %%d\\n", (int)offsetof(%s, %s), (int)sizeof(((%s*)0)->%s));' % (t, f, t, f, t, f))
-    macros = {'VQVAE_RDEC_MAX_CLASSES': scoring.MAX_CLASSES, 'VQVAE_RDEC_MAX_DILATION': scoring.MAX_DILATION,
-              'VQVAE_RDEC_REDUCE_LANES': scoring.REDUCE_LANES}
-    assert sorted(m for m in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(VQVAE_\w+)', _code(), flags=re.M) if not m.endswith('_H_')) == sorted(macros)
-    lines += ['printf("%s %%d\\n", (int)(%s));' % (m, m) for m in macros]
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % HEADER, 'int main(void) {'] + lines + ['return 0; }', '']
-    c, exe = str(tmp_path / 'rdec.c'), str(tmp_path / 'rdec')
-    open(c, 'w').write('\n'.join(src))
-    subprocess.check_call([A.host_cc(), '-std=c99', '-o', exe, c])                # one C99 program, as abi_headers.run_c99
-    out = {ln.split()[0]: [int(v) for v in ln.split()[1:]] for ln in subprocess.check_output([exe], universal_newlines=True).splitlines()}
-    for t, cls in mirrored.items():
-        assert out[t] == [C.sizeof(cls)], t
-        for f, _ in cls._fields_:
-            d = getattr(cls, f)
-            assert out['%s.%s' % (t, f)] == [d.offset, d.size], (t, f)
-    for m, v in macros.items():
-        assert out[m] == [v], m
-    assert R.LANES == scoring.REDUCE_LANES
-
-
-def test_a_bumped_bound_version_is_the_exact_import_error(monkeypatch):
-    from vqvae_amd import _lib, scoring
-    monkeypatch.setattr(scoring, '_bound', None)
-    monkeypatch.setattr(scoring, 'ABI_VERSION', 2)
-    with pytest.raises(ImportError) as e:
-        scoring.load()
-    assert str(e.value) == 'libvqvae_hip.so at %s has ragged-decoder ABI 1, this package binds 2: rebuild it (__graft_entry__.build())' % _lib.LIB_PATH
-    assert scoring._bound is None
+    h = _lib.HEADERS[HEADER]                                   # against the header and the library: tests/test_host_abi.py
+    assert set(h.prototypes) == NAMES and len(NAMES) == 9 and h.words == 'ragged-decoder ABI' and h.version == 1
+    assert HEADER in os.listdir(A.INCLUDE) and not any('abi_version' in open(os.path.join(A.CSRC, f)).read() for f in os.listdir(A.CSRC) if f.endswith('.h'))
+    assert set(A.structs(HEADER)) == {'vqvae_rdec_desc', 'vqvae_rdec_tables'}
+    assert (_lib.RdecDesc._c_name_, _lib.RdecTables._c_name_) == ('vqvae_rdec_desc', 'vqvae_rdec_tables')
+    assert [f for f, _ in _lib.RdecDesc._fields_] == ['n', 'R', 'D', 'S', 'Q', 'Cl', 'G', 'n_blocks', 'upscale', 'reserved', 'ttot', 'tltot']
+    assert [f for f, _ in _lib.RdecTables._fields_] == ['off', 'qoff', 'latoff', 'tl']
+    assert sorted(A.macros(HEADER)) == ['VQVAE_RAGGED_DECODER_MAX_CLASSES', 'VQVAE_RAGGED_DECODER_MAX_DILATION',
+                                        'VQVAE_RAGGED_DECODER_REDUCE_LANES']
+    assert (_lib.RAGGED_DECODER_MAX_CLASSES, _lib.RAGGED_DECODER_MAX_DILATION, _lib.RAGGED_DECODER_REDUCE_LANES) == (512, 512, 256)
+    assert (scoring.MAX_CLASSES, scoring.MAX_DILATION, scoring.REDUCE_LANES) == (512, 512, 256) and R.LANES == scoring.REDUCE_LANES
+    for name in ('HEADER', 'ABI_WORDS', 'ABI_VERSION', 'PROTOTYPES', 'STRUCTS', '_bound', 'load', 'call', 'RdecDesc', 'RdecTables'):
+        assert not hasattr(scoring, name), name
 
 
 def test_the_source_is_built_and_depends_on_its_header():
     srcs = re.search(r'^SRCS\s*:?=\s*(.*)$', A.make_database(), flags=re.M).group(1).split()
     assert 'ragged_decoder.hip' in srcs
-    assert 'ragged_decoder_abi.h' in [os.path.basename(p) for p in A.object_rule_prerequisites()]
+    assert HEADER in [os.path.basename(p) for p in A.object_rule_prerequisites()]
 
 
 def test_the_package_exports_the_calls():

@@ -1,4 +1,4 @@
-"""Code statistics over a validation list: codestats.compare_codes_many and codestats.code_stats (csrc/codes_abi.h) timed
+"""Code statistics over a validation list: codestats.compare_codes_many and codestats.code_stats (include/vqvae_codes.h) timed
 end to end and per launch family, beside the NumPy restatement of the edit distance on the host CPU.
 usage: python tools/codes_bench.py [--rounds 3] [--utterances 300] [--seed 0] [--speakers 100] [--cpu-pairs 32]
                                    [--cpu-threads 16] [--step-timeout 300] [--out FILE]
@@ -92,7 +92,7 @@ def step(a):
             el = C.c_float(0)
             _lib.call('vqvae_event_elapsed_ms', C.byref(el), e0.h, e1.h)
             return float(el.value)
-        call0 = codestats.call
+        call0 = _lib.call
         for name, fn in (('collapsed', lambda: codestats.compare_codes_many(ca, cb, collapse=True)),
                          ('raw', lambda: codestats.compare_codes_many(ca, cb, collapse=False)),
                          ('code_stats', lambda: codestats.code_stats(ca, speakers, a.speakers))):
@@ -103,15 +103,18 @@ def step(a):
                 marks = []
 
                 def call(entry, *args):
-                    e0 = backend.Event().record(st)
-                    call0(entry, *args)
-                    marks.append((entry, e0, backend.Event().record(st)))
-                codestats.call = call
+                    if entry in FAMILIES:
+                        e0 = backend.Event().record(st)
+                        call0(entry, *args)
+                        marks.append((entry, e0, backend.Event().record(st)))
+                    else:
+                        call0(entry, *args)
+                _lib.call = call
                 try:
                     fn()
                     backend.synchronize()
                 finally:
-                    codestats.call = call0
+                    _lib.call = call0
                 for k in FAMILIES:
                     rounds[k].append(sum(elapsed(e0, e1) for entry, e0, e1 in marks if entry == k))
                     launches[k] = sum(1 for entry, _, _ in marks if entry == k)
