@@ -23,5 +23,7 @@ from .scoring import Scores, evaluate_many, score_many  # noqa: F401
 from .alignment import Alignment, align_many, compare_aligned_many  # noqa: F401
 from .codestats import (CodeComparison, CodeRuns, CodeStats, code_stats, collapse_many,  # noqa: F401
                         compare_codes_many)
+from .speakerid import (RaggedSpeakerFeatures, SpeakerModels, SpeakerScores, fit_speakers,  # noqa: F401
+                        identify_many, score_speakers, speaker_features)
 from .synthesis import synthesize, synthesize_many  # noqa: F401
 from .reporting import LogReport, PlotReport, PrintReport  # noqa: F401

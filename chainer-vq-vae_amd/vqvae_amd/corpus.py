@@ -136,6 +136,15 @@ class _Utterances(object):
         from .codestats import code_stats
         return code_stats(codes, speakers=self.speakers, **kw)
 
+    def fit_speakers(self, cfg, chunk_bytes=1 << 30, **kw):
+        """One Gaussian per speaker over these utterances' mel-cepstra, read in place, with these utterances' speaker ids
+        (speakerid.SpeakerModels); see speakerid.fit_speakers for the keywords."""
+        from . import speakerid
+        from .metrics import features_many
+        speakerid.feature_dim(cfg, kw.get('deltas', True), 'fit_speakers')
+        speakerid._speaker_ids(self.speakers, kw.get('n_speakers'), len(self), 'fit_speakers')
+        return speakerid.fit_speakers(features_many(self, cfg, chunk_bytes=chunk_bytes), self.speakers, **kw)
+
 
 class ResidentCorpus(_Utterances):
     """``waves``: loaded, silence-trimmed waveforms (what inputs.crop_or_pad takes); ``speakers``: one int id each.
