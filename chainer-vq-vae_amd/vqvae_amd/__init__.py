@@ -20,6 +20,7 @@ from .frontend import (LatentCodes, condition_many, encode_many, frontend_many, 
 from .metrics import MelConfig, RaggedFeatures, compare_many, features_many  # noqa: F401
 from .pitch import PitchConfig, RaggedPitch, compare_pitch_many, pitch_many  # noqa: F401
 from .scoring import Scores, evaluate_many, score_many  # noqa: F401
+from .scoring_mol import MolScores, evaluate_many_mol, score_many_mol  # noqa: F401
 from .alignment import Alignment, align_many, compare_aligned_many  # noqa: F401
 from .codestats import (CodeComparison, CodeRuns, CodeStats, code_stats, collapse_many,  # noqa: F401
                         compare_codes_many)

@@ -130,6 +130,12 @@ class _Utterances(object):
         from .scoring import score_many
         return score_many(wavenet, condition, self, chunk_bytes, per_sample, return_logits)
 
+    def score_mol(self, wavenet, condition, chunk_bytes=1 << 30, per_sample=False, return_params=False):
+        """``score`` for a mixture-of-logistics decoder (scoring_mol.MolScores): inputs and targets are the samples, read in
+        place from the corpus buffer; see scoring_mol.score_many_mol."""
+        from .scoring_mol import score_many_mol
+        return score_many_mol(wavenet, condition, self, chunk_bytes, per_sample, return_params)
+
     def code_stats(self, codes, **kw):
         """Usage, speaker leakage and durations of these utterances' codes (``encode``'s result) with these utterances'
         speaker ids as the groups (codestats.CodeStats); see codestats.code_stats for the keywords."""

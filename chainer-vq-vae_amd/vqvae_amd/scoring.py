@@ -71,9 +71,13 @@ def plan_chunks(n, tl, lengths, dims, chunk_bytes, logits=False, who='score_many
     """Runs [(start, stop), ...] of consecutive utterances whose largest buffer stays within ``chunk_bytes``
     (ragged.plan_runs over chunk_elements).  An utterance that does not fit one chunk alone is a ValueError naming it:
     an utterance is never split across chunks."""
+    return plan_elements(chunk_elements(n, tl, lengths, dims, logits), n, chunk_bytes, who)
+
+
+def plan_elements(per, n, chunk_bytes, who):
+    """plan_chunks over a given (stages, N) table of elements."""
     if int(chunk_bytes) < 1:
         raise ValueError('%s: chunk_bytes must be positive, got %r' % (who, chunk_bytes))
-    per = chunk_elements(n, tl, lengths, dims, logits)
     worst = per.max(axis=0)
     bad = np.nonzero((4 * worst > int(chunk_bytes)) | (worst >= _CAP))[0]
     if bad.size:
@@ -149,6 +153,11 @@ def _check_decoder(wavenet, who):
     if getattr(wavenet, 'use_logistic', False):
         raise NotImplementedError('%s: a mixture-of-logistics decoder (use_logistic) is out of scope here: the pass scores '
                                   'the softmax output only' % who)
+    return _check_blocks(wavenet, who)
+
+
+def _check_blocks(wavenet, who):
+    """What the ragged decoder asks of the blocks and of the matmul mode, whatever the output (scoring_mol shares it)."""
     blocks = list(wavenet.resnet.children())
     if not blocks:
         raise ValueError('%s: the decoder has no residual blocks' % who)
@@ -245,21 +254,26 @@ def _class_source(waves, Q, who):
     sizes, source = ragged.wave_source(waves, who)
 
     def fill(start, stop, q):
-        thr = _thresholds(Q)
         x_ptr, in_off, keep = source(start, stop)
-        L = sizes[start:stop]
-        in_off = np.asarray(in_off, np.int64)
-        out = ragged.offsets(L)
-        u = 0
-        while u < len(L):                      # one call per run of utterances that lie end to end in the source
-            v = u + 1
-            while v < len(L) and in_off[v] == in_off[v - 1] + L[v - 1]:
-                v += 1
-            _lib.call('vqvae_mulaw_bins', x_ptr + 4 * int(in_off[u]), int(L[u:v].sum()), thr.ptr, thr.size, q.ptr + 4 * int(out[u]), _S())
-            u = v
+        _bin_runs(x_ptr, in_off, sizes[start:stop], Q, q)
         return keep
 
     return sizes, fill
+
+
+def _bin_runs(x_ptr, in_off, L, Q, q):
+    """The classes of utterances of ``L`` samples that start at elements ``in_off`` of the float32 buffer at ``x_ptr``,
+    end to end into the int32 device buffer q."""
+    thr = _thresholds(Q)
+    in_off = np.asarray(in_off, np.int64)
+    out = ragged.offsets(L)
+    u = 0
+    while u < len(L):                      # one call per run of utterances that lie end to end in the source
+        v = u + 1
+        while v < len(L) and in_off[v] == in_off[v - 1] + L[v - 1]:
+            v += 1
+        _lib.call('vqvae_mulaw_bins', x_ptr + 4 * int(in_off[u]), int(L[u:v].sum()), thr.ptr, thr.size, q.ptr + 4 * int(out[u]), _S())
+        u = v
 
 
 class _Buffers(object):
@@ -398,14 +412,21 @@ def evaluate_many(encoder, vq, condition_embed, wavenet, waves, speakers, chunk_
                   return_logits=False):
     """``frontend_many`` followed by ``score_many`` on the same waves: host waves are uploaded once and both passes read
     them on the device.  ``speakers``: the input's own speaker ids, or any other (the likelihood under another voice)."""
-    from .corpus import _Utterances
     from .frontend import frontend_many
-    if not isinstance(waves, _Utterances):
-        waves = list(waves)
-        host = [i for i, w in enumerate(waves) if not backend.is_device(w)]
-        if host:
-            up = backend.to_device_many([np.ascontiguousarray(waves[i], np.float32).reshape(-1) for i in host])
-            for i, a in zip(host, up):
-                waves[i] = a
+    waves = _device_waves(waves)
     cond = frontend_many(encoder, vq, condition_embed, waves, speakers, chunk_bytes)
     return score_many(wavenet, cond, waves, chunk_bytes, per_sample, return_logits)
+
+
+def _device_waves(waves):
+    """``waves`` with every host wave of a list uploaded (one batched copy); a ResidentCorpus / CorpusView as it is."""
+    from .corpus import _Utterances
+    if isinstance(waves, _Utterances):
+        return waves
+    waves = list(waves)
+    host = [i for i, w in enumerate(waves) if not backend.is_device(w)]
+    if host:
+        up = backend.to_device_many([np.ascontiguousarray(waves[i], np.float32).reshape(-1) for i in host])
+        for i, a in zip(host, up):
+            waves[i] = a
+    return waves
