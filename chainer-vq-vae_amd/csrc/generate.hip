@@ -374,8 +374,10 @@ extern "C" int vqvae_wavenet_gen_step(const vqvae_gen_desc* d, vqvae_stream_t s)
 //     takes z_l straight to the next gate, and the term in x_l -- already on its way while z_l is
 //     being computed -- is evaluated in the shadow of the z_l hand-off.  The critical path is
 //     z_0 -> z_1 -> ... -> z_{L-1}; x_{l+1} is still produced (queues, next block's shadow term) but
-//     nobody waits for it.  Same mathematics, different rounding order (~1e-6 relative on the
-//     pre-activations; the parity tests hold the 1e-4 fp32 bar against the oracle's plain order).
+//     nobody waits for it.  Same mathematics, different rounding order: against float64 the teacher-forced
+//     logits of a 12-step run measure 0.75 .. 1.20 times the error of NumPy's float32 run of the plain order in
+//     relative L2 and 0.71 .. 2.37 times in max-over-scale (both classes, every instantiation), and
+//     tests/test_gpu_gen_accuracy.py holds them to err <= 3 e32 + 1e-7 per run and per step.
 // The global sequential dependency (nothing of step t+1 can be produced before the sample of step
 // t, which needs every workgroup's step-t rows) makes single-buffered mailboxes race-free.
 //   * Two width classes, both compile-time (the chain wave's instruction count is its latency):

@@ -723,7 +723,10 @@ int vqvae_comm_destroy(void* comm);
  *      accumulate): same step semantics, same state layouts (n, C) / (ring_len, n, C) sized by the caller for
  *      its n, nothing written for sequences >= n.  A sequence's values are the same from run to run and do
  *      not depend on n or on the other sequences of the batch (within the lockstep kernels; the two kernel
- *      families sum in different orders and agree to fp32 rounding).                             */
+ *      families sum in different orders: every quantity a step leaves in caller memory -- the ring slots it
+ *      pushes, h0 / h1, z, skip_acc, s1, logits -- is within 3 e32 + 1e-7 of its float64 value in both
+ *      families, in relative L2 and in max-over-scale, e32 being the error of NumPy's float32 evaluation of the
+ *      same step: tests/test_gpu_gen_accuracy.py).                                               */
 #define VQVAE_GEN_NONE    0   /* no sampling: logits only, the caller writes x_cur (modules.py:246) */
 #define VQVAE_GEN_SOFTMAX 1   /* numpy.random.choice over softmax(y) (generate.py:135-141)          */
 #define VQVAE_GEN_MOL     2   /* softmax-weighted logistic samples (generate.py:113-133)            */
