@@ -26,5 +26,6 @@ from .codestats import (CodeComparison, CodeRuns, CodeStats, code_stats, collaps
                         compare_codes_many)
 from .speakerid import (RaggedSpeakerFeatures, SpeakerModels, SpeakerScores, fit_speakers,  # noqa: F401
                         identify_many, score_speakers, speaker_features)
+from .segmental import SegmentalCodes, segment_latents, segment_many  # noqa: F401
 from .synthesis import synthesize, synthesize_many  # noqa: F401
 from .reporting import LogReport, PlotReport, PrintReport  # noqa: F401

@@ -124,6 +124,12 @@ class _Utterances(object):
         from .frontend import encode_corpus
         return encode_corpus(self, encoder, vq, chunk_bytes)
 
+    def segment(self, encoder, vq, penalties, chunk_bytes=1 << 30):
+        """The duration-penalised codes of these utterances under every penalty (segmental.SegmentalCodes), read in place
+        like ``encode``; see segmental.segment_many."""
+        from .segmental import segment_corpus
+        return segment_corpus(self, encoder, vq, penalties, chunk_bytes)
+
     def score(self, wavenet, condition, chunk_bytes=1 << 30, per_sample=False, return_logits=False):
         """The likelihood of these utterances under ``wavenet`` given ``condition`` (scoring.Scores): the samples are
         binned in place from the corpus buffer; see scoring.score_many."""

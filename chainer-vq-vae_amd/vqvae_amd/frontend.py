@@ -260,9 +260,11 @@ class _Buffers(object):
         return self.bufs[i]
 
 
-def _encode_chunk(enc, W, tb, x_ptr, bufs, idx_ptr, want_e, latents=None):
+def _encode_chunk(enc, W, tb, x_ptr, bufs, idx_ptr, want_e, latents=None, hook=None, first=0):
     """Stages 1..6 and the nearest-code search of one chunk.  Returns e (d, Ttot) when ``want_e``; the chunk's z is
-    appended to ``latents`` utterance by utterance as host arrays (d, tl_i) when that is a list."""
+    appended to ``latents`` utterance by utterance as host arrays (d, tl_i) when that is a list.  ``hook``: a callable
+    handed the chunk's z while it is on the device -- hook(z pointer, elements between its d channel rows, the chunk's
+    tables, the index of its first utterance); with None nothing more is launched."""
     from .utils import StraightThrough
     depth = len(enc)
     d, k = W.shape[1], W.shape[0]
@@ -281,6 +283,8 @@ def _encode_chunk(enc, W, tb, x_ptr, bufs, idx_ptr, want_e, latents=None):
     if latents is not None:
         z = DeviceArray((d, T), np.float32, _block=y._block, _ptr=y.ptr).get()
         latents += ragged.split(z, tb.off[depth])
+    if hook is not None:
+        hook(src, T, tb, first)
     return e
 
 
@@ -295,9 +299,10 @@ def _condition_chunk(cond, tb, s, e_ptr, bufs, local_ptr):
         src, which = y_ptr, which ^ 1
 
 
-def _run(who, encoder, vq, condition_embed, lengths, source, speakers, chunk_bytes, codes_in=None, latents=None):
+def _run(who, encoder, vq, condition_embed, lengths, source, speakers, chunk_bytes, codes_in=None, latents=None, hook=None):
     """The shared driver.  ``source(start, stop)`` -> (device pointer of x, off_in (n,)) for a run of utterances (encode);
-    ``codes_in``: LatentCodes instead of an encoder (condition_many).  Returns (LatentCodes or None, LatentCondition or None)."""
+    ``codes_in``: LatentCodes instead of an encoder (condition_many); ``hook``: see _encode_chunk (segmental.segment_many).
+    Returns (LatentCodes or None, LatentCondition or None)."""
     from .generation import LatentCondition
     W = _codebook(vq, who)
     k, d = W.shape
@@ -337,7 +342,7 @@ def _run(who, encoder, vq, condition_embed, lengths, source, speakers, chunk_byt
             if enc is not None:
                 x_ptr, in_off, keep = source(start, stop)
                 tb = _Tables(in_off, stage_lengths(lengths[start:stop], depth))
-                e = _encode_chunk(enc, W, tb, x_ptr, bufs, indices.ptr + 4 * int(lat_off[start]), cond is not None, latents)
+                e = _encode_chunk(enc, W, tb, x_ptr, bufs, indices.ptr + 4 * int(lat_off[start]), cond is not None, latents, hook, start)
                 del keep
             else:
                 tb = _Tables(np.zeros(0, np.int64), tl[None, start:stop])
