@@ -27,5 +27,7 @@ from .codestats import (CodeComparison, CodeRuns, CodeStats, code_stats, collaps
 from .speakerid import (RaggedSpeakerFeatures, SpeakerModels, SpeakerScores, fit_speakers,  # noqa: F401
                         identify_many, score_speakers, speaker_features)
 from .segmental import SegmentalCodes, segment_latents, segment_many  # noqa: F401
+from .abx import (ABXPlan, ABXScores, Frames, Items, PairDistances, abx_many, code_table, pair_distances,  # noqa: F401
+                  plan_abx)
 from .synthesis import synthesize, synthesize_many  # noqa: F401
 from .reporting import LogReport, PlotReport, PrintReport  # noqa: F401

@@ -130,6 +130,12 @@ class _Utterances(object):
         from .segmental import segment_corpus
         return segment_corpus(self, encoder, vq, penalties, chunk_bytes)
 
+    def abx(self, encoder, vq, items, **kwargs):
+        """The ABX error of ``items`` (abx.Items, in latent frames of these utterances) over the encoder's latents or the
+        codes (abx.ABXScores), read in place like ``encode``; see abx.abx_many for the keywords."""
+        from .abx import abx_corpus
+        return abx_corpus(self, encoder, vq, items, **kwargs)
+
     def score(self, wavenet, condition, chunk_bytes=1 << 30, per_sample=False, return_logits=False):
         """The likelihood of these utterances under ``wavenet`` given ``condition`` (scoring.Scores): the samples are
         binned in place from the corpus buffer; see scoring.score_many."""
